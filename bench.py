@@ -96,7 +96,77 @@ def parse():
                     "batch and print {n_gpus, exchange}: the launcher's own test (gloo when there is no GPU)")
     ap.add_argument("--no-secondary", action="store_true", help="default run only: do not measure the edit (C3) and POA (C4-shaped) workloads beside the headline one")
     ap.add_argument("--no-exchange", action="store_true", help="skip the scatter / align / gather self-check of the shard exchange after the timed region")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what the last of them computed (rank 0's batch) as DIR/<name>.npy (e.g. bench_outputs/), "
+                    "float64, at most 64 MB in all: the records of every pair (a fixed, seeded sample of %d above that many) and the CIGAR words of a seeded "
+                    "sample of them; poa: every program's result and a seeded sample of the walks or row blocks" % DUMP_RECORDS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: all arrays together
+DUMP_RECORDS = 131072       # pairs / programs whose records are written whole; a seeded sample of this many above it
+
+
+def dump_sample(n, k):
+    """a fixed, seeded choice of k of n items (all of them when n <= k), in ascending order"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n, k, replace=False)).astype(np.int64)
+
+
+def dump_prefix(order, bound, budget):
+    """the longest prefix of `order` (a seeded permutation) whose upper bounds of output words, bound[i], fit in `budget` words: which items' variable-length
+    outputs are written, fixed by the inputs alone"""
+    fit = np.cumsum(bound[order].astype(np.float64)) <= budget
+    return np.sort(order[:int(fit.sum()) if fit.all() else int(np.argmin(fit))])
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64 (each value an integer well below 2**53, so exactly); -> what the JSON line reports"""
+    conv = {k: np.ascontiguousarray(np.asarray(v).astype(np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_BYTES, "--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": os.path.abspath(path), "bytes": total, "arrays": {k: list(a.shape) for k, a in conv.items()}}
+
+
+def dump_pairwise(path, n, out, off, status, qlen, tlen, d_cig):
+    """the pairwise paths' outputs: records (score, qb, qe, tb, te, mat, mis, ins, del, aln) and status of every pair (or of a seeded sample), and the CIGAR
+    words of a seeded sample of those pairs, as many as fit in the rest of the budget (a pair has at most qlen + tlen words)"""
+    import torch
+    idx = dump_sample(n, DUMP_RECORDS)
+    budget = (DUMP_BYTES - 8 * (14 * len(idx) + 1) - 4096) // 8
+    order = np.random.default_rng(SEED + 1).permutation(idx)
+    cpairs = dump_prefix(order, qlen.astype(np.int64) + tlen.astype(np.int64), budget)
+    coff = np.zeros(len(cpairs) + 1, dtype=np.int64)
+    coff[1:] = np.cumsum(off[cpairs + 1] - off[cpairs])
+    parts = [d_cig[int(off[k]):int(off[k + 1])] for k in cpairs]
+    cig = torch.cat(parts).cpu().numpy().view(np.uint32) if parts else np.zeros(0, np.uint32)
+    return dump_outputs(path, {"pair_index": idx, "records": out[idx], "status": status[idx], "cigar_pair_index": cpairs, "cigar_offsets": coff, "cigar": cig})
+
+
+def dump_poa_graph(path, res, packed, launch, cap):
+    """the graph-form POA sweep's outputs: every program's result (maxscr, maxidx, maxoff, status, nevents, fin_node, fin_x; not `reserved`, where the walk
+    landed in the packed buffer, which is the order the programs finished in) and the walk words (node << 3 | bt) of a seeded sample of programs, as many as
+    fit in the rest of the budget (a program has at most its event_cap words).  Programs in launch order; res[k] came from launch launch[k]."""
+    fields = [f for f in res.dtype.names if f != "reserved"]
+    idx = dump_sample(len(res), DUMP_RECORDS)
+    budget = (DUMP_BYTES - 8 * ((len(fields) + 3) * len(idx) + 1) - 4096) // 8
+    wp = dump_prefix(np.random.default_rng(SEED + 1).permutation(idx), cap, budget)
+    walks = []
+    for k in wp:
+        ne = min(max(int(res[k]["nevents"]), 0), int(cap[k])) if res[k]["status"] == 0 else 0
+        walks.append(packed[launch[k]][int(res[k]["reserved"]):int(res[k]["reserved"]) + ne])
+    woff = np.zeros(len(wp) + 1, dtype=np.int64)
+    woff[1:] = np.cumsum([len(w) for w in walks])
+    return dump_outputs(path, {"program_index": idx, "results": np.stack([res[f][idx] for f in fields], axis=1), "walk_program_index": wp, "walk_offsets": woff,
+                               "walks": np.concatenate(walks) if walks else np.zeros(0, np.uint32)})
 
 
 def ensure_ranks(args):
@@ -511,6 +581,14 @@ def main_poa_recorded(args):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        # (before the launches below run again for their kernel times)
+        res_all = np.concatenate([dv["res"].cpu().numpy().view(B.POA_RESULT_DTYPE)[:n] for _, n, _, _, dv, _ in launches])
+        packed = [dv["packed"].cpu().numpy().view(np.uint32) for _, _, _, _, dv, _ in launches]
+        launch_of = np.concatenate([np.full(n, i, dtype=np.int64) for i, (_, n, _, _, _, _) in enumerate(launches)])
+        cap = np.concatenate([[2 * (rc["slen"] + len(rc["nodes"])) + 64 for rc in rcs] for _, _, _, _, _, rcs in launches]).astype(np.int64)
+        dumped = dump_poa_graph(args.dump_outputs, res_all, packed, launch_of, cap)
     kms_tot = 0.0
     for sp, n, nn, msl, dv, _ in launches:
         launch(sp, n, nn, msl, dv)
@@ -582,6 +660,8 @@ def main_poa_recorded(args):
         "cpu_baseline": cpub,
         "lockstep_end_to_end": e2e,
     }
+    if dumped is not None:
+        line["outputs_dumped"] = dumped
     emit(line)
     ctx.close()
 
@@ -675,6 +755,21 @@ def main_poa(args):
         barrier()
     kms, klaunch, _ = ctx.last_kernel_ms()
     res = d_res.cpu().numpy().view(B.SWEEP_RESULT_DTYPE)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # every window's end cell (maxscr, maxidx, maxoff) and a seeded sample of 2**20 bytes of the row blocks the sweep wrote (block 0 of a window and the
+        # bytes of a block past bw * (piecewise + 1) + 68 are not written)
+        idx = dump_sample(nwin, DUMP_RECORDS)
+        rng = np.random.default_rng(SEED + 2)
+        m = 1 << 20
+        w = rng.choice(np.flatnonzero(blocks > 1), m)
+        j = 1 + (rng.random(m) * (blocks[w] - 1)).astype(np.int64)
+        pos = (progs["first_block"][w].astype(np.int64) + j) * blk + rng.integers(0, bw * (S_oracle_piecewise(pp, bw) + 1) + 68, m)
+        pos.sort()
+        assert pos[-1] < d_rows.numel()
+        rb = d_rows[torch.from_numpy(pos).to(dev)].cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, {"window_index": idx, "results": np.stack([res[f][idx] for f in ("maxscr", "maxidx", "maxoff")], axis=1),
+                                                  "row_byte_offset": pos, "row_bytes": rb})
     if rank == 0:
         import poa_support as P
         # parity spot check (outside the timed region): the K distinct programs vs the oracle, rows and results
@@ -712,6 +807,8 @@ def main_poa(args):
                          "algorithmic_bytes_per_launch": round(balg, 1)},
             "checks": {"oracle_identical_first8_programs": ident},
         }
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
         if world == 1 and args.cpu_pairs >= 0:
             line["cpu_baseline"] = poa_cpu_baseline(args, bw)
         emit(line)
@@ -842,6 +939,8 @@ def main():
     status = d_st.cpu().numpy()
     ncig = int(off[n])
     nbad = int((status != 0).sum())
+    # (before anything below reuses the CIGAR buffer: the shard exchange aligns into it)
+    dumped = dump_pairwise(args.dump_outputs, n, out, off, status, qlen, tlen, d_cig) if args.dump_outputs and rank == 0 else None
 
     # ---- outside the timed region: what a caller with HOST buffers pays (PCIe-inclusive, never `value`), and the shard exchange on this very batch
     pcie_ms = None
@@ -931,6 +1030,8 @@ def main():
                                           "launches_per_step": klaunch if dom_trace else tlaunch}},
             "checks": {"pairs_flagged": nbad, "cigar_words": ncig, "oracle_identical_first8": ident},
         }
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
         if world == 1 and args.cpu_pairs >= 0:
             line["cpu_baseline"] = cpu_baseline(args, L, bw, sc, mode)
     # ---- the shard exchange on this very batch, after the line is complete: a fault or a hang of the exchange (RCCL at more than one rank has only

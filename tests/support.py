@@ -93,6 +93,60 @@ def ref():
     return _REF
 
 
+_RECORDING = []
+
+
+class RefCalls:
+    """one reference function as a randomized test calls it, live or replayed.  With the reference build present every call goes to it; with
+    BSA_RECORD_REF set the calls are also recorded, and tests/golden/make_golden_ref_calls.py writes them to tests/golden/<name>.npz.  Without the
+    build the recorded answers are replayed in call order, each only for the very inputs it was recorded for."""
+
+    def __init__(self, name, live):
+        self.name, self.live, self.k = name, live, 0
+        self.path = os.path.join(ROOT, "tests", "golden", name + ".npz")
+        self.keys, self.outs = [], []
+        self.z = None
+        if os.environ.get("BSA_RECORD_REF"):
+            _RECORDING.append(self)
+        elif not have_ref():
+            self.z = np.load(self.path)
+            self.zkeys = self.z["keys"]
+
+    @staticmethod
+    def digest(args):
+        import hashlib
+        import json
+        h = hashlib.sha256()
+        for a in args:
+            if isinstance(a, np.ndarray):
+                h.update(np.ascontiguousarray(a).tobytes() + str((a.dtype.str, a.shape)).encode())
+            else:
+                h.update(json.dumps(a, sort_keys=True, default=lambda x: x.tolist() if hasattr(x, "tolist") else str(x)).encode())
+            h.update(b"|")
+        return h.hexdigest()
+
+    def __call__(self, *args):
+        key = self.digest(args)
+        if self.z is None:
+            out = tuple(np.asarray(x) for x in self.live(*args))
+            if _RECORDING:
+                self.keys.append(key)
+                self.outs.append(out)
+            return out
+        k = self.k
+        self.k += 1
+        assert k < len(self.zkeys) and str(self.zkeys[k]) == key, \
+            "%s: call %d is not the one recorded (regenerate with tests/golden/make_golden_ref_calls.py)" % (self.path, k)
+        return tuple(self.z["c%d_%d" % (k, j)] for j in range(int(self.z["nout"][k])))
+
+    def save(self):
+        arrs = {"keys": np.array(self.keys), "nout": np.array([len(o) for o in self.outs], np.int32)}
+        for k, out in enumerate(self.outs):
+            for j, x in enumerate(out):
+                arrs["c%d_%d" % (k, j)] = x
+        np.savez_compressed(self.path, **arrs)
+
+
 def score_matrix(mat, mis):
     m = np.empty(16, dtype=np.int8)
     for i in range(16):

@@ -107,8 +107,9 @@ def test_oracle_rejects_bad_input():
     assert n == 0 and not res.any()
 
 
-@pytest.mark.skipif(not S.have_ref(), reason="reference build (oracle/_ref) not present")
 def test_align8_oracle_vs_reference_random():
+    """(without the reference build: its answers to these very calls, tests/golden/ref_calls_align8.npz)"""
+    ref_align = S.RefCalls("ref_calls_align8", S.ref_align)
     rng = np.random.default_rng(11)
     scorings = [(2, -6, -3, -2, 0, 0), (2, -2, -4, -2, 0, 0), (2, -6, 0, -3, 0, 0), (2, -6, -3, -2, -8, -1), (1, -1, -1, -1, 0, 0)]
     n = 0
@@ -128,14 +129,15 @@ def test_align8_oracle_vs_reference_random():
         o = S.oracle_align(Q, T, mode, bw, *sc)
         if o[2] == S.ORC_ERR_TRACE:
             continue        # the reference does not terminate on these
-        rr = S.ref_align(Q, T, mode, bw, *sc)
+        rr = ref_align(Q, T, mode, bw, *sc)
         assert np.array_equal(rr[0], o[0]) and np.array_equal(rr[1], o[1]), (it, L, len(Q), bw, mode, sc)
         n += 1
     assert n > 600
 
 
-@pytest.mark.skipif(not S.have_ref(), reason="reference build (oracle/_ref) not present")
 def test_edit_oracle_vs_reference_random():
+    """(without the reference build: its answers to these very calls, tests/golden/ref_calls_edit.npz)"""
+    ref_edit = S.RefCalls("ref_calls_edit", S.ref_edit)
     rng = np.random.default_rng(12)
     for it in range(600):
         L = int(rng.choice([1, 2, 15, 63, 64, 65, 100, 129, 500, 1000, 3000]))
@@ -149,7 +151,7 @@ def test_edit_oracle_vs_reference_random():
             continue
         bw = int(rng.choice([0, 64, 128, 256]))
         mode = int(rng.choice([0, 1, 2]))
-        rr = S.ref_edit(Q, T, mode, bw)
+        rr = ref_edit(Q, T, mode, bw)
         o = S.oracle_edit(Q, T, mode, bw)
         assert np.array_equal(rr[0], o[0]) and np.array_equal(rr[1], o[1]), (it, L, len(Q), bw, mode)
 
