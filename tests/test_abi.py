@@ -60,6 +60,17 @@ def test_score_matrix_helper():
     assert [p.matrix[i] for i in range(16)] == [2 if (i >> 2) == (i & 3) else -6 for i in range(16)]
 
 
+def test_matrix_argument_arrives_in_order():
+    """make_params(matrix=...) hands the 16 bytes over as given -- matrix[qbase * 4 + tbase], not transposed, not projected"""
+    import bsalign_amd as B
+    import matrix_support as MS
+    m = MS.GENERAL["asym"]
+    p = B.make_params(0, 128, 0, 0, -3, -2, matrix=m)
+    got = np.array([p.matrix[i] for i in range(16)], dtype=np.int8)
+    assert np.array_equal(got, m) and not np.array_equal(got, MS.transposed(m))
+    assert bytes(p)[8:24] == m.tobytes()            # (mode, bandwidth, then the matrix: bsa_align_params_t)
+
+
 def test_no_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():

@@ -166,3 +166,29 @@ def test_golden_filter_is_auditable():
     for k in range(nd):
         mode, bw, M, X, O, E, Q, P = (int(x) for x in g["dropped_meta_%d" % k])
         assert S.oracle_align(g["dropped_q_%d" % k], g["dropped_t_%d" % k], mode, bw, M, X, O, E, Q, P)[2] == S.ORC_ERR_TRACE
+
+
+def test_align8_oracle_vs_reference_custom_matrices():
+    """general 4 x 4 substitution matrices (tests/matrix_support.py: asymmetric, transition / transversion, positive mismatches,
+    non-positive diagonal entries, all-positive, all-negative, both sides of every exact-arithmetic guard bound), all three modes,
+    bandwidths 0 / 16 / 48 / 64 / 128 / 256, linear, affine and two-piece gaps
+    (without the reference build: its answers to these very calls, tests/golden/ref_calls_align8_mtx.npz)"""
+    import matrix_support as MS
+    ref_align = S.RefCalls("ref_calls_align8_mtx", S.ref_align)
+    rng = np.random.default_rng(23)
+    n = flagged = 0
+    for name, (mtx, gaps) in MS.CATALOGUE.items():
+        models = (gaps, MS.LINEAR, MS.TWOPIECE) if name in MS.GENERAL else (gaps,)
+        for bw in (0, 16, 48, 64, 128, 256):
+            for mode in (S.MODE_GLOBAL, S.MODE_OVERLAP, S.MODE_EXTEND):
+                for gp in models:
+                    lens = [1, 15, 16, 17, 63, 64, 65, 300] + ([bw - 1, bw, bw + 1] if bw else []) + ([1500] if rng.random() < 0.2 else [])
+                    for q, t in MS.mk_pairs(rng, 2 if len(models) == 1 else 1, bw, lens=lens):
+                        o = S.oracle_align(q, t, mode, bw, 0, 0, *gp, mtx=mtx)
+                        if o[2] == S.ORC_ERR_TRACE:
+                            flagged += 1
+                            continue        # the reference does not terminate on these
+                        rr = ref_align(q, t, mode, bw, 0, 0, *gp, mtx)
+                        assert np.array_equal(rr[0], o[0]) and np.array_equal(rr[1], o[1]), (name, len(q), len(t), bw, mode, gp)
+                        n += 1
+    assert n > 700 and flagged < n // 8, (n, flagged)
