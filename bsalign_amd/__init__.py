@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSA_LIB_PATH") or os.path.join(_HERE, "libbsalign_hip.so")      # BSA_LIB_PATH: development builds
 
 MODE_GLOBAL, MODE_OVERLAP, MODE_EXTEND = 0, 1, 2
+MODE_ROWRECORDS, MODE_SCORE_ONLY = 0x100, 0x400       # flags OR-ed into the mode (include/bsalign_hip.h)
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
@@ -289,6 +290,19 @@ class Context:
     def align_batch(self, pairs, par, cigar_cap=None):
         """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status)"""
         return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap)
+
+    def align_scores(self, pairs, par):
+        """bsa_align_batch with BSA_MODE_SCORE_ONLY OR-ed into par.mode and no CIGAR arena: returns (results, status); score, qe and te as
+        align_batch returns them, the fields only a traceback finds are -1"""
+        sp = AlignParams.from_buffer_copy(par)
+        sp.mode = par.mode | MODE_SCORE_ONLY
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        n = len(pairs)
+        out = np.zeros(n, dtype=RESULT_DTYPE)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self._chk(lib().bsa_align_batch(self.h, _p(seqs), seqs.size, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(sp),
+                                        _p(out), None, 0, None, _p(status)))
+        return out, status[:n]
 
     def sweep_host(self, tasks, progs, queries, qoff, qlen, par, nblocks, want_rows=True):
         """host-pointer form of the POA sweep (bsa_sweep_host): tasks ROW_TASK_DTYPE, progs SWEEP_PROG_DTYPE,

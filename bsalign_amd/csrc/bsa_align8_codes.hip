@@ -23,9 +23,9 @@
 // ref_bw != 0 (a whole-query band run at a wider register-kernel width, bsa_api.hip): the row maximum is taken over the
 // REFERENCE's band -- ref_bw columns, or roundup(qlen, 16) when ref_bw == 1 -- in the reference's striping of it (WR cells per
 // lane), whose tie rules depend on that striping; the end record is in natural order, so only the lane boundaries move.
+// `er`: the end record (the spare rows of a code slot, or the whole slot of a score-only pair: k_align8_score_finish)
 template<int WK>
-static __device__ void codes_end_cell(const uint8_t *rows, uint32_t RB, uint32_t qlen, uint32_t tlen, uint32_t ref_bw, int &score, int &qe, int &te){
-	const bsa_code_end_t *er = (const bsa_code_end_t*)(rows + (size_t)bsa_code_rows(tlen) * RB);
+static __device__ void codes_end_cell(const bsa_code_end_t *er, uint32_t qlen, uint32_t tlen, uint32_t ref_bw, int &score, int &qe, int &te){
 	const int8_t *us = (const int8_t*)(er + 1);           // natural band order: lane l, cell x at l * W + x
 	const uint32_t W = ref_bw == 0u ? (uint32_t)WK : ref_bw == 1u ? (max(qlen, 1u) + 15u) / 16u : ref_bw / 16u;
 	// H in front of band position p, from the kernel's own 16 block starts
@@ -72,6 +72,49 @@ static __device__ void codes_end_cell(const uint8_t *rows, uint32_t RB, uint32_t
 	}
 	if(ms > best){ score = ms; qe = er->rbeg_last + (int)((uint32_t)lane * W + jj); te = (int)tlen - 1; }
 	else { score = best; qe = (int)qlen - 1; te = bte; }
+}
+template<int WK>
+static __device__ void codes_end_cell(const uint8_t *rows, uint32_t RB, uint32_t qlen, uint32_t tlen, uint32_t ref_bw, int &score, int &qe, int &te){
+	codes_end_cell<WK>((const bsa_code_end_t*)(rows + (size_t)bsa_code_rows(tlen) * RB), qlen, tlen, ref_bw, score, qe, te);
+}
+
+// BSA_MODE_SCORE_ONLY: result of a pair from the record the SCORE forward kernel left (bsa_score_rec_bytes), with the walkers' end-cell rules.
+// One thread a pair.  qb, tb, mat, mis, ins, del and aln would need the traceback: -1.  A global pair whose band never reached the query end is
+// flagged BSA_ST_TRACE with score and end cell as the walkers leave them (bsa_align_batch hands such pairs over, as on the full path).
+template<int WK>
+__global__ void __launch_bounds__(256) k_align8_score_finish(const Align8Args a, bsa_result_t *out){
+	const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+	if(g >= a.count) return;
+	const uint32_t ppos = a.first + g, pair = a.order[ppos];
+	const uint8_t *rec = a.rows + a.slot_off[ppos];
+	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
+	bsa_result_t rs;
+	rs.score = 0; rs.qe = rs.te = 0;
+	if(a.status[pair] == 0u){
+		if((a.mode & 3) == BSA_MODE_GLOBAL){
+			rs.score = *(const int*)rec;
+			if(rs.score == (int)0x80000000u) atomicOr(&a.status[pair], BSA_ST_TRACE);           // band never reached the query end (bsalign.h:4034)
+			else { rs.qe = (int)qlen; rs.te = (int)tlen; }
+		} else {
+			codes_end_cell<WK>((const bsa_code_end_t*)rec, qlen, tlen, a.ref_bw, rs.score, rs.qe, rs.te);
+			rs.qe++; rs.te++;
+		}
+	}
+	rs.qb = rs.tb = -1; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = -1;
+	out[pair] = rs;
+}
+
+hipError_t bsa_launch_align8_score_finish(const Align8Args &a, bsa_result_t *out, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	const dim3 grid((a.count + 255u) / 256u);
+	bsa_last_trace_kernel = "k_align8_score_finish";
+	switch(a.bw / 16){
+		case 4:  hipLaunchKernelGGL((k_align8_score_finish<4>), grid, dim3(256), 0, st, a, out); break;
+		case 8:  hipLaunchKernelGGL((k_align8_score_finish<8>), grid, dim3(256), 0, st, a, out); break;
+		case 16: hipLaunchKernelGGL((k_align8_score_finish<16>), grid, dim3(256), 0, st, a, out); break;
+		default: return hipErrorInvalidValue;
+	}
+	return hipGetLastError();
 }
 
 

@@ -150,7 +150,10 @@ static __device__ __forceinline__ void x_load_qcodes(const uint8_t *p, uint32_t 
 // instructions.  A reference block's dword is then M | R << 8 | field of cell c at bits 31 - 2c, 30 - 2c (bsa_common.h).
 // EXT: the two LDS areas come from the caller (k_align8_fwd_x_mix runs two shapes of this function in one launch and a block only ever one of
 // them: they share the areas instead of each instantiation carrying its own).
-template<int W, int L, int PW = 1, bool STATIC = false, int NWV = 4, bool DO2 = false, bool EXT = false>
+// SCORE (BSA_MODE_SCORE_ONLY, one-piece gaps): the recurrence and the band steering only -- no flags, no code rows, no band offsets.  The pair's slot
+// is a record of fixed size (bsa_score_rec_bytes): the final score (global) or the end record bsa_code_end_t and the last row's u bytes (overlap /
+// extend), read by k_align8_score_finish (bsa_align8_codes.hip).
+template<int W, int L, int PW = 1, bool STATIC = false, int NWV = 4, bool DO2 = false, bool EXT = false, bool SCORE = false>
 static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint32_t first_pos, const uint32_t count, const uint32_t tid_base,
 		const uint32_t row0 = 0u, const uint32_t row1 = 0xFFFFFFF8u, uint32_t *st = nullptr, uint32_t *ext_stage = nullptr, uint32_t *ext_qwin = nullptr){
 	constexpr int BW = 2 * L * W;
@@ -161,6 +164,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	constexpr int TOPBIT = 8 + ((W < 8) ? W : 8) - 1;     // accumulator bit of the first cell it holds
 	static_assert(PW == 0 || PW == 1 || (PW == 2 && ((W == 8 && (L == 8 || L == 4)) || (W == 16 && (L == 8 || L == 4)))), "two-piece gaps: bandwidth 128 (eight lanes per pair), 64 (four), 256 (eight, sixteen cells a half)");
 	static_assert(!DO2 || (PW == 1 && WR == 8), "two-bit D / Od fields: one-piece gaps, bandwidth 128");
+	static_assert(!SCORE || (PW <= 1 && !DO2 && !EXT), "score-only: one-piece gaps, plain code format, own LDS");
 	constexpr int NDO = DO2 ? W / 4 : 1;                  // accumulators of the two-bit fields (four cells each, in the high byte of a half)
 	constexpr int CWD = (PW == 2) ? WR / 4 : (WR >= 8) ? WR / 8 : 1;          // code dwords per reference block and row (two-piece gaps: eight bits a cell)
 	constexpr int ND = (PW == 2) ? 2 * W / 4 : (WR == 8) ? 2 * NACC : (WR == 16) ? 4 : (W == 8) ? 4 : 2;      // code dwords per lane and row
@@ -174,7 +178,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	const uint32_t qlen = a.qlen[pair];
 	uint32_t tlen = a.tlen[pair];
 	const uint8_t *qp = a.qst + a.qpoff[pair], *tp = a.tst + a.tpoff[pair];
-	int *begs = (int*)(a.rows + a.slot_off[ppos]);
+	int *begs = (int*)(a.rows + a.slot_off[ppos]);          // (SCORE: the pair's record)
 	uint8_t *rowp = (uint8_t*)begs + bsa_begs_bytes(tlen);
 	if(!live || a.status[pair] != 0u) tlen = 0;
 
@@ -277,8 +281,9 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 		PN = sp[64 * r++]; PM = sp[64 * r++]; HB = (int)sp[64 * r++]; svU = sp[64 * r++]; svNE = sp[64 * r++]; svNQ = sp[64 * r++];
 		rbeg = sp[64 * r++]; mov = sp[64 * r++]; cand_sc = (int)sp[64 * r++]; cand_te = (int)sp[64 * r++];
 	}
-	__shared__ uint32_t x_stage[EXT ? 1 : NWV][EXT ? 1 : 4 * ND][64];       // [wave][4 q + row of the group (CWD == 1) | ND row + dword (CWD >= 2)][lane]
-	uint32_t *const stg = EXT ? ext_stage + (size_t)(lt >> 6) * (4 * ND * 64) + (lt & 63) : &x_stage[(!EXT && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
+	constexpr bool OWNSTG = !EXT && !SCORE;
+	__shared__ uint32_t x_stage[OWNSTG ? NWV : 1][OWNSTG ? 4 * ND : 1][64];       // [wave][4 q + row of the group (CWD == 1) | ND row + dword (CWD >= 2)][lane]
+	uint32_t *const stg = EXT ? ext_stage + (size_t)(lt >> 6) * (4 * ND * 64) + (lt & 63) : &x_stage[(OWNSTG && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
 	// QUERY WINDOW (round 5).  A lane needs the W query codes of each of its two blocks on every row, at a band offset that moves by about one base a
 	// row: loaded from memory row by row that is one full round trip the wave waits for per row -- and `vmcnt` also holds the row's wait back behind the
 	// code-row stores in flight (a second such round trip per row, added as an experiment, cost 5.4 ms of the 61: 9 %).  Instead the lane keeps, in LDS
@@ -302,7 +307,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	uint32_t *const qwp = EXT ? ext_qwin + (size_t)(lt >> 6) * (2 * KD * 64) + (lt & 63) : &x_qwin[(QWIN && !EXT && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
 	uint32_t wbase = 0x40000000u;                          // band offset the window starts at (this value: no window yet)
 	int begq = 0;
-	if(tlen != 0u && first && row0 == 0u) begs[0] = 0;
+	if(!SCORE && tlen != 0u && first && row0 == 0u) begs[0] = 0;
 	uint64_t twin = 0;
 	if(row0 < tlen){ __builtin_memcpy(&twin, tp + row0, 8); twin <<= 2; }
 	// STATIC: the band never moves, so a lane's query codes are the same on every row -- loaded once
@@ -533,10 +538,11 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 			}
 			const uint32_t fm = x_max(f, mg[k]);
 			f = x_sub(fm, uk);
-			if constexpr (PW != 0) accR[k >> 3] = x_acc(accR[k >> 3], x_minu(x_sub(fm, mg[k]), ONE), TWO);
+			if constexpr (PW != 0 && !SCORE) accR[k >> 3] = x_acc(accR[k >> 3], x_minu(x_sub(fm, mg[k]), ONE), TWO);
 			const uint32_t n = x_sub(h, ee[k]);
 			const uint32_t ne = (PW == 0) ? 0u : x_minu(n, NGOQ);
-			if constexpr (DO2){
+			if constexpr (SCORE){}
+			else if constexpr (DO2){
 				const uint32_t kk = ((k & 3) == 0) ? KDO0 : ((k & 3) == 1) ? KDO1 : KDO2;
 				if((k & 3) == 3) accDO[k >> 2] = x_add(accDO[k >> 2], ne);
 				else accDO[k >> 2] = x_acc(ne, accDO[k >> 2], kk);                 // ne * K + acc
@@ -544,7 +550,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 				accD[k >> 3] = x_acc(accD[k >> 3], x_minu(n, ONE), TWO);
 				if constexpr (PW != 0) accO[k >> 3] = x_acc(accO[k >> 3], x_satsubu(ne, NGOQ1), TWO);
 			}
-			accM[k >> 3] = x_acc(accM[k >> 3], x_minu(x_sub(h, S[k]), ONE), TWO);
+			if constexpr (!SCORE) accM[k >> 3] = x_acc(accM[k >> 3], x_minu(x_sub(h, S[k]), ONE), TWO);
 			const uint32_t un = x_sub(h, v);
 			v = x_sub(h, uk);
 			if(CR == 2 && k == W / 2 - 1) vmid = v;
@@ -565,6 +571,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 		if(first) tmpU0 = (tmpU0 & 0xffff0000u) | (NGEQ & 0xffffu);
 		const uint32_t Psh = x_shift_down<L>(PN, 0u, first);           // ubegs[b] - ubegs[0] - b W gape of the block's own start
 		// ---- flags of special cells, then the code row (bsa_common.h "COMPACT slot"); M, D, R were accumulated inverted
+		if constexpr (!SCORE){
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull, 0)){
 			if(first && rbeg == 0u){
 				const uint32_t hl = hfirst & 0xffffu;
@@ -745,11 +752,13 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 				}
 			}
 		}
+		}          // (!SCORE)
 		if(act){
 			// band offsets: lane (i mod L) keeps the offset of row i, the group stores them together
 			constexpr uint32_t LM = (uint32_t)(L - 1);
 			const bool lastrow = i + 1u == tlen;
-			if constexpr (BQ16){
+			if constexpr (SCORE){}
+			else if constexpr (BQ16){
 				// Four rows of offsets are 16 bytes at an odd dword: stored as they come, every piece is a partial sector that the L2 has written back long
 				// before its neighbours arrive (48 us later).  The lane keeps its last four offsets in LDS slots of its own (slot (row >> 2) & 3) and the
 				// pair stores begs[16 k .. 16 k + 15] -- rows 16 k - 1 .. 16 k + 14, one whole line -- when row 16 k + 14 is done; what is pending at the end of
@@ -793,12 +802,13 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 			if(lastrow && mode == BSA_MODE_GLOBAL){
 				// global score = H at query column qlen - 1 of the last row (bsalign.h:4034-4037), kept in begs[tlen + 1]
 				const uint32_t pos = qlen - 1u - rbeg;
-				if(pos >= (uint32_t)BW){ if(first) begs[tlen + 1u] = (int)0x80000000u; }        // band never reached the query end
-				else if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl) begs[tlen + 1u] = score_at(pos);
+				int *const gs = SCORE ? begs : begs + tlen + 1u;          // (SCORE: the record is the score)
+				if(pos >= (uint32_t)BW){ if(first) *gs = (int)0x80000000u; }        // band never reached the query end
+				else if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl) *gs = score_at(pos);
 			} else if(lastrow){
 				// end record (bsa_common.h bsa_code_end_t): the candidates and the last row itself, per reference block, in natural
 				// band order (row_max is taken by the traceback kernel)
-				bsa_code_end_t *er = (bsa_code_end_t*)(rowp + (size_t)bsa_code_rows(tlen) * (64u * CWD));
+				bsa_code_end_t *er = SCORE ? (bsa_code_end_t*)begs : (bsa_code_end_t*)(rowp + (size_t)bsa_code_rows(tlen) * (64u * CWD));
 #pragma unroll
 				for(int q = 0; q < 16 / L; q++){ er->cand_sc[jl + L * q] = q ? BSA_SCORE_MIN : cand_sc; er->cand_te[jl + L * q] = q ? 0 : cand_te; }
 				int8_t *ub = (int8_t*)(er + 1);
@@ -897,14 +907,14 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	}
 }
 
-template<int W, int L, bool DO2 = false>
+template<int W, int L, bool DO2 = false, bool SCORE = false>
 __global__ void __launch_bounds__(256) k_align8_fwd_x(const Align8Args a){
-	x_forward<W, L, 1, false, 4, DO2>(a, a.first, a.count, blockIdx.x * 256u);
+	x_forward<W, L, 1, false, 4, DO2, false, SCORE>(a, a.first, a.count, blockIdx.x * 256u);
 }
 // linear gaps (piecewise 0)
-template<int W, int L>
+template<int W, int L, bool SCORE = false>
 __global__ void __launch_bounds__(256) k_align8_fwd_x0(const Align8Args a){
-	x_forward<W, L, 0>(a, a.first, a.count, blockIdx.x * 256u);
+	x_forward<W, L, 0, false, 4, false, false, SCORE>(a, a.first, a.count, blockIdx.x * 256u);
 }
 // two-piece gaps (bandwidth 128): 8 bits per band cell
 __global__ void __launch_bounds__(256) k_align8_fwd_x2(const Align8Args a){
@@ -916,9 +926,9 @@ __global__ void __launch_bounds__(256) k_align8_fwd_x2w(const Align8Args a){
 	x_forward<W, L, 2>(a, a.first, a.count, blockIdx.x * 256u);
 }
 // bands that cover their whole queries (Align8Args::static_band): the row stays in place, no steering
-template<int W, int L, int PW, bool DO2 = false>
+template<int W, int L, int PW, bool DO2 = false, bool SCORE = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_align8_fwd_x_static(const Align8Args a){
-	x_forward<W, L, PW, true, 4, DO2>(a, a.first, a.count, blockIdx.x * 256u);
+	x_forward<W, L, PW, true, 4, DO2, false, SCORE>(a, a.first, a.count, blockIdx.x * 256u);
 }
 
 // Bandwidth 128, a batch that is not a whole number of four-lane rounds: the first nb8 blocks take the last n8 pairs
@@ -941,7 +951,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
 // ideal.  ctl[0] = next item, ctl[16 + g] = segments of group g that are done (release / acquire at agent scope: the next segment
 // usually runs on another CU).  An item only ever waits for an item that was handed out before it, i.e. one that is running.
 struct XQArgs { uint32_t *ctl; uint32_t *state; uint32_t ngroups, nseg, seg_rows, spin_cap; };          // ctl[0]: next ticket, ctl[1]: some wave gave up waiting, ctl[16 + g]: segments of group g done
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3>
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) k_align8_fwd_xq(const Align8Args a, const XQArgs q){
 	// one item per wave (a block is a wave: the dispatcher refills a wave slot the moment it is free); the ticket, not the block
 	// index, names the item, so that an item's predecessor is always one that has started
@@ -978,7 +988,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) 
 		}
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 	}
-	x_forward<W, L, PW, false, 1, DO2>(a, a.first, a.count, g * 64u, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
+	x_forward<W, L, PW, false, 1, DO2, false, SCORE>(a, a.first, a.count, g * 64u, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
 	if(s + 1u < q.nseg){
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the state's write-through stores have arrived
 		if(threadIdx.x == 0u) __hip_atomic_fetch_max(done, s + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (max: a successor that gave up may have written s + 2)
@@ -1001,7 +1011,7 @@ size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count){
 	return (16u + groups) * 4u + 256u + groups * (size_t)(XS_WORDS(Wl, pw) * 64u * 4u);
 }
 // true when the launch was made
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3>
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false>
 static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err){
 	const char *qe = bsa_env("BSA_ALIGN8_XQ");
 	if(!a.xq || (qe && qe[0] == '0')) return false;
@@ -1022,9 +1032,10 @@ static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err){
 	if(const char *sc = bsa_env("BSA_ALIGN8_XQ_SPIN_CAP")){ const long v = atol(sc); if(v >= 1) q.spin_cap = (uint32_t)v; }          // (test hook: a cap of a few turns makes hand-over waits give up)
 	err = hipMemsetAsync(a.xq, 0, ctl_bytes, st);
 	if(err != hipSuccess) return true;
-	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS>), dim3(groups * nseg), dim3(64), 0, st, a, q);
+	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE>), dim3(groups * nseg), dim3(64), 0, st, a, q);
 	err = hipGetLastError();
-	bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
+	bsa_last_fwd_kernel = SCORE ? "k_align8_fwd_xq score-only (exact-arithmetic forward DP in row segments, no traceback codes)"
+		: "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
 	return true;
 }
 
@@ -1164,5 +1175,41 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		case 16: hipLaunchKernelGGL((k_align8_fwd_x<16, 8>), dim3(b8), dim3(256), 0, st, a); break;
 		default: return hipErrorInvalidValue;
 	}
+	return hipGetLastError();
+}
+
+// BSA_MODE_SCORE_ONLY (bsa_api.hip): the SCORE forms of the one-piece kernels above at bandwidth 64, 128 and 256 -- the same choice between
+// whole-query bands in place, row segments and whole pairs as the launcher above makes, each pair leaving its record (bsa_score_rec_bytes)
+hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	if(pw > 1 || a.code_fmt != 0u || !(a.bw == 64u || a.bw == 128u || a.bw == 256u)) return hipErrorInvalidValue;
+	const dim3 b4((a.count + 63u) / 64u), b8((a.count + 31u) / 32u);
+	if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
+		bsa_last_fwd_kernel = "k_align8_fwd_x_static score-only (exact-arithmetic forward DP, band in place, no traceback codes)";
+		if(pw == 1 && a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 1, false, true>), b4, dim3(256), 0, st, a);
+		if(pw == 1 && a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, false, true>), b4, dim3(256), 0, st, a);
+		if(pw == 1 && a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 1, false, true>), b8, dim3(256), 0, st, a);
+		if(pw == 0 && a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 0, false, true>), b4, dim3(256), 0, st, a);
+		if(pw == 0 && a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 0, false, true>), b4, dim3(256), 0, st, a);
+		if(pw == 0 && a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 0, false, true>), b8, dim3(256), 0, st, a);
+		return hipGetLastError();
+	}
+	hipError_t qerr = hipSuccess;
+	if(pw == 0){
+		if(a.bw == 64u && x_launch_xq<8, 4, 0, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 256u && x_launch_xq<16, 8, 0, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x0<8, 4, true>), b4, dim3(256), 0, st, a);
+		if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x0<16, 4, true>), b4, dim3(256), 0, st, a);
+		if(a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x0<16, 8, true>), b8, dim3(256), 0, st, a);
+	} else {
+		if(a.bw == 64u && x_launch_xq<8, 4, 1, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 128u && x_launch_xq<16, 4, 1, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 256u && x_launch_xq<16, 8, 1, false, 3, true>(a, st, qerr)) return qerr;
+		if(a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x<8, 4, false, true>), b4, dim3(256), 0, st, a);
+		if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x<16, 4, false, true>), b4, dim3(256), 0, st, a);
+		if(a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x<16, 8, false, true>), b8, dim3(256), 0, st, a);
+	}
+	bsa_last_fwd_kernel = "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)";
 	return hipGetLastError();
 }

@@ -777,7 +777,18 @@ struct bsa_align_plan : PlanBase {
 	uint32_t max_qlen = 0;
 	size_t stage_bytes = 0;                      // staged bytes of all pairs (which staging kernel)
 	uint32_t qpad = 0, tpad = 16;
+	bool score_only = false;                     // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
+	bool score_fast = false;                     // ... on the SCORE forward kernels (a record a pair); otherwise the full path, its results trimmed
 };
+
+// BSA_MODE_SCORE_ONLY: what the traceback would find is not returned (include/bsalign_hip.h)
+__global__ void k_score_only_trim(bsa_result_t *out, uint32_t n){
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if(k >= n) return;
+	bsa_result_t &r = out[k];
+	r.qb = r.tb = -1; r.mat = r.mis = r.ins = r.del = r.aln = -1;
+}
+static void score_only_trim(bsa_result_t &r){ r.qb = r.tb = -1; r.mat = r.mis = r.ins = r.del = r.aln = -1; }
 
 extern "C" void bsa_align_plan_destroy(bsa_align_plan_t *p){ plan_free(p); }
 extern "C" double bsa_align_plan_cells(const bsa_align_plan_t *p){ return p ? p->cells : 0.0; }
@@ -811,6 +822,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	if(n > 0xFFFFFFF0ull) { c->err = "too many pairs"; return BSA_E_ARG; }
 	const int type = par->mode & 3;
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
+	if((par->mode & BSA_MODE_SCORE_ONLY) && (par->mode & BSA_MODE_ROWRECORDS)){ c->err = "BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS exclude each other"; return BSA_E_ARG; }
 	(void)hipSetDevice(c->device);
 	const uint32_t bw_req = (par->bandwidth + 15u) / 16u * 16u;   // bsalign.h:3862; 0 = per pair roundup(qlen, 16) (bsalign.h:3861)
 	uint32_t bw = bw_req;
@@ -890,6 +902,10 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 		p->codes = !p->sys && !p->generic && !(le && le[0] == '1') && !(par->mode & BSA_MODE_ROWRECORDS) && bsa_align8_codes_supported(t, p->pw);
 		// the compact traceback packs band offsets into 26 bits of its ring entries
 		for(size_t k = 0; k < n && p->codes; k++) if(qlen[k] >= (1u << 26)) p->codes = false;
+		// score only: the SCORE forms of the exact-arithmetic forward kernels where bsa_align_run would take their full forms with one-piece gaps
+		const char *fe = bsa_env("BSA_ALIGN8_FWD");
+		p->score_only = (par->mode & BSA_MODE_SCORE_ONLY) != 0;
+		p->score_fast = p->score_only && p->codes && p->pw <= 1 && !(fe && fe[0] == 'p') && bsa_align8_x_supported(t, p->pw);
 	}
 	std::vector<uint32_t> order(n);
 	for(size_t k = 0; k < n; k++) order[k] = (uint32_t)k;
@@ -907,7 +923,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 		if(qlen[k] && tlen[k]) cells += (double)tlen[k] * (double)bw_ref(k);
 	}
 	for(size_t pos = 0; pos < n; pos++)
-		need[pos] = p->sys ? bsa_align8_sys_slot_bytes(qlen[order[pos]], tlen[order[pos]], p->pw)
+		need[pos] = p->score_fast ? bsa_score_rec_bytes(bw, type) : p->sys ? bsa_align8_sys_slot_bytes(qlen[order[pos]], tlen[order[pos]], p->pw)
 			: p->codes ? bsa_code_slot_bytes(tlen[order[pos]], bw / 16u, p->pw) : bsa_slot_bytes(tlen[order[pos]], bw_of(order[pos]) / 16u, p->pw);
 	p->cells = cells;
 	p->stage_bytes = qacc + tacc;
@@ -924,7 +940,7 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	if(!p || !d_out) return BSA_E_ARG;
 	bsa_ctx *c = p->ctx;
 	const uint32_t n = (uint32_t)p->n;
-	const bool want_cig = d_cigar != nullptr && d_cigar_off != nullptr;
+	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;          // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
 	if(rc != BSA_OK) return rc;
 	hipStream_t st = c->stream;
@@ -966,11 +982,14 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 		const bool force_pk = fe && fe[0] == 'p';
 		fwd_x = (pw == 2) || (!force_pk && bsa_align8_x_supported(a, pw));       // (two-piece gaps: the only forward kernel of the compact path)
 	}
-	if(codes && fwd_x && bsa_align8_do2_supported(a, pw) && bsa_align8_trace_reads_do2(a, pw)) a.code_fmt = 1u;      // two-bit D / Od fields (bsa_common.h)
+	const bool score_fast = p->score_fast;          // (decided by the plan, whose slots are records of that size)
+	if(score_fast) fwd_x = true;
+	if(codes && fwd_x && !score_fast && bsa_align8_do2_supported(a, pw) && bsa_align8_trace_reads_do2(a, pw)) a.code_fmt = 1u;      // two-bit D / Od fields (bsa_common.h)
 	c->fwd_name = (sys && p->sys_chk) ? "k_align8_fwd_sys<CHK> (whole-query band, systolic wavefront checking every pair against the int8 range, 4-bit traceback codes)" : sys ? "k_align8_fwd_sys (whole-query band, systolic wavefront, 4-bit traceback codes)" : (fwd_x && pw == 2) ? "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)"
 		: fwd_x ? "k_align8_fwd_x (exact-arithmetic forward DP, 4-bit traceback codes)" : codes ? "k_align8_fwd_pk<.,.,true> (packed forward DP, 4-bit traceback codes)"
 		: generic ? "k_align8_fwd_gen (run-time bandwidth, row records)" : "k_align8_fwd_pk / k_align8_fwd (row records)";
 	c->trace_name = sys ? "k_align8_trace_sys" : codes ? "" : "k_align8_backcal";
+	if(score_fast){ c->fwd_name = "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)"; c->trace_name = "k_align8_score_finish"; }
 	bsa_last_trace_kernel = nullptr; bsa_last_fwd_kernel = nullptr;
 	if(codes && fwd_x && !p->static_band){
 		// the persistent form of the forward kernel hands band states from one row segment to the next through this buffer
@@ -984,7 +1003,8 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	}
 	auto fwd = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		Align8Args b = a; b.first = ch.first; b.count = ch.count; b.rows = half; b.max_tlen = ch.max_tlen;
-		if(sys) HIPCHK(c, bsa_launch_align8_fwd_sys(b, pw, p->max_qlen, s));
+		if(score_fast) HIPCHK(c, bsa_launch_align8_fwd_x_score(b, pw, s));
+		else if(sys) HIPCHK(c, bsa_launch_align8_fwd_sys(b, pw, p->max_qlen, s));
 		else if(codes && fwd_x) HIPCHK(c, bsa_launch_align8_fwd_x(b, pw, s));
 		else if(codes) HIPCHK(c, bsa_launch_align8_fwd_codes(b, pw, s));
 		else if(generic) HIPCHK(c, bsa_launch_align8_fwd_gen(b, pw, max_bw, s));
@@ -993,7 +1013,8 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	};
 	auto trace = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		Align8Args b = a; b.first = ch.first; b.count = ch.count; b.rows = half;
-		if(sys) HIPCHK(c, bsa_launch_align8_trace_sys(b, pw, d_out, cnt, p->d_slot_end, s));
+		if(score_fast) HIPCHK(c, bsa_launch_align8_score_finish(b, d_out, s));
+		else if(sys) HIPCHK(c, bsa_launch_align8_trace_sys(b, pw, d_out, cnt, p->d_slot_end, s));
 		else if(codes) HIPCHK(c, bsa_launch_align8_trace_codes(b, pw, d_out, cnt, s));
 		else HIPCHK(c, bsa_launch_align8_backcal(b, pw, d_out, cnt, s));
 		return BSA_OK;
@@ -1001,6 +1022,11 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	const int rc8 = run_pipeline(p, want_cig, d_cigar, cigar_cap_words, d_cigar_off, fwd, trace);
 	if(codes && bsa_last_trace_kernel) c->trace_name = bsa_last_trace_kernel;
 	if(codes && fwd_x && bsa_last_fwd_kernel) c->fwd_name = bsa_last_fwd_kernel;
+	if(rc8 == BSA_OK && p->score_only && !score_fast){
+		// the full path ran (a configuration without SCORE kernels): the same result contract
+		hipLaunchKernelGGL(k_score_only_trim, dim3((n + 255u) / 256u), dim3(256), 0, st, d_out, n);
+		HIPCHK(c, hipGetLastError());
+	}
 	return rc8;
 }
 
@@ -1191,11 +1217,27 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	return rc;
 }
 
+static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_align_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
+		uint64_t *cigar_off, uint32_t *status);
+// BSA_MODE_SCORE_ONLY: no CIGAR arena is used (cigar may be NULL); a given cigar_off gets n + 1 zeros
 extern "C" int bsa_align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_align_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
 		uint64_t *cigar_off, uint32_t *status){
 	if(!c || !out || !par) return BSA_E_ARG;
+	if(!(par->mode & BSA_MODE_SCORE_ONLY)) return align_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status);
+	if(par->mode & BSA_MODE_ROWRECORDS){ c->err = "BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS exclude each other"; return BSA_E_ARG; }
+	const int rc = align_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, nullptr, 0, nullptr, status);
+	if(rc == BSA_OK && cigar_off) memset(cigar_off, 0, (n + 1) * sizeof(uint64_t));
+	return rc;
+}
+
+static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_align_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
+		uint64_t *cigar_off, uint32_t *status){
 	if(n == 0){ if(cigar_off) cigar_off[0] = 0; return BSA_OK; }
 	if(!seqs || !qoff || !qlen || !toff || !tlen) return BSA_E_ARG;
 	for(size_t k = 0; k < n; k++)            // the staging kernel reads seqs + qoff[k] .. + qlen[k] unconditionally
@@ -1318,7 +1360,7 @@ extern "C" int bsa_align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_by
 	for(size_t k = 0; k < m; k++){ sq[k] = qoff[idx[k]]; stt[k] = toff[idx[k]]; sql[k] = qlen[idx[k]]; stl[k] = tlen[idx[k]]; scap += (size_t)sql[k] + stl[k] + 2; }
 	std::vector<uint32_t> scig(cigar ? scap : 0);
 	bsa_align_params_t lp = *par;
-	lp.mode |= BSA_MODE_ROWRECORDS;
+	lp.mode = (lp.mode | BSA_MODE_ROWRECORDS) & ~BSA_MODE_SCORE_ONLY;
 	const std::string keep_fwd = c->fwd_name, keep_trace = c->trace_name;         // the batch's kernels stay the ones reported, not the re-run's
 	rc = bsa_align_batch(c, seqs, seqs_bytes, sq.data(), sql.data(), stt.data(), stl.data(), m, &lp, sout.data(),
 		cigar ? scig.data() : nullptr, scap, (cigar && cigar_off) ? soff.data() : nullptr, sst.data());
@@ -1326,7 +1368,10 @@ extern "C" int bsa_align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_by
 	// (literal_can_take filtered what the literal kernels decline, so BSA_E_UNSUPPORTED here is a real error of the re-run, not a pair
 	// to leave flagged: it is returned like any other)
 	if(rc != BSA_OK) return rc;
-	for(size_t k = 0; k < m; k++){ out[idx[k]] = sout[k]; st[idx[k]] = sst[k]; if(sst[k] & BSA_ST_TRACE) left_flagged ++; }
+	for(size_t k = 0; k < m; k++){
+		out[idx[k]] = sout[k]; st[idx[k]] = sst[k]; if(sst[k] & BSA_ST_TRACE) left_flagged ++;
+		if(par->mode & BSA_MODE_SCORE_ONLY) score_only_trim(out[idx[k]]);
+	}
 	if(cigar && cigar_off){
 		// splice the re-run pairs' CIGARs into the arena (the compact pass left them empty or, in the debug hook, filled)
 		std::vector<uint32_t> merged;

@@ -106,6 +106,8 @@ static inline __host__ __device__ uint32_t bsa_code_rows(uint32_t tlen){ return 
 // end record of the non-global modes: per lane the best end-of-query score seen while the band touched the query end
 // and its row (bsalign.h:4023-4032), and the last row itself for row_max (bsalign.h:4038-4046)
 struct bsa_code_end_t { int32_t cand_sc[16], cand_te[16], ubegs[17], rbeg_last; };
+// score-only slot (BSA_MODE_SCORE_ONLY): global mode the final score (int32), overlap / extend the end record followed by the last row's u bytes
+static inline __host__ __device__ size_t bsa_score_rec_bytes(uint32_t bw, int mode){ return (mode & 3) == BSA_MODE_GLOBAL ? 4u : sizeof(bsa_code_end_t) + bw; }
 static inline __host__ __device__ size_t bsa_code_slot_bytes(uint32_t tlen, uint32_t W, int pw = 1){
 	return bsa_begs_bytes(tlen) + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * bsa_code_row_bytes(W, pw);
 }
@@ -238,6 +240,10 @@ hipError_t bsa_launch_diagdp_walk(const uint8_t *d_planes, const bsa_diagdp_prob
 // the kernels the launchers picked last (this thread), for bsa_ctx_last_kernel_name
 extern thread_local const char *bsa_last_fwd_kernel, *bsa_last_trace_kernel;
 hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st);
+// BSA_MODE_SCORE_ONLY: the SCORE forward kernels (bsa_align8_x.hip: one-piece gaps, bandwidth 64 / 128 / 256) and the kernel that turns their
+// per-pair records into results (bsa_align8_codes.hip)
+hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st);
+hipError_t bsa_launch_align8_score_finish(const Align8Args &a, bsa_result_t *out, hipStream_t st);
 size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count);       // what Align8Args::xq must hold for a launch of `count` pairs (0: no persistent form)
 // whole-query bands above 256 columns, global mode: systolic wavefront + its own code layout and traceback (bsa_align8_sys.hip)
 int bsa_align8_sys_supported(const Align8Args &a, int pw);          // 0 no, 1 inside the static guard, 2 with the kernel checking every pair (Align8Args::sys_chk)
