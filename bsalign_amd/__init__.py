@@ -380,6 +380,19 @@ class Context:
         p.mode, p.bandwidth = mode, bandwidth
         return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap)
 
+    def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0):
+        """bsa_edit_batch with BSA_MODE_SCORE_ONLY OR-ed into the mode and no CIGAR arena: returns (results, status); score, qe and te as
+        edit_batch returns them, the fields only a traceback finds are -1"""
+        p = EditParams()
+        p.mode, p.bandwidth = mode | MODE_SCORE_ONLY, bandwidth
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        n = len(pairs)
+        out = np.zeros(n, dtype=RESULT_DTYPE)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self._chk(lib().bsa_edit_batch(self.h, _p(seqs), seqs.size, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(p),
+                                       _p(out), None, 0, None, _p(status)))
+        return out, status[:n]
+
     def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None):
         """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch"""
         p = KmerParams()
@@ -443,7 +456,7 @@ class AlignPlan:
 
 
 class EditPlan:
-    """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device)"""
+    """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device); mode may carry MODE_SCORE_ONLY, then run with d_cigar=None"""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, mode=MODE_GLOBAL, bandwidth=0):
         self.ctx = ctx

@@ -1459,6 +1459,8 @@ struct bsa_edit_plan : PlanBase {
 	uint64_t *d_qboff = nullptr, *d_qbits = nullptr;
 	uint32_t *d_qwords = nullptr;
 	int32_t *d_sbeg = nullptr;
+	bool score_only = false;        // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
+	bool score_fast = false;        // ... on the SCORE forward kernels and k_edit_score_finish (global / extend: a last row a pair); overlap: the full path, trimmed
 };
 
 extern "C" void bsa_edit_plan_destroy(bsa_edit_plan_t *p){ plan_free(p); }
@@ -1514,6 +1516,9 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 		radix_sort_order(key, order);
 	}
 	const auto tp1 = std::chrono::steady_clock::now();
+	// score only: the overlap score needs the walk's tb (smin + te - tb, bsalign.h:1189-1190), so only global and extend mode run without one
+	p->score_only = (par->mode & BSA_MODE_SCORE_ONLY) != 0;
+	p->score_fast = p->score_only && type != BSA_MODE_OVERLAP;
 	std::vector<uint64_t> qpoff(n), tpoff(n), qboff(n), slot, slot_end;
 	std::vector<size_t> need(n); std::vector<uint32_t> bwv(n);
 	size_t qacc = 0, tacc = 0, bacc = 0;
@@ -1526,7 +1531,9 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	for(size_t pos = 0; pos < n; pos++){
 		const uint32_t k = order[pos];
 		bwv[pos] = cls[k];
-		need[pos] = ((size_t)tlen[k] + 1 + p->pad_rows) * (size_t)(bwk[k] / 64u) * 16;
+		// (score only: the pairs k_edit_fwd_gen takes -- wide classes it has to itself, moving wide bands -- keep two rows, bsa_launch_edit_fwd)
+		const bool gen = cls[k] > BSA_EDIT_REG_BW && ((cls[k] & 0xFFu) == 0u || bwk[k] != (qlen[k] + 63u) / 64u * 64u);
+		need[pos] = p->score_fast ? bsa_edit_score_rec_bytes(bwk[k], gen) : ((size_t)tlen[k] + 1 + p->pad_rows) * (size_t)(bwk[k] / 64u) * 16;
 	}
 	int rc = plan_chunks(p, order, need, bwv, slot, slot_end, true);
 	const auto tp2 = std::chrono::steady_clock::now();
@@ -1550,7 +1557,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	if(!p || !d_out) return BSA_E_ARG;
 	bsa_ctx *c = p->ctx;
 	const uint32_t n = (uint32_t)p->n;
-	const bool want_cig = d_cigar != nullptr && d_cigar_off != nullptr;
+	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;        // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
 	if(rc != BSA_OK) return rc;
 	hipStream_t st = c->stream;
@@ -1568,13 +1575,14 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	a.qbits = p->d_qbits; a.qboff = p->d_qboff; a.qwords = p->d_qwords;
 	a.qlen = p->d_qlen; a.tlen = p->d_tlen; a.order = p->d_order; a.slot_off = p->d_slot;
 	a.status = status; a.fwd_sbeg = p->d_sbeg; a.fwd_smin = p->d_sbeg + n; a.fwd_ry = p->d_sbeg + 2 * (size_t)n; a.pad_rows = p->pad_rows; a.mode = p->par.mode; a.bandwidth = p->par.bandwidth;
+	a.score = p->score_fast ? 1u : 0u;
 	uint32_t *cnt = p->d_cnt_pos;
 	auto fwd = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		for(uint32_t x = ch.sub0; x < ch.sub0 + ch.nsub; x++){      // one forward launch per class
 			const Sub &sb = p->subs[x];
 			EditArgs b = a; b.first = sb.first; b.count = sb.count; b.rows = half;
 			b.bw = sb.bw <= BSA_EDIT_REG_BW ? sb.bw : 0u; b.wide = sb.bw <= BSA_EDIT_REG_BW ? 0u : (sb.bw & 0xFFu);
-			b.row_fmt = (ch.nsub == 1u && sb.count == ch.count && ch.bw == sb.bw && bsa_edit_tiled_ok(b.bw, ch.count, b.mode)) ? 1u : 0u;
+			b.row_fmt = (!p->score_fast && ch.nsub == 1u && sb.count == ch.count && ch.bw == sb.bw && bsa_edit_tiled_ok(b.bw, ch.count, b.mode)) ? 1u : 0u;
 			HIPCHK(c, bsa_launch_edit_fwd(b, s));
 		}
 		return BSA_OK;
@@ -1582,6 +1590,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	auto trace = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		EditArgs b = a; b.first = ch.first; b.count = ch.count; b.rows = half;
 		b.bw = ch.bw <= BSA_EDIT_REG_BW ? ch.bw : 0u;               // several classes or wide bands: every pair works out its own
+		if(p->score_fast){ HIPCHK(c, bsa_launch_edit_score_finish(b, d_out, s)); return BSA_OK; }
 		b.row_fmt = (ch.nsub == 1u && p->subs[ch.sub0].count == ch.count && p->subs[ch.sub0].bw == ch.bw && bsa_edit_tiled_ok(b.bw, ch.count, b.mode)) ? 1u : 0u;      // (the same test as the forward launch of this chunk)
 		HIPCHK(c, bsa_launch_edit_trace(b, d_out, cnt, s));
 		return BSA_OK;
@@ -1590,14 +1599,34 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	const int rce = run_pipeline(p, want_cig, d_cigar, cigar_cap_words, d_cigar_off, fwd, trace);
 	c->fwd_name = bsa_last_fwd_kernel ? bsa_last_fwd_kernel : "k_edit_fwd*";         // (the last launch class of the batch)
 	c->trace_name = bsa_last_trace_kernel ? bsa_last_trace_kernel : "k_edit_trace";
+	if(rce == BSA_OK && p->score_only && !p->score_fast){
+		// overlap mode ran the full path: the same result contract
+		hipLaunchKernelGGL(k_score_only_trim, dim3((n + 255u) / 256u), dim3(256), 0, st, d_out, n);
+		HIPCHK(c, hipGetLastError());
+	}
 	return rce;
 }
 
+static int edit_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_edit_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
+		uint64_t *cigar_off, uint32_t *status);
+// BSA_MODE_SCORE_ONLY: no CIGAR arena is used (cigar may be NULL); a given cigar_off gets n + 1 zeros
 extern "C" int bsa_edit_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_edit_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
 		uint64_t *cigar_off, uint32_t *status){
 	if(!c || !out || !par) return BSA_E_ARG;
+	if(!(par->mode & BSA_MODE_SCORE_ONLY)) return edit_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status);
+	const int rc = edit_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, nullptr, 0, nullptr, status);
+	if(rc == BSA_OK && cigar_off) memset(cigar_off, 0, (n + 1) * sizeof(uint64_t));
+	return rc;
+}
+
+static int edit_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_edit_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
+		uint64_t *cigar_off, uint32_t *status){
 	if(n == 0){ if(cigar_off) cigar_off[0] = 0; return BSA_OK; }
 	if(!seqs || !qoff || !qlen || !toff || !tlen) return BSA_E_ARG;
 	for(size_t k = 0; k < n; k++)

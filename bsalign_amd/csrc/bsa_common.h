@@ -164,7 +164,11 @@ struct EditArgs {
 	uint32_t pad_rows;              // spare row records at the end of every slot (CIGAR scratch)
 	int32_t  mode;
 	uint32_t row_fmt;               // 0: row r = [plane0: NW u64][plane1: NW u64]; 1: TILED (k_edit_fwd_grp32 + k_edit_trace_wave, bsa_edit_row_dword)
+	uint32_t score;                 // 1: BSA_MODE_SCORE_ONLY -- the forward kernels' SCORE forms (a pair's slot: its last row, bsa_edit_score_rec_bytes)
 };
+// score-only slot of the edit path: the last row in row format 0 (2 NW u64); the generic kernel, which reads its previous row back, keeps two
+// rows in turn and leaves the last one in the first place
+static inline __host__ __device__ size_t bsa_edit_score_rec_bytes(uint32_t bw, bool two_rows){ return (two_rows ? 2u : 1u) * (size_t)(bw / 64u) * 16u; }
 
 // Row format 1 of the edit path (round 6): the walk of a banded alignment needs, of every row, the 32 columns around its diagonal -- one or two of a
 // row's 32-bit words per plane -- but a 64-byte row is one memory request whatever part of it is wanted (profiles/r06_fetch_size_calibration.txt),
@@ -258,3 +262,4 @@ hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, cons
 		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st);
 hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st);
 hipError_t bsa_launch_edit_trace(const EditArgs &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
+hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st);        // BSA_MODE_SCORE_ONLY: records -> results

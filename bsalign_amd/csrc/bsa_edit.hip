@@ -30,7 +30,9 @@ static __device__ __forceinline__ u64 fsr(u64 lo, u64 hi, uint32_t m){   // (hi:
 static __device__ __forceinline__ u64 lowmask(uint32_t n){ return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }
 // row records: row r (r = 0 is the initial row, r = i+1 the row of target base i): [plane0: NW u64][plane1: NW u64]
 // TRACK (overlap / extend): also follow H at the last query column from row to row (its minimum picks the end cell)
-template<int NW, bool TRACK>
+// SCORE (BSA_MODE_SCORE_ONLY): no row records; the pair's slot gets its last row alone, in the layout of a row record (the record
+// k_edit_score_finish reads) -- the same for every SCORE form below
+template<int NW, bool TRACK, bool SCORE>
 __global__ void __launch_bounds__(64) k_edit_fwd(const EditArgs a, uint32_t lanes){
 	constexpr uint32_t BW = NW * 64;
 	const uint32_t g = blockIdx.x * lanes + threadIdx.x;      // `lanes` pairs per wave (bsa_launch_edit_fwd)
@@ -61,7 +63,7 @@ __global__ void __launch_bounds__(64) k_edit_fwd(const EditArgs a, uint32_t lane
 		l0c = *(Q0m + lword); l0n = *(Q0m + lword + 1); l1c = *(Q1m + lword); l1n = *(Q1m + lword + 1);
 	};
 #pragma unroll
-	for(int k = 0; k < NW; k++){ Pv[k] = ~0ull; Mv[k] = 0ull; rows[k] = 0ull; rows[NW + k] = ~0ull; }   // row_init (:653-656)
+	for(int k = 0; k < NW; k++){ Pv[k] = ~0ull; Mv[k] = 0ull; if(!SCORE){ rows[k] = 0ull; rows[NW + k] = ~0ull; } }   // row_init (:653-656)
 	load_window(0);
 	int sbeg = 0;
 	uint32_t rb0 = 0;
@@ -155,14 +157,20 @@ __global__ void __launch_bounds__(64) k_edit_fwd(const EditArgs a, uint32_t lane
 			Pv[k] = Mh | ~(Xv | Ph);
 			Mv[k] = Ph & Xv;
 		}
-		u64 *rp = rows + (size_t)(i + 1) * (2 * NW);
+		if constexpr(!SCORE){
+			u64 *rp = rows + (size_t)(i + 1) * (2 * NW);
 #pragma unroll
-		for(int k = 0; k < NW; k++){ rp[k] = Mv[k]; rp[NW + k] = Pv[k]; }
+			for(int k = 0; k < NW; k++){ rp[k] = Mv[k]; rp[NW + k] = Pv[k]; }
+		}
 		// score at the last query column (overlap / extend, :1124-1139): slast followed the row-to-row delta there
 		if(TRACK && slast < smin){ smin = slast; ry = (int)i; }
 		rb0 = rb1;
 		quo += qstep; rem += rstep;
 		if(rem >= tlen){ rem -= tlen; quo++; }
+	}
+	if constexpr(SCORE){
+#pragma unroll
+		for(int k = 0; k < NW; k++){ rows[k] = Mv[k]; rows[NW + k] = Pv[k]; }
 	}
 	// H at the band start of the last row; the traceback kernel derives the scores from it
 	a.fwd_sbeg[ppos] = sbeg;
@@ -176,6 +184,8 @@ __global__ void __launch_bounds__(64) k_edit_fwd(const EditArgs a, uint32_t lane
 // planes are taken straight from the staged bit planes at the row's band offset.  One pair per lane, NW a run-time
 // value; used when NW > 16, i.e. for the full-width bands of overlap / extend mode and of `bandwidth 0` on queries
 // longer than 1024 bp (bsalign.h:1055-1067).  Streaming loads and stores, four words in and two out per 64 cells.
+// SCORE: the slot holds two rows, written in turn (row r in place r & 1); the last row ends up in place 0 (bsa_edit_score_rec_bytes)
+template<bool SCORE>
 __global__ void __launch_bounds__(64) k_edit_fwd_gen(const EditArgs a, uint32_t lanes){
 	const uint32_t g = blockIdx.x * lanes + threadIdx.x;
 	if(threadIdx.x >= lanes || g >= a.count) return;
@@ -208,8 +218,8 @@ __global__ void __launch_bounds__(64) k_edit_fwd_gen(const EditArgs a, uint32_t 
 			rb1 = (c + BW > qround) ? qround - BW : c;
 		}
 		const uint32_t movx = rb1 - rb0;
-		const u64 *pm = rows + (size_t)i * (2 * NW), *pp = pm + NW;      // previous row: Mv words, Pv words
-		u64 *nm = rows + (size_t)(i + 1) * (2 * NW), *np = nm + NW;
+		const u64 *pm = rows + (size_t)(SCORE ? (i & 1u) : i) * (2 * NW), *pp = pm + NW;      // previous row: Mv words, Pv words
+		u64 *nm = rows + (size_t)(SCORE ? ((i + 1u) & 1u) : i + 1u) * (2 * NW), *np = nm + NW;
 		const uint32_t ws = movx >> 6, bs = movx & 63u;
 		// ---- row_movx (:658-721): H at the new band start
 		if(overlap) sbeg = 0;
@@ -252,6 +262,7 @@ __global__ void __launch_bounds__(64) k_edit_fwd_gen(const EditArgs a, uint32_t 
 		quo += qstep; rem += rstep;
 		if(rem >= tlen){ rem -= tlen; quo++; }
 	}
+	if(SCORE && (tlen & 1u)) for(uint32_t k = 0; k < 2u * NW; k++) rows[k] = rows[2u * NW + k];
 	a.fwd_sbeg[ppos] = sbeg;
 	a.fwd_smin[ppos] = smin; a.fwd_ry[ppos] = ry;
 }
@@ -288,7 +299,7 @@ static __device__ __forceinline__ u64 chain_neg(u64 A, u64 B){
 	return C;
 }
 
-template<int WPL>
+template<int WPL, bool SCORE>
 __global__ void __launch_bounds__(256) k_edit_fwd_wide(const EditArgs a){
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
@@ -315,7 +326,7 @@ __global__ void __launch_bounds__(256) k_edit_fwd_wide(const EditArgs a){
 		q0[j] = act[j] ? Q0m[w] : 0ull; q1[j] = act[j] ? Q1m[w] : 0ull;
 		vm[j] = (qlen > w * 64u) ? lowmask(qlen - w * 64u) : 0ull;          // band cells that are real query columns (:1112 nvalid)
 		pv[j] = ~0ull; mv[j] = 0ull;
-		if(act[j]){ rows[w] = 0ull; rows[NW + w] = ~0ull; }                    // row_init (:653-656)
+		if(!SCORE && act[j]){ rows[w] = 0ull; rows[NW + w] = ~0ull; }          // row_init (:653-656)
 	}
 	const uint32_t lastw = (qlen - 1u) >> 6, lastb = (qlen - 1u) & 63u;      // H(qlen-1, row) is followed by the lane that owns that column
 	const int lastj = (int)(lastw % WPL);
@@ -368,13 +379,19 @@ __global__ void __launch_bounds__(256) k_edit_fwd_wide(const EditArgs a){
 			pv[j] = Mh | ~(Xv[j] | Ph);
 			mv[j] = Ph & Xv[j];
 		}
-		u64 *rp = rows + (size_t)(i + 1) * (2 * NW);
-		if(WPL == 1){ if(act[0]){ rp[w0] = mv[0]; rp[NW + w0] = pv[0]; } }
-		else {
+		if constexpr(!SCORE){
+			u64 *rp = rows + (size_t)(i + 1) * (2 * NW);
+			if(WPL == 1){ if(act[0]){ rp[w0] = mv[0]; rp[NW + w0] = pv[0]; } }
+			else {
 #pragma unroll
-			for(int j = 0; j < WPL; j++) if(act[j]){ rp[w0 + j] = mv[j]; rp[NW + w0 + j] = pv[j]; }
+				for(int j = 0; j < WPL; j++) if(act[j]){ rp[w0 + j] = mv[j]; rp[NW + w0 + j] = pv[j]; }
+			}
 		}
 		if(type != BSA_MODE_GLOBAL && slast < smin){ smin = slast; ry = (int)i; }
+	}
+	if constexpr(SCORE){
+#pragma unroll
+		for(int j = 0; j < WPL; j++) if(act[j]){ rows[w0 + j] = mv[j]; rows[NW + w0 + j] = pv[j]; }
 	}
 	if(lane == lastw / WPL){ a.fwd_smin[ppos] = smin; a.fwd_ry[ppos] = ry; }
 	if(lane == 0) a.fwd_sbeg[ppos] = overlap ? 0 : (int)tlen;                     // no band motion: H at the band start grows by one per row (:667-676)
@@ -393,7 +410,7 @@ static __device__ __forceinline__ u64 dpp_next_lane64(u64 x){        // lane j <
 	return (u64)(uint32_t)hi << 32 | (u64)(uint32_t)lo;
 }
 
-template<int G>
+template<int G, bool SCORE>
 __global__ void __launch_bounds__(256) k_edit_fwd_grp(const EditArgs a){
 	constexpr uint32_t PPW = 64u / G;
 	constexpr u64 GS = G == 2 ? 0x5555555555555555ull : G == 4 ? 0x1111111111111111ull : G == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;   // first lane of every group
@@ -414,7 +431,7 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp(const EditArgs a){
 	const bool word = gl < NW, top = gl + 1u == NW;
 	const uint32_t tl = live ? tlen : 0u;
 	u64 pv = ~0ull, mv = 0ull;
-	if(live && word){ rows[gl] = 0ull; rows[NW + gl] = ~0ull; }            // row_init (:653-656)
+	if(!SCORE && live && word){ rows[gl] = 0ull; rows[NW + gl] = ~0ull; }  // row_init (:653-656)
 	u64 q0 = word ? Q0m[gl] : 0ull, q1 = word ? Q1m[gl] : 0ull;            // query planes at band offset 0
 	// the top lane keeps the query bits behind the band end: position lpos sits in (l?c, l?n) at bit lpos & 63
 	uint32_t lpos = BW;
@@ -494,7 +511,7 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp(const EditArgs a){
 		if(act){
 			pv = Mh | ~(Xv | Ph);
 			mv = Ph & Xv;
-			rp[0] = mv; rp[NW] = pv;
+			if(!SCORE){ rp[0] = mv; rp[NW] = pv; }
 			if(type != BSA_MODE_GLOBAL && slast < smin){ smin = slast; ry = (int)i; }
 		}
 		rb0 = on ? rb1 : rb0;
@@ -502,6 +519,7 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp(const EditArgs a){
 		if(rem >= tlen - rstep){ rem -= tlen - rstep; quo++; } else rem += rstep;     // no 33-bit sum
 		rp += 2u * NW;
 	}
+	if(SCORE && live && word){ rows[gl] = mv; rows[NW + gl] = pv; }      // (a lane's words stay as they were after its pair's last row)
 	if(live && gl == 0u) a.fwd_sbeg[ppos] = sbeg;
 	if(live && gl == (type != BSA_MODE_GLOBAL ? lastw : 0u)){ a.fwd_smin[ppos] = smin; a.fwd_ry[ppos] = ry; }
 }
@@ -515,8 +533,10 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp(const EditArgs a){
 // TILED: rows in format 1 (bsa_common.h).  A lane's word of both planes of eight consecutive rows is ONE 64-byte block: the row loop runs a tile at a
 // time, the eight rows wait in registers and leave as four 16-byte stores -- written piecemeal (eight bytes a row) the blocks were merged by the L2 only
 // while few waves were in flight (32768 pairs: 156 ms instead of 90), staged through LDS the kernel paid 12 % more instructions.
-template<int G, bool TILED>
+// SCORE: never TILED (no rows but the last)
+template<int G, bool TILED, bool SCORE>
 __global__ void __launch_bounds__(256) k_edit_fwd_grp32(const EditArgs a){
+	static_assert(!(TILED && SCORE), "the score-only form writes one row");
 	constexpr uint32_t PPW = 64u / G;
 	constexpr u64 GS = G == 2 ? 0x5555555555555555ull : G == 4 ? 0x1111111111111111ull : G == 8 ? 0x0101010101010101ull : 0x0001000100010001ull;   // first lane of every group
 	const uint32_t lane = threadIdx.x & 63u, gl = lane % G, grp = lane / G;
@@ -538,7 +558,7 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp32(const EditArgs a){
 	const uint32_t tl = live ? tlen : 0u;
 	uint32_t pv = ~0u, mv = 0u;
 	if(live && word){                                                     // row_init (:653-656)
-		if constexpr(!TILED){ rows[gl] = 0u; rows[NH + gl] = ~0u; }          // (TILED: the initial row leaves with tile 0)
+		if constexpr(!TILED && !SCORE){ rows[gl] = 0u; rows[NH + gl] = ~0u; }          // (TILED: the initial row leaves with tile 0)
 	}
 	uint32_t q0 = word ? Q0m[gl] : 0u, q1 = word ? Q1m[gl] : 0u;           // query planes at band offset 0
 	// the top lane keeps the query bits behind the band end: position lpos sits in (l?c, l?n) at bit lpos & 31
@@ -632,7 +652,10 @@ __global__ void __launch_bounds__(256) k_edit_fwd_grp32(const EditArgs a){
 		if(rem >= tlen - rstep){ rem -= tlen - rstep; quo++; } else rem += rstep;     // no 33-bit sum
 			return act;
 	};
-	if constexpr(!TILED){
+	if constexpr(SCORE){
+		for(uint32_t i = 0; __any(i < tl); i++) (void)row_step(i);
+		if(live && word){ rows[gl] = mv; rows[NH + gl] = pv; }              // (a lane's words stay as they were after its pair's last row)
+	} else if constexpr(!TILED){
 		for(uint32_t i = 0; __any(i < tl); i++){
 			if(row_step(i)){ rp[0] = mv; rp[NH] = pv; }
 			rp += 2u * NH;
@@ -914,6 +937,66 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 }
 
 // ---------------------------------------------------------------------------------------------
+// end cell and score of a pair from its last row (bsalign.h:1124-1139, 1180-1203), one pair per WAVE (every lane calls it; results uniform):
+// k_edit_trace_wave before its walk, k_edit_score_finish (BSA_MODE_SCORE_ONLY) instead of one.  last_word(plane, w) = 64-bit word w of a
+// plane of the last row (row r = tlen; natural bit order).  Global: H at the band start of that row (sbeg) plus its u values up to the query end
+// -- the padding cells past it read through the reference's unsigned striped index (striped_seqedit_getval, :224, on `x - begs[..]`; see
+// plane_bit of k_edit_trace).  Overlap / extend: the forward kernel's minimum of H at the last query column and its first row; extend then
+// takes the first STRICT minimum of the last row (striped_seqedit_rowmin, :813-963) where it is lower.  rx >= qlen marks an end cell the walk
+// rejects (BSA_ST_TRACE).
+template<class LastWord>
+static __device__ __forceinline__ void edit_end_cell(LastWord last_word, uint32_t lane, int type, uint32_t qlen, uint32_t tlen, uint32_t BW,
+		int sbeg, int fwd_smin, int fwd_ry, int &rx, int &ry, int &smin, int &score){
+	const uint32_t NW = BW / 64u;
+	rx = (int)qlen - 1; ry = (int)tlen - 1; smin = 0x7FFFFFFF; score = 0;
+	if(type == BSA_MODE_GLOBAL){
+		uint32_t rbl = 0;        // band offset of the last row (bsalign.h:1112-1114)
+		{
+			const uint32_t qround = (qlen + 63u) / 64u * 64u;
+			uint32_t c = (uint32_t)(((u64)(tlen - 1u) * qlen) / tlen);
+			c = (c < BW / 2) ? 0u : c - BW / 2;
+			rbl = (c + BW > qround) ? qround - BW : c;
+		}
+		auto plane_bit = [&](uint32_t plane, uint32_t pu) -> int {
+			const uint32_t p = ((pu / NW) & 63u) * NW + (pu % NW);
+			return (int)((last_word(plane, p >> 6) >> (p & 63u)) & 1ull);
+		};
+		int part = 0;
+		for(uint32_t k = lane; k < NW; k += 64u) part += __popcll(last_word(1u, k)) - __popcll(last_word(0u, k));
+		for(uint32_t k = qlen + 1u + lane; k <= rbl + BW; k += 64u) part += plane_bit(0u, k - 1u - rbl) - plane_bit(1u, k - 1u - rbl);
+		for(int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+		score = sbeg + part;
+	} else {
+		smin = fwd_smin; ry = fwd_ry;
+		if(type == BSA_MODE_EXTEND){     // striped_seqedit_rowmin (:813-963): first strict minimum of the prefix sums of the last row
+			// lane l owns words l, l + 64, ... : word totals first, then the scan inside the words
+			int best = (int)tlen; uint32_t pmin = 0; int base = (int)tlen;
+			for(uint32_t w0 = 0; w0 < NW; w0 += 64u){
+				const uint32_t w = w0 + lane;
+				const u64 pl0 = w < NW ? last_word(0u, w) : 0ull, pl1 = w < NW ? last_word(1u, w) : 0ull;
+				int tot = __popcll(pl1) - __popcll(pl0), pre = tot;         // inclusive prefix over the lanes
+				for(int o = 1; o < 64; o <<= 1){ const int v = __shfl_up(pre, o); if((int)lane >= o) pre += v; }
+				int sc = base + pre - tot, lb = 0x7FFFFFFF; uint32_t lp = 0;
+				if(w < NW){
+					for(uint32_t b = 0; b < 64u; b++){
+						sc += (int)((pl1 >> b) & 1ull) - (int)((pl0 >> b) & 1ull);
+						if(sc < lb){ lb = sc; lp = w * 64u + b; }
+					}
+				}
+				for(int o = 1; o < 64; o <<= 1){            // first strict minimum over the lanes: smaller value, then smaller position
+					const int vb = __shfl_xor(lb, o); const uint32_t vp = __shfl_xor(lp, o);
+					if(vb < lb || (vb == lb && vp < lp)){ lb = vb; lp = vp; }
+				}
+				if(lb < best){ best = lb; pmin = lp; }
+				base += __shfl(pre, 63);
+			}
+			if(best < smin){ smin = best; rx = (int)pmin; ry = (int)tlen - 1; }
+		}
+	}
+	rx = __builtin_amdgcn_readfirstlane(rx); ry = __builtin_amdgcn_readfirstlane(ry);
+}
+
+// ---------------------------------------------------------------------------------------------
 // traceback, ONE walk per wave (few long pairs: C3 has 16 walks per SIMD, far too few to hide a lane-per-walk chain)
 // ---------------------------------------------------------------------------------------------
 // Every decision of striped_seqedit_backtrace (bsalign.h:986-1010) is a function of the cell alone, so the 64 lanes
@@ -963,49 +1046,10 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 		if constexpr(TILED) return (u64)rowsd[bsa_edit_row_dword(NH, row, plane, 2u * w)] | ((u64)rowsd[bsa_edit_row_dword(NH, row, plane, 2u * w + 1u)] << 32);
 		else return rows[(size_t)row * (2 * NW) + (size_t)plane * NW + w];
 	};
-	auto beg_of_row = [&](uint32_t r) -> uint32_t {
-		if(r == 0 || type != BSA_MODE_GLOBAL) return 0u;
-		uint32_t c = (uint32_t)(((u64)(r - 1) * qlen) / tlen);
-		c = (c < BW / 2) ? 0u : c - BW / 2;
-		return (c + BW > qround) ? qround - BW : c;
-	};
 	// ---- end cell and score (uniform; the same statements as k_edit_trace, the row scans spread over the lanes)
-	int rx = (int)qlen - 1, ry = (int)tlen - 1, smin = 0x7FFFFFFF, score = 0;
-	if(type == BSA_MODE_GLOBAL){
-		const uint32_t rbl = beg_of_row(tlen);
-		int part = 0;
-		for(uint32_t k = lane; k < NW; k += 64u) part += __popcll(row_word(tlen, 1u, k)) - __popcll(row_word(tlen, 0u, k));
-		for(uint32_t k = qlen + 1u + lane; k <= rbl + BW; k += 64u) part += plane_bit(tlen, 0, (long)(k - 1 - rbl)) - plane_bit(tlen, 1, (long)(k - 1 - rbl));
-		for(int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
-		score = a.fwd_sbeg[ppos] + part;
-	} else {
-		smin = a.fwd_smin[ppos]; ry = a.fwd_ry[ppos];
-		if(type == BSA_MODE_EXTEND){     // striped_seqedit_rowmin (:813-963): first strict minimum of the prefix sums of the last row
-			// lane l owns words l, l + 64, ... : word totals first, then the scan inside the words
-			int best = (int)tlen; uint32_t pmin = 0; int base = (int)tlen;
-			for(uint32_t w0 = 0; w0 < NW; w0 += 64u){
-				const uint32_t w = w0 + lane;
-				const u64 pl0 = w < NW ? row_word(tlen, 0u, w) : 0ull, pl1 = w < NW ? row_word(tlen, 1u, w) : 0ull;
-				int tot = __popcll(pl1) - __popcll(pl0), pre = tot;         // inclusive prefix over the lanes
-				for(int o = 1; o < 64; o <<= 1){ const int v = __shfl_up(pre, o); if((int)lane >= o) pre += v; }
-				int sc = base + pre - tot, lb = 0x7FFFFFFF; uint32_t lp = 0;
-				if(w < NW){
-					for(uint32_t b = 0; b < 64u; b++){
-						sc += (int)((pl1 >> b) & 1ull) - (int)((pl0 >> b) & 1ull);
-						if(sc < lb){ lb = sc; lp = w * 64u + b; }
-					}
-				}
-				for(int o = 1; o < 64; o <<= 1){            // first strict minimum over the lanes: smaller value, then smaller position
-					const int vb = __shfl_xor(lb, o); const uint32_t vp = __shfl_xor(lp, o);
-					if(vb < lb || (vb == lb && vp < lp)){ lb = vb; lp = vp; }
-				}
-				if(lb < best){ best = lb; pmin = lp; }
-				base += __shfl(pre, 63);
-			}
-			if(best < smin){ smin = best; rx = (int)pmin; ry = (int)tlen - 1; }
-		}
-	}
-	rx = __builtin_amdgcn_readfirstlane(rx); ry = __builtin_amdgcn_readfirstlane(ry);
+	int rx, ry, smin, score;
+	edit_end_cell([&](uint32_t plane, uint32_t w){ return row_word(tlen, plane, w); }, lane, type, qlen, tlen, BW, a.fwd_sbeg[ppos], a.fwd_smin[ppos],
+		a.fwd_ry[ppos], rx, ry, smin, score);
 	// ---- backtrace
 	uint32_t *cig_end = (uint32_t*)((uint8_t*)rows + (size_t)(tlen + 1 + a.pad_rows) * (2 * NW) * 8);
 	// CIGAR: one token per gap event (matches / mismatches since the last event, op, length), one token per lane; a gap that goes
@@ -1312,6 +1356,34 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 	if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = ncig; }
 }
 
+// BSA_MODE_SCORE_ONLY: the records of the SCORE forward kernels (a pair's last row) -> results, one pair per wave, through the walkers' own
+// edit_end_cell.  score, qe and te as k_edit_trace_wave returns them; qb, tb and the counts need a walk and are -1 (as k_score_only_trim
+// leaves them), for flagged pairs as well.
+__global__ void __launch_bounds__(256) k_edit_score_finish(const EditArgs a, bsa_result_t *out){
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+	if(g >= a.count) return;
+	const uint32_t ppos = a.first + g, pair = a.order[ppos];
+	bsa_result_t rs;
+	rs.score = 0; rs.qe = rs.te = 0; rs.qb = rs.tb = -1; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = -1;
+	if(a.status[pair] != 0u){ if(lane == 0) out[pair] = rs; return; }       // flagged by an earlier stage
+	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
+	const int type = a.mode & 3;
+	const uint32_t BW = a.bw ? a.bw : bsa_edit_bw_eff(qlen, tlen, type, a.bandwidth), NW = BW / 64u;
+	const u64 *rec = (const u64*)(a.rows + a.slot_off[ppos]);
+	int rx, ry, smin, score;
+	edit_end_cell([&](uint32_t plane, uint32_t w){ return rec[(size_t)plane * NW + w]; }, lane, type, qlen, tlen, BW, a.fwd_sbeg[ppos], a.fwd_smin[ppos],
+		a.fwd_ry[ppos], rx, ry, smin, score);
+	if(rx >= (int)qlen){                                                 // the end cell the walk rejects: the walkers' flag and zero result
+		if(lane == 0){ atomicOr(&a.status[pair], BSA_ST_TRACE); out[pair] = rs; }
+		return;
+	}
+	// (overlap mode -- smin + te - tb -- needs the walk's tb: it runs the full path, bsa_edit_run)
+	rs.qe = rx + 1; rs.te = ry + 1;
+	rs.score = type == BSA_MODE_EXTEND ? smin : score;
+	if(lane == 0) out[pair] = rs;
+}
+
 // stage one pair per block: query -> two bit planes (bit p of plane b = bit b of base p; zero beyond qlen),
 // query and target bytes copied (the traceback compares bases), codes validated
 // (TPP threads per pair: the block for few long pairs, a wave for batches of many -- the k-mer path stages 1.5 M pieces of ~26 bp)
@@ -1396,16 +1468,17 @@ bool bsa_edit_tiled_ok(uint32_t bw, uint32_t count, int mode){
 	return count <= 8u * (uint32_t)cus * 32u;                                         // k_edit_trace_wave's (narrow bands)
 }
 
-hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st){
-	if(a.count == 0) return hipSuccess;
+// SCORE: the score-only forms (EditArgs::score), same dispatch; the kernel names say which
+template<bool SCORE>
+static hipError_t launch_edit_fwd(const EditArgs &a, hipStream_t st){
 	// pairs per wave of the register kernels (BSA_EDIT_FWD_LANES overrides, for measurements).  64 is best: a wave's time
 	// is its own serial chain (~600 instructions per row of 64-bit funnel shifts and block updates) whatever its lane
 	// count -- 16384 pairs x 100 kbp, ms per launch: 64 lanes 102, 32 -> 104, 16 -> 136, 8 -> 261, 4 -> 374
 	uint32_t lanes = 64;
 	if(const char *e = bsa_env("BSA_EDIT_FWD_LANES")){ const int v = atoi(e); if(v >= 1 && v <= 64) lanes = (uint32_t)v; }
 	const uint32_t fblocks = (a.count + lanes - 1) / lanes;
-#define EDIT_CASE(N) case N: if(track) hipLaunchKernelGGL((k_edit_fwd<N, true>), dim3(fblocks), dim3(64), 0, st, a, lanes); \
-		else hipLaunchKernelGGL((k_edit_fwd<N, false>), dim3(fblocks), dim3(64), 0, st, a, lanes); break;
+#define EDIT_CASE(N) case N: if(track) hipLaunchKernelGGL((k_edit_fwd<N, true, SCORE>), dim3(fblocks), dim3(64), 0, st, a, lanes); \
+		else hipLaunchKernelGGL((k_edit_fwd<N, false, SCORE>), dim3(fblocks), dim3(64), 0, st, a, lanes); break;
 	const bool track = (a.mode & 3) != BSA_MODE_GLOBAL;
 	// few pairs: G lanes per pair (waves stay few, every row is a third of the serial chain); many pairs: one per lane
 	{
@@ -1420,57 +1493,71 @@ hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st){
 			if(const char *e = bsa_env("BSA_EDIT_GRP32")) g32 = a.bw != 0u && nw >= 1u && nw <= 8u && e[0] == '1';
 			if(bsa_env("BSA_EDIT_GRP")) g32 = false;
 			if(g32){
-				bsa_last_fwd_kernel = "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair)";
+				bsa_last_fwd_kernel = SCORE ? "k_edit_fwd_grp32 score-only (forward DP, 32-bit words, 2 NW lanes per pair, last row only)"
+					: "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair)";
 				const uint32_t ppw = 64u / G32, gblocks = ((a.count + ppw - 1) / ppw + 3) / 4;
-				if(a.row_fmt == 1u){
+				if(!SCORE && a.row_fmt == 1u){
 					bsa_last_fwd_kernel = "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair, rows tiled eight at a time)";
 					switch(G32){
-						case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, true>), dim3(gblocks), dim3(256), 0, st, a); break;
-						case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, true>), dim3(gblocks), dim3(256), 0, st, a); break;
-						default: hipLaunchKernelGGL((k_edit_fwd_grp32<8, true>), dim3(gblocks), dim3(256), 0, st, a); break;
+						case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
+						case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
+						default: hipLaunchKernelGGL((k_edit_fwd_grp32<8, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
 					}
 					return hipGetLastError();
 				}
 				switch(G32){
-					case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-					case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-					case 8: hipLaunchKernelGGL((k_edit_fwd_grp32<8, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-					default: hipLaunchKernelGGL((k_edit_fwd_grp32<16, false>), dim3(gblocks), dim3(256), 0, st, a); break;
+					case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+					case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+					case 8: hipLaunchKernelGGL((k_edit_fwd_grp32<8, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+					default: hipLaunchKernelGGL((k_edit_fwd_grp32<16, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
 				}
 				return hipGetLastError();
 			}
 		}
 		if(grp){
-			bsa_last_fwd_kernel = "k_edit_fwd_grp (forward DP, NW lanes per pair)";
+			bsa_last_fwd_kernel = SCORE ? "k_edit_fwd_grp score-only (forward DP, NW lanes per pair, last row only)" : "k_edit_fwd_grp (forward DP, NW lanes per pair)";
 			const uint32_t ppw = 64u / G, gblocks = ((a.count + ppw - 1) / ppw + 3) / 4;
 			switch(G){
-				case 2: hipLaunchKernelGGL((k_edit_fwd_grp<2>), dim3(gblocks), dim3(256), 0, st, a); break;
-				case 4: hipLaunchKernelGGL((k_edit_fwd_grp<4>), dim3(gblocks), dim3(256), 0, st, a); break;
-				case 8: hipLaunchKernelGGL((k_edit_fwd_grp<8>), dim3(gblocks), dim3(256), 0, st, a); break;
-				default: hipLaunchKernelGGL((k_edit_fwd_grp<16>), dim3(gblocks), dim3(256), 0, st, a); break;
+				case 2: hipLaunchKernelGGL((k_edit_fwd_grp<2, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+				case 4: hipLaunchKernelGGL((k_edit_fwd_grp<4, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+				case 8: hipLaunchKernelGGL((k_edit_fwd_grp<8, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
+				default: hipLaunchKernelGGL((k_edit_fwd_grp<16, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
 			}
 			return hipGetLastError();
 		}
 	}
-	bsa_last_fwd_kernel = a.bw ? "k_edit_fwd (forward DP, one pair per lane)" : "k_edit_fwd_wide / k_edit_fwd_gen (forward DP, bands above 1024 columns)";
+	if(SCORE) bsa_last_fwd_kernel = a.bw ? "k_edit_fwd score-only (forward DP, one pair per lane, last row only)" : "k_edit_fwd_wide / k_edit_fwd_gen score-only (forward DP, bands above 1024 columns, last row only)";
+	else bsa_last_fwd_kernel = a.bw ? "k_edit_fwd (forward DP, one pair per lane)" : "k_edit_fwd_wide / k_edit_fwd_gen (forward DP, bands above 1024 columns)";
 	switch(a.bw / 64){
 		EDIT_CASE(1) EDIT_CASE(2) EDIT_CASE(3) EDIT_CASE(4) EDIT_CASE(5) EDIT_CASE(6) EDIT_CASE(7) EDIT_CASE(8)
 		EDIT_CASE(9) EDIT_CASE(10) EDIT_CASE(11) EDIT_CASE(12) EDIT_CASE(13) EDIT_CASE(14) EDIT_CASE(15) EDIT_CASE(16)
 		default: {
 			// bands above 1024: static ones (overlap / extend / bandwidth 0) one pair per wave, the rest one pair per lane
-			if(a.wide == 1u) hipLaunchKernelGGL((k_edit_fwd_wide<1>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 2u) hipLaunchKernelGGL((k_edit_fwd_wide<2>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 4u) hipLaunchKernelGGL((k_edit_fwd_wide<4>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 8u) hipLaunchKernelGGL((k_edit_fwd_wide<8>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
+			if(a.wide == 1u) hipLaunchKernelGGL((k_edit_fwd_wide<1, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
+			else if(a.wide == 2u) hipLaunchKernelGGL((k_edit_fwd_wide<2, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
+			else if(a.wide == 4u) hipLaunchKernelGGL((k_edit_fwd_wide<4, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
+			else if(a.wide == 8u) hipLaunchKernelGGL((k_edit_fwd_wide<8, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
 			if(a.wide == 0u || ((a.mode & 3) == BSA_MODE_GLOBAL && a.bandwidth != 0u)){
 				uint32_t gl = 64;
 				while(gl > 2u && (a.count + gl / 2 - 1) / (gl / 2) <= 8192u) gl >>= 1;
 				if(const char *e = bsa_env("BSA_EDIT_GEN_LANES")){ const int v = atoi(e); if(v >= 1 && v <= 64) gl = (uint32_t)v; }
-				hipLaunchKernelGGL(k_edit_fwd_gen, dim3((a.count + gl - 1) / gl), dim3(64), 0, st, a, gl);
+				hipLaunchKernelGGL(k_edit_fwd_gen<SCORE>, dim3((a.count + gl - 1) / gl), dim3(64), 0, st, a, gl);
 			}
 		} break;
 	}
 #undef EDIT_CASE
+	return hipGetLastError();
+}
+
+hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	return a.score ? launch_edit_fwd<true>(a, st) : launch_edit_fwd<false>(a, st);
+}
+
+hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	bsa_last_trace_kernel = "k_edit_score_finish";
+	hipLaunchKernelGGL(k_edit_score_finish, dim3((a.count + 3) / 4), dim3(256), 0, st, a, out);
 	return hipGetLastError();
 }
 

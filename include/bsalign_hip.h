@@ -37,17 +37,22 @@ extern "C" {
 #define BSA_MODE_EXTEND   2
 #define BSA_MODE_ROWRECORDS 0x100 /* flag: keep the reference-layout row records and the literal traceback even where the
                                       compact 4-bit-code path applies (global mode, 1-piece gaps, small scores) */
-#define BSA_MODE_SCORE_ONLY 0x400 /* flag: score and end cell only, no traceback.  Every bsa_result_t gets score, qe and te exactly as the same
-                                      call without the flag returns them (overlap / extend: the reference's row_max tie rules included);
-                                      qb, tb, mat, mis, ins, del and aln would need a traceback and are set to -1.  No CIGAR is returned:
-                                      cigar / d_cigar may be NULL (cigar_cap_words 0), a given cigar_off / d_cigar_off gets n + 1 zeros.
-                                      status: the same bits as without the flag (BSA_ST_TRACE only where the band never reached the
-                                      query end in global mode; bsa_align_batch hands such pairs over as it does without the flag -- a pair
-                                      on which the reference's own traceback does not terminate is NOT flagged here, it simply has a score).
-                                      Fast (forward kernel alone, a fixed-size record a pair instead of code rows) with one-piece gaps at
-                                      bandwidth 64, 128 and 256 -- or whole-query bands of up to 256 columns -- inside the exact-arithmetic
-                                      guard; every other parameter set runs the full path and drops what the traceback found.
-                                      BSA_MODE_SCORE_ONLY | BSA_MODE_ROWRECORDS is BSA_E_ARG. */
+#define BSA_MODE_SCORE_ONLY 0x400 /* flag: score and end cell only, no traceback -- for the 8-bit aligner (bsa_align_batch / _plan_create /
+                                      _run) and the edit aligner (bsa_edit_batch / _plan_create / _run) alike.  Every bsa_result_t gets
+                                      score, qe and te exactly as the same call without the flag returns them (the reference's tie rules
+                                      included); qb, tb, mat, mis, ins, del and aln would need a traceback and are set to -1, for flagged and
+                                      empty pairs as well.  No CIGAR is returned: cigar / d_cigar may be NULL (cigar_cap_words 0), a given
+                                      cigar_off / d_cigar_off gets n + 1 zeros.  status: the same bits as without the flag.
+                                      8-bit aligner: BSA_ST_TRACE only where the band never reached the query end in global mode;
+                                      bsa_align_batch hands such pairs over as it does without the flag -- a pair on which the reference's
+                                      own traceback does not terminate is NOT flagged here, it simply has a score.  Fast (forward kernel
+                                      alone, a fixed-size record a pair instead of code rows) with one-piece gaps at bandwidth 64, 128 and
+                                      256 -- or whole-query bands of up to 256 columns -- inside the exact-arithmetic guard; every other
+                                      parameter set runs the full path and drops what the traceback found.
+                                      BSA_MODE_SCORE_ONLY | BSA_MODE_ROWRECORDS is BSA_E_ARG.
+                                      Edit aligner: fast (forward kernel alone, the last row a pair instead of every row's planes) in
+                                      global and extend mode at every bandwidth; overlap mode needs the walk's tb for its score
+                                      (smin + te - tb) and runs the full path, dropping what the traceback found. */
 
 /* CIGAR op codes (bsalign.h:61-69) */
 #define BSA_CIGAR_M 0
