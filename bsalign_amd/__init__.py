@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSA_LIB_PATH") or os.path.join(_HERE, "libbsalign_hip.so")      # BSA_LIB_PATH: development builds
 
 MODE_GLOBAL, MODE_OVERLAP, MODE_EXTEND = 0, 1, 2
-MODE_ROWRECORDS, MODE_SCORE_ONLY = 0x100, 0x400       # flags OR-ed into the mode (include/bsalign_hip.h)
+MODE_ROWRECORDS, MODE_SCORE_ONLY, MODE_SEQ2BIT = 0x100, 0x400, 0x800       # flags OR-ed into the mode (include/bsalign_hip.h)
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
@@ -136,6 +136,7 @@ def lib():
         L.bsa_synth_stride.restype = C.c_size_t
         L.bsa_synth_pairs_host.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint32, C.c_uint32, u8p, u32p]
         L.bsa_synth_pairs_dev.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint32, C.c_uint32, u8p, u32p]
+        L.bsa_seq_pack2bit.argtypes = [vp, u8p, C.c_uint64, u64p, u32p]
         if hasattr(L, "bsa_edit_batch"):
             L.bsa_edit_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(EditParams),
                                          vp, u32p, C.c_size_t, u64p, u32p]
@@ -198,8 +199,45 @@ def make_params(mode=MODE_GLOBAL, bandwidth=128, M=2, X=-6, O=-3, E=-2, Q=0, P=0
     return p
 
 
-def pack_pairs(pairs):
-    """[(q, t), ...] of uint8 code arrays -> (seqs blob, qoff, qlen, toff, tlen)"""
+def pack2bit(codes):
+    """codes (one base per byte) -> uint64 words in the BSA_MODE_SEQ2BIT layout (the reference's BaseBank.bits): base i at bits
+    62 - 2 (i % 32) of word i / 32, each code taken as c & 3, the bits behind the last base zero"""
+    c = np.ascontiguousarray(codes, dtype=np.uint8).ravel()
+    nw = (c.size + 31) // 32
+    buf = np.zeros(nw * 32, dtype=np.uint64)
+    buf[:c.size] = c & 3
+    shift = np.uint64(62) - np.uint64(2) * np.arange(32, dtype=np.uint64)
+    return np.bitwise_or.reduce(buf.reshape(nw, 32) << shift, axis=1).astype(np.uint64)
+
+
+def unpack2bit(words, off, n):
+    """bases [off, off + n) of BSA_MODE_SEQ2BIT words -> uint8 codes"""
+    i = np.uint64(off) + np.arange(n, dtype=np.uint64)
+    w = np.asarray(words, dtype=np.uint64)[(i >> np.uint64(5)).astype(np.intp)]
+    return ((w >> (np.uint64(62) - np.uint64(2) * (i & np.uint64(31)))) & np.uint64(3)).astype(np.uint8)
+
+
+def pack_pairs(pairs, seq2bit=False):
+    """[(q, t), ...] of uint8 code arrays -> (seqs blob, qoff, qlen, toff, tlen).
+    seq2bit: the blob is uint64 words (pack2bit) and the offsets are base offsets; the sequences start 3 bases into the first word and
+    have 3 bases between them, so that they start at every position in a word, as a caller's reads do (the last one ends in the last word)"""
+    if seq2bit:
+        n = len(pairs)
+        qlen = np.array([len(q) for q, _ in pairs], dtype=np.uint32)
+        tlen = np.array([len(t) for _, t in pairs], dtype=np.uint32)
+        qoff = np.zeros(n, dtype=np.uint64)
+        toff = np.zeros(n, dtype=np.uint64)
+        gap = np.zeros(3, dtype=np.uint8)
+        parts, acc = [gap], 3
+        for k, (q, t) in enumerate(pairs):
+            qoff[k] = acc
+            parts += [_np(q, np.uint8), gap]
+            acc += len(q) + 3
+            toff[k] = acc
+            parts += [_np(t, np.uint8)] + ([gap] if k + 1 < n else [])
+            acc += len(t) + (3 if k + 1 < n else 0)
+        words = pack2bit(np.concatenate(parts))
+        return (words if words.size else np.zeros(1, dtype=np.uint64)), qoff, qlen, toff, tlen
     n = len(pairs)
     qlen = np.array([len(q) for q, _ in pairs], dtype=np.uint32)
     tlen = np.array([len(t) for _, t in pairs], dtype=np.uint32)
@@ -272,8 +310,8 @@ class Context:
     def last_kernel_names(self):
         return lib().bsa_ctx_last_kernel_name(self.h, 0).decode(), lib().bsa_ctx_last_kernel_name(self.h, 1).decode()
 
-    def _batch(self, fn, pairs, par, cigar_cap=None):
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+    def _batch(self, fn, pairs, par, cigar_cap=None, seq2bit=False):
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
@@ -281,26 +319,30 @@ class Context:
             cigar_cap = int(qlen.sum() + tlen.sum()) + 2 * n + 16
         cig = np.zeros(cigar_cap, dtype=np.uint32)
         off = np.zeros(n + 1, dtype=np.uint64)
-        rc = fn(self.h, _p(seqs), seqs.size, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(par),
+        rc = fn(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(par),
                 _p(out), _p(cig), cigar_cap, _p(off), _p(status))
         self._chk(rc)
         cigs = [cig[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
         return out, cigs, status[:n]
 
-    def align_batch(self, pairs, par, cigar_cap=None):
-        """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status)"""
-        return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap)
+    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False):
+        """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status); seq2bit: the sequences go down
+        2-bit packed (pack_pairs(..., seq2bit=True), BSA_MODE_SEQ2BIT OR-ed into par.mode)"""
+        if seq2bit:
+            par = AlignParams.from_buffer_copy(par)
+            par.mode |= MODE_SEQ2BIT
+        return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit)
 
-    def align_scores(self, pairs, par):
+    def align_scores(self, pairs, par, seq2bit=False):
         """bsa_align_batch with BSA_MODE_SCORE_ONLY OR-ed into par.mode and no CIGAR arena: returns (results, status); score, qe and te as
         align_batch returns them, the fields only a traceback finds are -1"""
         sp = AlignParams.from_buffer_copy(par)
-        sp.mode = par.mode | MODE_SCORE_ONLY
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        sp.mode = par.mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0)
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
-        self._chk(lib().bsa_align_batch(self.h, _p(seqs), seqs.size, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(sp),
+        self._chk(lib().bsa_align_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(sp),
                                         _p(out), None, 0, None, _p(status)))
         return out, status[:n]
 
@@ -375,23 +417,33 @@ class Context:
     def diagdp_last_ms(self):
         return float(lib().bsa_diagdp_last_ms(self.h))
 
-    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None):
+    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None, seq2bit=False):
         p = EditParams()
-        p.mode, p.bandwidth = mode, bandwidth
-        return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap)
+        p.mode, p.bandwidth = mode | (MODE_SEQ2BIT if seq2bit else 0), bandwidth
+        return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap, seq2bit)
 
-    def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0):
+    def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0, seq2bit=False):
         """bsa_edit_batch with BSA_MODE_SCORE_ONLY OR-ed into the mode and no CIGAR arena: returns (results, status); score, qe and te as
         edit_batch returns them, the fields only a traceback finds are -1"""
         p = EditParams()
-        p.mode, p.bandwidth = mode | MODE_SCORE_ONLY, bandwidth
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        p.mode, p.bandwidth = mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0), bandwidth
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
-        self._chk(lib().bsa_edit_batch(self.h, _p(seqs), seqs.size, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(p),
+        self._chk(lib().bsa_edit_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, C.byref(p),
                                        _p(out), None, 0, None, _p(status)))
         return out, status[:n]
+
+    def seq_pack2bit(self, d_codes, d_bits, d_bad=None):
+        """bsa_seq_pack2bit on torch tensors: d_codes (uint8, one base per byte) -> d_bits (int64 / uint64, at least
+        ceil(n / 32) elements) in the BSA_MODE_SEQ2BIT layout; d_bad (int32, one element, cleared by the caller) is set to 1 when a
+        code is above 3.  Asynchronous on the context's stream."""
+        n = d_codes.numel()
+        if d_bits.numel() * d_bits.element_size() < (n + 31) // 32 * 8:
+            raise ValueError("seq_pack2bit: d_bits holds fewer than ceil(n / 32) words")
+        self._chk(lib().bsa_seq_pack2bit(self.h, C.c_void_p(d_codes.data_ptr()), n, C.c_void_p(d_bits.data_ptr()),
+                                         C.c_void_p(d_bad.data_ptr() if d_bad is not None else 0)))
 
     def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None):
         """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch"""
@@ -413,7 +465,8 @@ def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):
 
 class AlignPlan:
     """two-phase form (bsa_align_plan_create / bsa_align_run): host metadata once, device-resident data per run.
-    Device buffers are torch tensors (plumbing only); the run is asynchronous on the context's stream."""
+    Device buffers are torch tensors (plumbing only); the run is asynchronous on the context's stream.  With MODE_SEQ2BIT in
+    par.mode, d_seqs holds 2-bit packed words (pack2bit) and the offsets are base offsets."""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, par):
         self.ctx = ctx
@@ -456,7 +509,8 @@ class AlignPlan:
 
 
 class EditPlan:
-    """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device); mode may carry MODE_SCORE_ONLY, then run with d_cigar=None"""
+    """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device); mode may carry MODE_SCORE_ONLY, then run with d_cigar=None,
+    and MODE_SEQ2BIT (d_seqs 2-bit packed words, base offsets)"""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, mode=MODE_GLOBAL, bandwidth=0):
         self.ctx = ctx

@@ -288,6 +288,69 @@ __global__ void __launch_bounds__(256) k_stage(const uint8_t *seqs, const uint64
 	if(lane == 0) status[k] = st;
 }
 
+// k_stage for BSA_MODE_SEQ2BIT blobs: the offsets are base offsets into 2-bit packed words (bsa_bits16); the staged bytes, the padding
+// and the empty-pair flag are k_stage's.  No code is above 3, so no BSA_ST_BAD_BASE.
+template<int TPP>
+__global__ void __launch_bounds__(256) k_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
+		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
+		uint8_t *qst, uint8_t *tst, uint32_t qpad, uint32_t tpad, uint32_t *status, uint32_t n){
+	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
+	if(k >= n) return;
+	const uint32_t ql = qlen[k], tl = tlen[k];
+	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
+	// 16 bases per thread and trip from at most two words, expanded to one 16-byte store
+	auto copy = [&](uint64_t off, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode){
+		const uint32_t total = (len + pad + 15u) & ~15u;
+		for(uint32_t i = lane * 16u; i < total; i += (uint32_t)TPP * 16u){
+			const uint32_t x = bsa_bits16(seqs, off + i, off + len);
+			uint64_t v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
+			if(i + 16u > len){ v0 = bsa_pad_bytes(v0, (int64_t)len - i, padcode); v1 = bsa_pad_bytes(v1, (int64_t)len - i - 8, padcode); }
+			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32);
+			*(uint4*)(dst + i) = o;
+		}
+	};
+	copy(qoff[k], dq, ql, qpad, (uint8_t)BSA_QPAD_CODE);
+	copy(toff[k], dt, tl, tpad, (uint8_t)0);
+	if(lane == 0) status[k] = (ql == 0 || tl == 0) ? BSA_ST_EMPTY : 0u;
+}
+
+// bsa_seq_pack2bit: 32 codes a thread into one word of the BSA_MODE_SEQ2BIT layout (c & 3; a code above 3 sets *bad)
+__global__ void __launch_bounds__(256) k_pack2bit(const uint8_t *codes, uint64_t nbases, uint64_t *bits, uint32_t *bad){
+	const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x, b0 = w * 32u;
+	if(b0 >= nbases) return;
+	uint64_t v = 0, hi = 0;
+	if(b0 + 32u <= nbases){
+#pragma unroll
+		for(uint32_t j = 0; j < 4u; j++){
+			uint64_t c;
+			__builtin_memcpy(&c, codes + b0 + 8u * j, 8);
+			hi |= c;
+#pragma unroll
+			for(uint32_t b = 0; b < 8u; b++) v |= ((c >> (8u * b)) & 3ull) << (62u - 2u * (8u * j + b));
+		}
+		hi &= 0xFCFCFCFCFCFCFCFCull;
+	} else {
+		for(uint32_t j = 0; b0 + j < nbases; j++){
+			const uint8_t c = codes[b0 + j];
+			hi |= c & 0xFCu;
+			v |= (uint64_t)(c & 3u) << (62u - 2u * j);
+		}
+	}
+	bits[w] = v;
+	if(bad && hi) *bad = 1u;
+}
+
+extern "C" int bsa_seq_pack2bit(bsa_ctx_t *c, const uint8_t *d_codes, uint64_t nbases, uint64_t *d_bits, uint32_t *d_bad){
+	if(!c || (nbases && (!d_codes || !d_bits))) return BSA_E_ARG;
+	if(nbases == 0) return BSA_OK;
+	(void)hipSetDevice(c->device);
+	const uint64_t words = (nbases + 31u) / 32u, blocks = (words + 255u) / 256u;
+	if(blocks > 0x7FFFFFFFull){ c->err = "bsa_seq_pack2bit: too many bases"; return BSA_E_ARG; }
+	hipLaunchKernelGGL(k_pack2bit, dim3((uint32_t)blocks), dim3(256), 0, c->stream, d_codes, nbases, d_bits, d_bad);
+	HIPCHK(c, hipGetLastError());
+	return BSA_OK;
+}
+
 // single-block exclusive scan of cnt[0..n) into off[0..n], off[n] = total; *carry (optional) is a running base
 __global__ void __launch_bounds__(1024) k_excl_scan(const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *carry){
 	__shared__ uint64_t part[1024];
@@ -779,6 +842,7 @@ struct bsa_align_plan : PlanBase {
 	uint32_t qpad = 0, tpad = 16;
 	bool score_only = false;                     // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
 	bool score_fast = false;                     // ... on the SCORE forward kernels (a record a pair); otherwise the full path, its results trimmed
+	bool seq2bit = false;                        // BSA_MODE_SEQ2BIT: d_seqs holds 2-bit packed words, offsets in bases (k_stage2b)
 };
 
 // BSA_MODE_SCORE_ONLY: what the traceback would find is not returned (include/bsalign_hip.h)
@@ -876,6 +940,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	}
 	bsa_align_plan *p = new bsa_align_plan();
 	p->ctx = c; p->n = n; p->par = *par; p->bw = bw;
+	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
 	p->sys = sys; p->sys_chk = sys && sys_chk; p->max_qlen = max_qlen;
 	p->ref_bw = widened ? (bw_req ? bw_req : 1u) : sys ? bw_req : 0u;
 	p->static_band = bw != 0 && n > 0;
@@ -939,6 +1004,7 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 		size_t cigar_cap_words, uint64_t *d_cigar_off, uint32_t *d_status){
 	if(!p || !d_out) return BSA_E_ARG;
 	bsa_ctx *c = p->ctx;
+	if(p->seq2bit && ((uintptr_t)d_seqs & 7u)){ c->err = "BSA_MODE_SEQ2BIT: d_seqs must be 8-byte aligned"; return BSA_E_ARG; }
 	const uint32_t n = (uint32_t)p->n;
 	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;          // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
@@ -950,7 +1016,14 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	}
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
-	if(p->stage_bytes / std::max<size_t>(n, 1) >= 8192)         // long pairs: a block per pair
+	if(p->seq2bit){
+		if(p->stage_bytes / std::max<size_t>(n, 1) >= 8192)
+			hipLaunchKernelGGL(k_stage2b<256>, dim3(n), dim3(256), 0, st, (const uint64_t*)d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
+				p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
+		else
+			hipLaunchKernelGGL(k_stage2b<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, (const uint64_t*)d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
+				p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
+	} else if(p->stage_bytes / std::max<size_t>(n, 1) >= 8192)         // long pairs: a block per pair
 		hipLaunchKernelGGL(k_stage<256>, dim3(n), dim3(256), 0, st, d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
 			p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
 	else
@@ -1067,6 +1140,18 @@ static hipError_t par_copy(int device, void *dst, const void *src, size_t bytes,
 	return hipSuccess;
 }
 
+// every pair inside the blob: offsets and lengths in bytes, or with BSA_MODE_SEQ2BIT in bases of a whole number of 2-bit packed words
+static int check_blob(bsa_ctx *c, int mode, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n){
+	uint64_t lim = seqs_bytes;
+	if(mode & BSA_MODE_SEQ2BIT){
+		if(seqs_bytes % 8u){ c->err = "BSA_MODE_SEQ2BIT: seqs_bytes must be a multiple of 8"; return BSA_E_ARG; }
+		lim = 4u * (uint64_t)seqs_bytes;
+	}
+	for(size_t k = 0; k < n; k++)
+		if(qoff[k] > lim || toff[k] > lim || qoff[k] + qlen[k] > lim || toff[k] + tlen[k] > lim){ c->err = "sequence offsets outside the blob"; return BSA_E_ARG; }
+	return BSA_OK;
+}
+
 // ---- a large host-pointer batch in TWO slices (round 6) --------------------------------------------------------------
 // A caller with host buffers pays the upload in front of the kernels and the download behind them: C2 176-180 ms against 72 ms on resident
 // inputs.  With the batch cut in two -- 50 000 pairs still fill the chip, smaller launches do not -- slice B's sequences
@@ -1084,7 +1169,8 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	if(se && se[0] == '1') return BSA_OK;
 	const uint32_t bw_req = (par->bandwidth + 15u) / 16u * 16u;
 	if(bw_req == 0 || !bsa_align8_supported_bw(bw_req) || (par->mode & BSA_MODE_ROWRECORDS)) return BSA_OK;
-	if(!forced && (n < 80000 || seqs_bytes < ((size_t)512 << 20))) return BSA_OK;
+	const bool packed = (par->mode & BSA_MODE_SEQ2BIT) != 0;
+	if(!forced && (n < 80000 || (packed ? 4u : 1u) * seqs_bytes < ((size_t)512 << 20))) return BSA_OK;      // (bases: a packed batch is sliced where its 1 B/base twin is)
 	if(n < 2 || (cigar && cigar_off && cigar_cap_words > ((size_t)1 << 31))) return BSA_OK;
 	// the cut: half of the bytes
 	size_t tot = 0, h = 0;
@@ -1092,10 +1178,15 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	{ size_t acc = 0; while(h < n && acc < tot / 2){ acc += (size_t)qlen[h] + tlen[h]; h++; } }
 	if(h == 0 || h >= n) return BSA_OK;
 	// the byte intervals a slice reads, merged (gaps below 64 KB travel along); many scattered intervals: not for this path
+	// (BSA_MODE_SEQ2BIT: the words that hold a base interval)
 	struct Iv { size_t lo, hi; };
+	auto bytes_of = [&](uint64_t off, uint32_t len) -> Iv {
+		if(!packed) return {(size_t)off, (size_t)off + len};
+		return {(size_t)(off / 32u) * 8u, (size_t)((off + len + 31u) / 32u) * 8u};
+	};
 	auto intervals = [&](size_t k0, size_t k1, std::vector<Iv> &v) -> bool {
 		std::vector<Iv> raw; raw.reserve(2 * (k1 - k0));
-		for(size_t k = k0; k < k1; k++){ if(qlen[k]) raw.push_back({(size_t)qoff[k], (size_t)qoff[k] + qlen[k]}); if(tlen[k]) raw.push_back({(size_t)toff[k], (size_t)toff[k] + tlen[k]}); }
+		for(size_t k = k0; k < k1; k++){ if(qlen[k]) raw.push_back(bytes_of(qoff[k], qlen[k])); if(tlen[k]) raw.push_back(bytes_of(toff[k], tlen[k])); }
 		std::sort(raw.begin(), raw.end(), [](const Iv &a, const Iv &b){ return a.lo < b.lo; });
 		for(const Iv &x : raw){
 			if(!v.empty() && x.lo <= v.back().hi + ((size_t)64 << 10)) v.back().hi = std::max(v.back().hi, x.hi);
@@ -1240,8 +1331,8 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		uint64_t *cigar_off, uint32_t *status){
 	if(n == 0){ if(cigar_off) cigar_off[0] = 0; return BSA_OK; }
 	if(!seqs || !qoff || !qlen || !toff || !tlen) return BSA_E_ARG;
-	for(size_t k = 0; k < n; k++)            // the staging kernel reads seqs + qoff[k] .. + qlen[k] unconditionally
-		if(qoff[k] + qlen[k] > seqs_bytes || toff[k] + tlen[k] > seqs_bytes){ c->err = "sequence offsets outside the blob"; return BSA_E_ARG; }
+	int rc = check_blob(c, par->mode, seqs_bytes, qoff, qlen, toff, tlen, n);          // the staging kernel reads seqs + qoff[k] .. + qlen[k] unconditionally
+	if(rc != BSA_OK) return rc;
 	(void)hipSetDevice(c->device);
 	// Whole-query bands (bandwidth 0, or one the register kernels do not have): a plan runs at ONE width, so a batch whose pairs
 	// fall into different width classes of the widened dispatch (bsa_align_plan_create) -- or some of whose queries are too long
@@ -1306,7 +1397,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 	uint32_t *st = status ? status : st_own.data();
 	auto tm1 = tm0;
 	bool sliced = false, codes = false;
-	int rc = align_batch_sliced(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, st, &sliced, &codes);
+	rc = align_batch_sliced(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, st, &sliced, &codes);
 	if(rc != BSA_OK) return rc;
 	if(!sliced){
 	rc = batch_host(c, seqs, seqs_bytes, n, out, cigar, cigar_cap_words, cigar_off, st,
@@ -1461,6 +1552,7 @@ struct bsa_edit_plan : PlanBase {
 	int32_t *d_sbeg = nullptr;
 	bool score_only = false;        // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
 	bool score_fast = false;        // ... on the SCORE forward kernels and k_edit_score_finish (global / extend: a last row a pair); overlap: the full path, trimmed
+	bool seq2bit = false;           // BSA_MODE_SEQ2BIT: d_seqs holds 2-bit packed words, offsets in bases (k_edit_stage2b)
 };
 
 extern "C" void bsa_edit_plan_destroy(bsa_edit_plan_t *p){ plan_free(p); }
@@ -1476,6 +1568,7 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	(void)hipSetDevice(c->device);
 	bsa_edit_plan *p = new bsa_edit_plan();
 	p->ctx = c; p->n = n; p->par = *par;
+	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
 	const auto tp0 = std::chrono::steady_clock::now();
 	std::vector<uint32_t> bwk(n), order(n), qwords(n);
 	double cells = 0;
@@ -1556,6 +1649,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 		size_t cigar_cap_words, uint64_t *d_cigar_off, uint32_t *d_status){
 	if(!p || !d_out) return BSA_E_ARG;
 	bsa_ctx *c = p->ctx;
+	if(p->seq2bit && ((uintptr_t)d_seqs & 7u)){ c->err = "BSA_MODE_SEQ2BIT: d_seqs must be 8-byte aligned"; return BSA_E_ARG; }
 	const uint32_t n = (uint32_t)p->n;
 	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;        // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
@@ -1568,7 +1662,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
 	HIPCHK(c, bsa_launch_edit_stage(d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, p->d_qpoff, p->d_tpoff, p->d_qboff, p->d_qwords,
-		p->d_qst, p->d_tst, p->d_qbits, status, n, st));
+		p->d_qst, p->d_tst, p->d_qbits, status, n, st, p->seq2bit));
 	EditArgs a;
 	memset(&a, 0, sizeof(a));
 	a.qst = p->d_qst; a.tst = p->d_tst; a.qpoff = p->d_qpoff; a.tpoff = p->d_tpoff;
@@ -1629,8 +1723,7 @@ static int edit_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		uint64_t *cigar_off, uint32_t *status){
 	if(n == 0){ if(cigar_off) cigar_off[0] = 0; return BSA_OK; }
 	if(!seqs || !qoff || !qlen || !toff || !tlen) return BSA_E_ARG;
-	for(size_t k = 0; k < n; k++)
-		if(qoff[k] + qlen[k] > seqs_bytes || toff[k] + tlen[k] > seqs_bytes){ c->err = "sequence offsets outside the blob"; return BSA_E_ARG; }
+	if(check_blob(c, par->mode, seqs_bytes, qoff, qlen, toff, tlen, n) != BSA_OK) return BSA_E_ARG;
 	(void)hipSetDevice(c->device);
 	bsa_edit_plan_t *p = nullptr;
 	const bool timing = bsa_env("BSA_BATCH_TIMING") != nullptr;        // host-side phase times on stderr

@@ -1437,14 +1437,54 @@ __global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const u
 	if(lane == 0) status[k] = st;
 }
 
+// k_edit_stage for BSA_MODE_SEQ2BIT blobs: base offsets into 2-bit packed words (bsa_common.h, bsa_bits16).  The two planes come straight
+// from the bits (bit 0 / bit 1 of each base de-interleaved), the staged bytes from spreading them; zero beyond the sequence, no
+// BSA_ST_BAD_BASE (no code is above 3)
+template<int TPP>
+__global__ void __launch_bounds__(256) k_edit_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
+		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
+		const uint64_t *qboff, const uint32_t *qwords, uint8_t *qst, uint8_t *tst, u64 *qbits, uint32_t *status, uint32_t n){
+	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
+	if(k >= n) return;
+	const uint32_t ql = qlen[k], tl = tlen[k], nw = qwords[k];
+	const uint64_t qo = qoff[k], to = toff[k];
+	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
+	u64 *p0 = qbits + qboff[k], *p1 = p0 + nw;
+	const uint32_t qbytes = (ql + 16u + 15u) & ~15u, qplane = nw * 64u;
+	for(uint32_t i = lane * 16u; i < max(qbytes, qplane); i += (uint32_t)TPP * 16u){
+		const uint32_t x = bsa_bits16(seqs, qo + i, qo + ql);
+		if(i < qbytes){
+			const u64 v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
+			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dq + i) = o;
+		}
+		if(i < qplane){
+			((uint16_t*)p0)[i >> 4] = (uint16_t)bsa_even16(x);
+			((uint16_t*)p1)[i >> 4] = (uint16_t)bsa_even16(x >> 1);
+		}
+	}
+	const uint32_t tbytes = (tl + 16u + 15u) & ~15u;
+	for(uint32_t i = lane * 16u; i < tbytes; i += (uint32_t)TPP * 16u){
+		const uint32_t x = bsa_bits16(seqs, to + i, to + tl);
+		const u64 v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
+		uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dt + i) = o;
+	}
+	if(lane == 0) status[k] = (ql == 0 || tl == 0) ? BSA_ST_EMPTY : 0u;
+}
+
 bool bsa_edit_supported_bw(uint32_t bw){       // register kernels up to 16 words, the generic kernel beyond
 	return bw >= 64 && (bw % 64) == 0;
 }
 
 hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
-		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st){
+		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit){
 	if(n == 0) return hipSuccess;
+	if(seq2bit){
+		const uint64_t *w = (const uint64_t*)seqs;
+		if(n >= 65536u) hipLaunchKernelGGL(k_edit_stage2b<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, w, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
+		else hipLaunchKernelGGL(k_edit_stage2b<256>, dim3(n), dim3(256), 0, st, w, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
+		return hipGetLastError();
+	}
 	if(n >= 65536u) hipLaunchKernelGGL(k_edit_stage<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, seqs, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
 	else hipLaunchKernelGGL(k_edit_stage<256>, dim3(n), dim3(256), 0, st, seqs, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
 	return hipGetLastError();

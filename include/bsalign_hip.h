@@ -53,6 +53,22 @@ extern "C" {
                                       Edit aligner: fast (forward kernel alone, the last row a pair instead of every row's planes) in
                                       global and extend mode at every bandwidth; overlap mode needs the walk's tb for its score
                                       (smin + te - tb) and runs the full path, dropping what the traceback found. */
+#define BSA_MODE_SEQ2BIT 0x800    /* flag: the sequence blob is 2-bit packed -- for bsa_align_batch / _plan_create / _run and bsa_edit_batch /
+                                      _plan_create / _run.  seqs / d_seqs then points to uint64_t words holding 32 bases each, MSB first:
+                                      base i sits at bits 62 - 2 (i % 32) of word i / 32 (little-endian words).  Example: the 35 bases
+                                      ACGT ACGT ... (codes 0 1 2 3 repeated) are word 0 = 0x1B1B1B1B1B1B1B1B and word 1 = 0x1800000000000000 (bases
+                                      32..34 = A C G in its top six bits).  This is the layout of the reference's BaseBank.bits (dna.h,
+                                      seq2bits / bits2bit), so a caller holding a BaseBank passes bnk->bits and its own read offsets.
+                                      qoff[k] / toff[k] are BASE offsets into the words, any offset (a read need not start on a word or a
+                                      byte); seqs_bytes is the size of the word array in bytes and must be a multiple of 8; every pair must
+                                      have off + len <= 4 * seqs_bytes, else BSA_E_ARG.  d_seqs must be 8-byte aligned (bsa_align_run /
+                                      bsa_edit_run: BSA_E_ARG otherwise).  Nothing is read behind the word that holds a pair's last base.
+                                      Results, CIGAR words and status are bit-identical to the same call on the unpacked bytes, except that
+                                      BSA_ST_BAD_BASE cannot occur.  Combines with BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS.  Only the
+                                      upload and the staging kernels see the packed form: the kernels behind them read the same staged
+                                      1 B/base copy as without the flag.  Not taken by bsa_kmer_edit_batch, the compat single-pair layer,
+                                      the bsalign-hip CLI, bsa_shard_*, the POA or the rows API.  bsa_seq_pack2bit packs device-resident
+                                      1 B/base codes. */
 
 /* CIGAR op codes (bsalign.h:61-69) */
 #define BSA_CIGAR_M 0
@@ -461,6 +477,11 @@ int bsa_synth_pairs_host(uint64_t seed, uint64_t first_pair, size_t n, uint32_t 
                          uint8_t *seqs, uint32_t *qlen);
 int bsa_synth_pairs_dev(bsa_ctx_t *ctx, uint64_t seed, uint64_t first_pair, size_t n, uint32_t L, uint32_t err_q32,
                         uint8_t *d_seqs, uint32_t *d_qlen);
+
+/* device codes (one base per byte) -> BSA_MODE_SEQ2BIT words, asynchronous on the context stream: ceil(nbases / 32) words, each code
+ * packed as c & 3, the bits behind the last base zero.  d_bad (device, may be NULL) is set to 1 when any code is above 3 and
+ * left as it is otherwise (the caller clears it). */
+int bsa_seq_pack2bit(bsa_ctx_t *ctx, const uint8_t *d_codes, uint64_t nbases, uint64_t *d_bits, uint32_t *d_bad);
 
 #ifdef __cplusplus
 }
