@@ -7,8 +7,12 @@ of synthetic read pairs that is already resident in HBM.  Default workload = BAS
 torch.distributed.run, one rank per GPU) every rank aligns its own 100 k pairs (weak scaling, no data-path
 collective: pairs are independent); RCCL is used only for the barrier / max-over-ranks of the timing.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric GCUPS, roofline of the dominant
-kernel (forward DP) measured with HIP events inside the library, and a CPU baseline of the same workload.
+Prints ONE JSON line on rank 0 (contract in the task statement): metric GCUPS and the roofline of the dominant
+kernel (forward DP) measured with HIP events inside the library during the timed steps.  A plain run does only that:
+set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds what takes time of its own
+outside the steps: the parity spot check against the oracle, a CPU baseline of the same workload, the PCIe-inclusive
+host-pointer call, the shard exchange on the timed batch, per-launch kernel times of the POA lines, the reference's
+end-to-end POA leg and, for the default configuration, the secondary workloads (C3, POA, whole-query bands).
 """
 import argparse
 import ctypes as C
@@ -84,7 +88,10 @@ def parse():
     ap.add_argument("--mode", default="global", choices=["global", "overlap", "extend"], help="pairwise workloads only (the headline configurations are global)")
     ap.add_argument("--eps", type=float, default=0.10)
     ap.add_argument("--scoring", default="2,-6,-3,-2,0,0", help="M,X,O,E,Q,P (reference CLI defaults, main.c:264)")
-    ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs of the CPU baseline sample (0 = auto, -1 = skip)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure also run the parity spot check, the CPU baseline, the PCIe-inclusive call, the shard "
+                    "exchange, the POA lines' per-launch kernel times and end-to-end leg and, for the default configuration, the secondary workloads")
+    ap.add_argument("--cpu-pairs", type=int, default=0, help="with --full: pairs of the CPU baseline sample (0 = auto, -1 = skip the baseline, the PCIe-inclusive call, the "
+                    "exchange and the POA end-to-end leg)")
     ap.add_argument("--workspace-gb", type=float, default=0.0)
     ap.add_argument("--poa-source", default="auto", choices=["auto", "synthetic", "recorded", "fixture"], help="poa workload: graph programs recorded from the reference's end_bspoa on "
                     "synthetic reads (needs oracle/_ref; the default when it is there), the programs the reference recorded into tests/golden/poa_graph.npz tiled over the windows "
@@ -94,8 +101,8 @@ def parse():
     ap.add_argument("--cpu-worker", default="", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true", help="only start the ranks, count them over the process group, run the shard exchange on a small synthetic "
                     "batch and print {n_gpus, exchange}: the launcher's own test (gloo when there is no GPU)")
-    ap.add_argument("--no-secondary", action="store_true", help="default run only: do not measure the edit (C3) and POA (C4-shaped) workloads beside the headline one")
-    ap.add_argument("--no-exchange", action="store_true", help="skip the scatter / align / gather self-check of the shard exchange after the timed region")
+    ap.add_argument("--no-secondary", action="store_true", help="default configuration with --full: do not measure the edit (C3) and POA (C4-shaped) workloads beside the headline one")
+    ap.add_argument("--no-exchange", action="store_true", help="with --full: skip the scatter / align / gather self-check of the shard exchange after the timed region")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what the last of them computed (rank 0's batch) as DIR/<name>.npy (e.g. bench_outputs/), "
                     "float64, at most 64 MB in all: the records of every pair (a fixed, seeded sample of %d above that many) and the CIGAR words of a seeded "
                     "sample of them; poa: every program's result and a seeded sample of the walks or row blocks" % DUMP_RECORDS)
@@ -521,7 +528,7 @@ def main_poa_recorded(args):
         nreads, L = 12, (args.length or 1500)
         pp = P.par()
         windows = [P.synth_reads((SEED + 977 * w) & 0x7FFFFFFF, L, nreads, eps=(args.eps,)) for w in range(nwin)]
-        _, t_ref = P.run_many(windows, 0, pp, threads=ncores)
+        t_ref = P.run_many(windows, 0, pp, threads=ncores)[1] if args.full else None        # (the CPU baseline's whole end_bspoa)
         rec, _ = P.run_many(windows, 1, pp, threads=ncores, record=2)
         core_seconds = sum(w["core_seconds"] for w in rec)
         updates = sum(w["core_updates"] for w in rec)
@@ -589,54 +596,11 @@ def main_poa_recorded(args):
         launch_of = np.concatenate([np.full(n, i, dtype=np.int64) for i, (_, n, _, _, _, _) in enumerate(launches)])
         cap = np.concatenate([[2 * (rc["slen"] + len(rc["nodes"])) + 64 for rc in rcs] for _, _, _, _, _, rcs in launches]).astype(np.int64)
         dumped = dump_poa_graph(args.dump_outputs, res_all, packed, launch_of, cap)
-    kms_tot = 0.0
-    for sp, n, nn, msl, dv, _ in launches:
-        launch(sp, n, nn, msl, dv)
-        kms_tot += ctx.last_kernel_ms()[0]
-    ident, steps_total = True, 0
-    for sp, n, nn, msl, dv, rcs in launches:
-        res = dv["res"].cpu().numpy().view(B.POA_RESULT_DTYPE)
-        for i, rc in enumerate(rcs):
-            gi = int(rc["nodes"][int(res[i]["maxidx"])]["gnode"]) if res[i]["maxidx"] >= 0 else -1
-            ident &= res[i]["status"] == 0 and (int(res[i]["maxscr"]), gi, int(res[i]["maxoff"])) == (rc["maxscr"], rc["maxidx"], rc["maxoff"])
-            steps_total += int(res[i]["nevents"])
-    # lock-step end to end: the reference's host code per window on host threads, every sweep + walk through the batcher
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    e2e = None
-    try:
-        if fixture:
-            raise RuntimeError("not run: the end-to-end leg drives the reference's own host code (oracle/_ref)")
-        if args.cpu_pairs < 0:
-            raise RuntimeError("not run (--cpu-pairs -1: the timed launches only, as the profiler's counter passes want them)")
-        from test_poa_batched_gpu import Batcher
-        bt = Batcher(ctx, nwin)
-        try:
-            devres, t_dev = P.run_many(windows, 7, pp)
-            st = bt.stats()
-        finally:
-            bt.close()
-        base, _ = P.run_many(windows, 0, pp, threads=ncores)
-        same = all(np.array_equal(a["cns"], b["cns"]) and a["msa"] == b["msa"] for a, b in zip(base, devres))
-        e2e = {"windows_per_s": round(nwin / t_dev, 2), "seconds": round(t_dev, 3), "identical_to_reference": bool(same), "batches": st["batches"], "launches": st["launches"],
-               "MB_up": round(st["bytes_up"] / 1e6, 1), "MB_down": round(st["bytes_down"] / 1e6, 1), "device_s": round(st["device_us"] / 1e6, 3),
-               "note": "host side = the reference's own C (oracle/_ref) on one thread per window, one runnable thread per CPU; informational, not the measured value"}
-    except Exception as ex:          # the checker is optional here
-        e2e = {"error": str(ex)}
     nl = len(launches)
-    achieved = (balg / nl) / (kms_tot / nl / 1e3) / 1e9 if kms_tot > 0 else 0.0
+    steps_total = sum(int(dv["res"].cpu().numpy().view(B.POA_RESULT_DTYPE)[:n]["nevents"].astype(np.int64).sum()) for _, n, _, _, dv, _ in launches)
     shape = "poa-%s|n%d|reads%d|L%d" % (("fixture%d" % args.poa_case if args.poa_case else "fixture") if fixture else "recorded", nwin, nreads, L)
     pardesc = ("default POA parameters (overlap, bandwidth 128, 2-piece gaps)" if (not fixture or args.poa_case == 0) else
                "mode %d, bandwidth %d, M %d X %d O %d E %d Q %d P %d" % (pp["alnmode"], pp["bandwidth"], pp["M"], pp["X"], pp["O"], pp["E"], pp["Q"], pp["P"]))
-    ent = counters_for(shape, "k_poa_wf")
-    traffic = traffic_of(ent)
-    if fixture:
-        cpub = {"value": None, "unit": "GCUPS", "cores": 0, "kind": "reference", "sample": "not measured: oracle/_ref is absent and the fixture holds programs, not reads (the default "
-                "source, recorded, times the reference's align_rd_bspoacore on the same windows)"}
-    else:
-        cpub = {"value": round(updates * 128 / (t_ref * 0 + core_seconds / ncores) / 1e9, 4) if core_seconds > 0 else None, "unit": "GCUPS", "cores": ncores, "kind": "reference",
-                         "sample": "the reference's align_rd_bspoacore inside end_bspoa of the same %d windows on %d host threads (one window per thread at a time): %.2f s summed over threads "
-                                   "= %.4f GCUPS per core; the whole end_bspoa of all windows: %.2f s = %.1f windows/s" % (nwin, ncores, core_seconds, updates * 128 / core_seconds / 1e9 if core_seconds > 0 else 0, t_ref, nwin / t_ref),
-                         "end_bspoa_windows_per_s": round(nwin / t_ref, 2), "threads": ncores}
     line = {
         "metric": "GCUPS (giga band-cell updates / s), POA seq->graph DP (align_rd_bspoacore) + traceback (alignment2graph_bspoa) on " +
                   ("the committed fixture programs, tiled: every window the same reads" if fixture else "recorded programs"),
@@ -649,17 +613,62 @@ def main_poa_recorded(args):
                                ("; a step = every read's sweep and traceback of every window, read r of all windows per launch (%d launches, %d programs, %.0f row updates + %.0f merges, "
                                 "%d traceback steps)" % (nl, nprog_total, updates, merges, steps_total)),
                    "shape": shape, "windows": nwin, "pairs_per_gpu": nwin, "bandwidth": int(pp["bandwidth"]), "reads": nreads, "length": L, "sweep_windows_per_s": round(nwin * args.steps / elapsed, 1)},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                     "kernel": "k_poa_wf<%d, %d> (row-at-a-time forward pass, plain nodes in copies of their own + traceback in tiles)" % (
-                         2 if (pp["Q"] or pp["P"]) else 1 if pp["O"] else 0, 1 if int(pp["bandwidth"]) <= 64 else 2 if int(pp["bandwidth"]) <= 128 else 4), "kernel_ms_avg": round(kms_tot / nl, 3), "launches_per_step": nl, "algorithmic_bytes_per_launch": round(balg / nl, 1),
-                     "issue": issue_fractions(ent, kms_tot / nl),
-                     "traffic_from": (ent or {}).get("source") if traffic else None,
-                     "note": "not HBM-bound: one wave per read, a graph node per trip (about 180 instructions); a lone wave is bound by its own dependent latencies, thousands of "
-                             "windows in flight by VALU issue (HISTORY section 4b); about 6 KB of LDS per read, five waves per SIMD"},
-        "checks": {"best_end_cell_identical_all_programs": bool(ident), "programs": nprog_total},
-        "cpu_baseline": cpub,
-        "lockstep_end_to_end": e2e,
     }
+    if args.full:
+        # per-launch kernel times: every launch once more, on its own
+        kms_tot = 0.0
+        for sp, n, nn, msl, dv, _ in launches:
+            launch(sp, n, nn, msl, dv)
+            kms_tot += ctx.last_kernel_ms()[0]
+        ident = True
+        for sp, n, nn, msl, dv, rcs in launches:
+            res = dv["res"].cpu().numpy().view(B.POA_RESULT_DTYPE)
+            for i, rc in enumerate(rcs):
+                gi = int(rc["nodes"][int(res[i]["maxidx"])]["gnode"]) if res[i]["maxidx"] >= 0 else -1
+                ident &= res[i]["status"] == 0 and (int(res[i]["maxscr"]), gi, int(res[i]["maxoff"])) == (rc["maxscr"], rc["maxidx"], rc["maxoff"])
+        # lock-step end to end: the reference's host code per window on host threads, every sweep + walk through the batcher
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        e2e = None
+        try:
+            if fixture:
+                raise RuntimeError("not run: the end-to-end leg drives the reference's own host code (oracle/_ref)")
+            if args.cpu_pairs < 0:
+                raise RuntimeError("not run (--cpu-pairs -1: the timed launches only, as the profiler's counter passes want them)")
+            from test_poa_batched_gpu import Batcher
+            bt = Batcher(ctx, nwin)
+            try:
+                devres, t_dev = P.run_many(windows, 7, pp)
+                st = bt.stats()
+            finally:
+                bt.close()
+            base, _ = P.run_many(windows, 0, pp, threads=ncores)
+            same = all(np.array_equal(a["cns"], b["cns"]) and a["msa"] == b["msa"] for a, b in zip(base, devres))
+            e2e = {"windows_per_s": round(nwin / t_dev, 2), "seconds": round(t_dev, 3), "identical_to_reference": bool(same), "batches": st["batches"], "launches": st["launches"],
+                   "MB_up": round(st["bytes_up"] / 1e6, 1), "MB_down": round(st["bytes_down"] / 1e6, 1), "device_s": round(st["device_us"] / 1e6, 3),
+                   "note": "host side = the reference's own C (oracle/_ref) on one thread per window, one runnable thread per CPU; informational, not the measured value"}
+        except Exception as ex:          # the checker is optional here
+            e2e = {"error": str(ex)}
+        achieved = (balg / nl) / (kms_tot / nl / 1e3) / 1e9 if kms_tot > 0 else 0.0
+        ent = counters_for(shape, "k_poa_wf")
+        traffic = traffic_of(ent)
+        if fixture:
+            cpub = {"value": None, "unit": "GCUPS", "cores": 0, "kind": "reference", "sample": "not measured: oracle/_ref is absent and the fixture holds programs, not reads (the default "
+                    "source, recorded, times the reference's align_rd_bspoacore on the same windows)"}
+        else:
+            cpub = {"value": round(updates * 128 / (t_ref * 0 + core_seconds / ncores) / 1e9, 4) if core_seconds > 0 else None, "unit": "GCUPS", "cores": ncores, "kind": "reference",
+                    "sample": "the reference's align_rd_bspoacore inside end_bspoa of the same %d windows on %d host threads (one window per thread at a time): %.2f s summed over threads "
+                              "= %.4f GCUPS per core; the whole end_bspoa of all windows: %.2f s = %.1f windows/s" % (nwin, ncores, core_seconds, updates * 128 / core_seconds / 1e9 if core_seconds > 0 else 0, t_ref, nwin / t_ref),
+                    "end_bspoa_windows_per_s": round(nwin / t_ref, 2), "threads": ncores}
+        line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                            "kernel": "k_poa_wf<%d, %d> (row-at-a-time forward pass, plain nodes in copies of their own + traceback in tiles)" % (
+                                2 if (pp["Q"] or pp["P"]) else 1 if pp["O"] else 0, 1 if int(pp["bandwidth"]) <= 64 else 2 if int(pp["bandwidth"]) <= 128 else 4), "kernel_ms_avg": round(kms_tot / nl, 3), "launches_per_step": nl, "algorithmic_bytes_per_launch": round(balg / nl, 1),
+                            "issue": issue_fractions(ent, kms_tot / nl),
+                            "traffic_from": (ent or {}).get("source") if traffic else None,
+                            "note": "not HBM-bound: one wave per read, a graph node per trip (about 180 instructions); a lone wave is bound by its own dependent latencies, thousands of "
+                                    "windows in flight by VALU issue (HISTORY section 4b); about 6 KB of LDS per read, five waves per SIMD"}
+        line["checks"] = {"best_end_cell_identical_all_programs": bool(ident), "programs": nprog_total}
+        line["cpu_baseline"] = cpub
+        line["lockstep_end_to_end"] = e2e
     if dumped is not None:
         line["outputs_dumped"] = dumped
     emit(line)
@@ -771,21 +780,23 @@ def main_poa(args):
         dumped = dump_outputs(args.dump_outputs, {"window_index": idx, "results": np.stack([res[f][idx] for f in ("maxscr", "maxidx", "maxoff")], axis=1),
                                                   "row_byte_offset": pos, "row_bytes": rb})
     if rank == 0:
-        import poa_support as P
-        # parity spot check (outside the timed region): the K distinct programs vs the oracle, rows and results
-        ident = True
-        rows_host = d_rows[: int(blocks[:K].sum()) * blk].cpu().numpy()
-        pw = S_oracle_piecewise(pp, bw)
-        used = bw * (pw + 1) + 68
-        for k in range(K):
-            t = tasks[first[k]:first[k] + ntask[k]].copy()
-            t["query"] = 0
-            orows, ores = P.oracle_sweep(t, np.array([(0, ntask[k], 0, 0)], dtype=P.PROG_DTYPE), queries[k], np.zeros(1, np.uint64),
-                                         np.array([qlen[k]], np.uint32), dict(pp), bw, nblk[k], pw)
-            b0 = int(progs[k]["first_block"])
-            mine = rows_host[b0 * blk:(b0 + nblk[k]) * blk].reshape(nblk[k], blk)[1:, :used]
-            ident &= bool(np.array_equal(mine, orows.reshape(nblk[k], blk)[1:, :used]))
-            ident &= (int(res[k]["maxscr"]), int(res[k]["maxidx"]), int(res[k]["maxoff"])) == (int(ores[0]["maxscr"]), int(ores[0]["maxidx"]), int(ores[0]["maxoff"]))
+        ident = None
+        if args.full:
+            import poa_support as P
+            # parity spot check (outside the timed region): the K distinct programs vs the oracle, rows and results
+            ident = True
+            rows_host = d_rows[: int(blocks[:K].sum()) * blk].cpu().numpy()
+            pw = S_oracle_piecewise(pp, bw)
+            used = bw * (pw + 1) + 68
+            for k in range(K):
+                t = tasks[first[k]:first[k] + ntask[k]].copy()
+                t["query"] = 0
+                orows, ores = P.oracle_sweep(t, np.array([(0, ntask[k], 0, 0)], dtype=P.PROG_DTYPE), queries[k], np.zeros(1, np.uint64),
+                                             np.array([qlen[k]], np.uint32), dict(pp), bw, nblk[k], pw)
+                b0 = int(progs[k]["first_block"])
+                mine = rows_host[b0 * blk:(b0 + nblk[k]) * blk].reshape(nblk[k], blk)[1:, :used]
+                ident &= bool(np.array_equal(mine, orows.reshape(nblk[k], blk)[1:, :used]))
+                ident &= (int(res[k]["maxscr"]), int(res[k]["maxidx"]), int(res[k]["maxoff"])) == (int(ores[0]["maxscr"]), int(ores[0]["maxidx"]), int(ores[0]["maxoff"]))
         # algorithmic bytes: one row block read + one written per row update; a merge reads two and writes one
         balg = (2.0 * updates + 3.0 * merges) * blk
         achieved = balg / (kms / 1e3) / 1e9 if kms > 0 else 0.0
@@ -805,11 +816,12 @@ def main_poa(args):
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                          "traffic": traffic, "kernel": "k_sweep", "kernel_ms_avg": round(kms, 3), "launches_per_step": klaunch,
                          "algorithmic_bytes_per_launch": round(balg, 1)},
-            "checks": {"oracle_identical_first8_programs": ident},
         }
+        if ident is not None:
+            line["checks"] = {"oracle_identical_first8_programs": ident}
         if dumped is not None:
             line["outputs_dumped"] = dumped
-        if world == 1 and args.cpu_pairs >= 0:
+        if args.full and world == 1 and args.cpu_pairs >= 0:
             line["cpu_baseline"] = poa_cpu_baseline(args, bw)
         emit(line)
     ctx.close()
@@ -942,12 +954,12 @@ def main():
     # (before anything below reuses the CIGAR buffer: the shard exchange aligns into it)
     dumped = dump_pairwise(args.dump_outputs, n, out, off, status, qlen, tlen, d_cig) if args.dump_outputs and rank == 0 else None
 
-    # ---- outside the timed region: what a caller with HOST buffers pays (PCIe-inclusive, never `value`), and the shard exchange on this very batch
+    # ---- --full, outside the timed region: what a caller with HOST buffers pays (PCIe-inclusive, never `value`), and the shard exchange on this very batch
     pcie_ms = None
     pcie_first_ms = None
     exchange = None
     host = None
-    if not args.no_exchange and args.cpu_pairs >= 0:
+    if args.full and not args.no_exchange and args.cpu_pairs >= 0:
         plan.close()
         plan = None
         if rank == 0:
@@ -975,17 +987,20 @@ def main():
             del h_cig
 
     if rank == 0:
-        import support as S
-        # parity spot check (outside the timed region): first pairs of the batch vs the oracle
-        ident = True
-        cig_host = d_cig[: int(off[8])].cpu().numpy().view(np.uint32) if n >= 8 else None
-        for k in range(min(8, n)):
-            q, t = S.synth_pair(k, L, err_q32=int(args.eps * 4294967296.0))
-            if args.workload == "align8":
-                res, cig, _ = S.oracle_align(q, t, mode, bw, *sc)
-            else:
-                res, cig, _ = S.oracle_edit(q, t, mode, bw)
-            ident &= bool(np.array_equal(out[k], res)) and bool(np.array_equal(cig_host[int(off[k]):int(off[k + 1])], cig))
+        checks = {"pairs_flagged": nbad, "cigar_words": ncig}
+        if args.full:
+            import support as S
+            # parity spot check (outside the timed region): first pairs of the batch vs the oracle
+            ident = True
+            cig_host = d_cig[: int(off[8])].cpu().numpy().view(np.uint32) if n >= 8 else None
+            for k in range(min(8, n)):
+                q, t = S.synth_pair(k, L, err_q32=int(args.eps * 4294967296.0))
+                if args.workload == "align8":
+                    res, cig, _ = S.oracle_align(q, t, mode, bw, *sc)
+                else:
+                    res, cig, _ = S.oracle_edit(q, t, mode, bw)
+                ident &= bool(np.array_equal(out[k], res)) and bool(np.array_equal(cig_host[int(off[k]):int(off[k + 1])], cig))
+            checks["oracle_identical_first8"] = ident
         # algorithmic bytes: 4-bit (8-bit path) / 2-bit (edit) traceback code per band cell +
         # sequences at 1 B/base + result struct + CIGAR words
         # (two-piece gaps: 8 bits per cell, SURVEY.md 8(d) / bsalign.h:47-54)
@@ -1028,15 +1043,15 @@ def main():
                          "traffic_from": (ent or {}).get("source") if traffic else None,
                          "other_kernel": {"kernel": fwd_name if dom_trace else trace_name, "kernel_ms_avg": round(kms if dom_trace else tms, 3),
                                           "launches_per_step": klaunch if dom_trace else tlaunch}},
-            "checks": {"pairs_flagged": nbad, "cigar_words": ncig, "oracle_identical_first8": ident},
+            "checks": checks,
         }
         if dumped is not None:
             line["outputs_dumped"] = dumped
-        if world == 1 and args.cpu_pairs >= 0:
+        if args.full and world == 1 and args.cpu_pairs >= 0:
             line["cpu_baseline"] = cpu_baseline(args, L, bw, sc, mode)
-    # ---- the shard exchange on this very batch, after the line is complete: a fault or a hang of the exchange (RCCL at more than one rank has only
-    # ever run here over gloo / shared memory: no multi-GPU node) must not cost the run its measured line
-    if not args.no_exchange and args.cpu_pairs >= 0:
+    # ---- --full: the shard exchange on this very batch, after the line is complete: a fault or a hang of the exchange (RCCL at more than one rank has
+    # only ever run over gloo / shared memory: no multi-GPU node) must not cost the run its measured line
+    if args.full and not args.no_exchange and args.cpu_pairs >= 0:
         import threading
         finished = threading.Event()
         limit = float(os.environ.get("BSA_BENCH_EXCHANGE_TIMEOUT", "300"))
@@ -1084,7 +1099,7 @@ def main():
     if rank == 0:
         default_run = (world == 1 and args.workload == "align8" and not args.pairs and not args.length and not args.bw and args.mode == "global"
                        and args.scoring == "2,-6,-3,-2,0,0" and args.cpu_pairs >= 0 and not args.no_secondary and not os.environ.get("BSA_BENCH_NO_SECONDARY"))
-        if default_run:
+        if args.full and default_run:
             # the other two configurations BASELINE.json names (C3, C4-shaped windows) in the same run, under the same clock: the device is free again here
             torch.cuda.empty_cache()
             line["secondary"] = secondary_lines(args)
@@ -1092,16 +1107,16 @@ def main():
 
 
 def secondary_lines(args):
-    """`bench.py` with no workload flags also measures the edit path (C3: 32768 x 100 kbp, bandwidth 256), the POA's sweep + walk (4096 windows x 12 reads x
+    """`bench.py --full` with no workload flags also measures the edit path (C3: 32768 x 100 kbp, bandwidth 256), the POA's sweep + walk (4096 windows x 12 reads x
     1.5 kbp: programs recorded from the reference's end_bspoa where oracle/_ref exists, else the committed fixture programs) and whole-query bands with scores
-    outside the static guard (2048 x 10 kbp, 10,-30,-20,-10) -- each as a run of this very script
-    with its own steps, roofline and cpu_baseline, its JSON line embedded under "secondary"."""
+    outside the static guard (2048 x 10 kbp, 10,-30,-20,-10) -- each as a --full run of this very script
+    with its own steps, roofline, checks and cpu_baseline, its JSON line embedded under "secondary"."""
     import subprocess
     out = []
     # (third: `bsalign align -W 0` with scores outside the static exactness guard -- the shape that ran below the CPU until round 6 -- on the checked systolic kernel)
-    for extra in (["--workload", "edit", "--steps", "3", "--warmup", "1", "--no-exchange"],
-                  ["--workload", "poa", "--pairs", "4096", "--steps", "5", "--warmup", "1"],
-                  ["--pairs", "2048", "--length", "10000", "--bw", "-1", "--scoring", "10,-30,-20,-10,0,0", "--steps", "3", "--warmup", "1", "--no-exchange"]):
+    for extra in (["--full", "--workload", "edit", "--steps", "3", "--warmup", "1", "--no-exchange"],
+                  ["--full", "--workload", "poa", "--pairs", "4096", "--steps", "5", "--warmup", "1"],
+                  ["--full", "--pairs", "2048", "--length", "10000", "--bw", "-1", "--scoring", "10,-30,-20,-10,0,0", "--steps", "3", "--warmup", "1", "--no-exchange"]):
         t0 = time.perf_counter()
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra, capture_output=True, text=True, timeout=900)

@@ -536,7 +536,7 @@ def test_checked_systolic_kernel_flags_what_the_int8_arithmetic_clamps(ctx):
 def test_host_pointer_batch_in_two_slices(ctx, mode, monkeypatch):
     """bsa_align_batch on host buffers cuts a large batch in two so that the second half's sequences travel while the first half's kernels run and
     the first half's results go back while the second half's run (forced here: BSA_BATCH_SLICES=2): results, status words, CIGAR offsets and
-    words equal the unsliced call's (BSA_BATCH_SLICES=1) and the oracle's.  (bench.py's full-size check `host_pointer_call_identical` runs the
+    words equal the unsliced call's (BSA_BATCH_SLICES=1) and the oracle's.  (`bench.py --full`'s full-size check `host_pointer_call_identical` runs the
     sliced path on its own blob layout: all targets, then all queries -- two byte intervals a slice.)"""
     import bsalign_amd as B
     rng = np.random.default_rng(5150 + mode)

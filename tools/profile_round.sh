@@ -38,10 +38,10 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_ACTIV
 	timeout 900 rocprofv3 --pmc $set --output-format csv -d $OUT -o align8_pmc_sq_$tag -- python bench.py --steps 1 --warmup 0 --cpu-pairs -1 > $OUT/align8_pmc_sq_$tag.log 2>&1
 done
 # the bench lines themselves (with the CPU baseline), outside the profiler
-timeout 900 python bench.py --steps 3 --warmup 1 > $OUT/align8_bench_line.json 2> $OUT/align8_bench_line.err
-timeout 900 python bench.py --workload edit --steps 3 --warmup 1 > $OUT/edit_bench_line.json 2> $OUT/edit_bench_line.err
-timeout 900 python bench.py --workload poa --steps 2 --warmup 1 > $OUT/poa_bench_line.json 2> $OUT/poa_bench_line.err
-timeout 900 python bench.py $EF --steps 3 --warmup 1 --cpu-pairs 40 > $OUT/editfull_bench_line.json 2> $OUT/editfull_bench_line.err
+timeout 900 python bench.py --full --steps 3 --warmup 1 > $OUT/align8_bench_line.json 2> $OUT/align8_bench_line.err
+timeout 900 python bench.py --full --workload edit --steps 3 --warmup 1 > $OUT/edit_bench_line.json 2> $OUT/edit_bench_line.err
+timeout 900 python bench.py --full --workload poa --steps 2 --warmup 1 > $OUT/poa_bench_line.json 2> $OUT/poa_bench_line.err
+timeout 900 python bench.py --full $EF --steps 3 --warmup 1 --cpu-pairs 40 > $OUT/editfull_bench_line.json 2> $OUT/editfull_bench_line.err
 # keep only the small summaries (the merge back is capped at 64 MiB)
 find $OUT -name '*.db' -delete
 find $OUT -name '*_kernel_trace.csv' -delete

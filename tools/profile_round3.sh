@@ -32,11 +32,11 @@ for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY"; do
 	timeout -s KILL 600 rocprofv3 --pmc $set --output-format csv -d $OUT -o poarec_pmc_sq -- python bench.py --workload poa --steps 1 --warmup 0 --cpu-pairs -1 > $OUT/poarec_pmc_sq.log 2>&1 < /dev/null
 done
 # the bench lines themselves (with the CPU baseline), outside the profiler
-timeout -s KILL 600 python bench.py --steps 3 --warmup 1 > $OUT/align8_bench_line.json 2> $OUT/align8_bench_line.err < /dev/null
-timeout -s KILL 600 python bench.py $WQ --steps 3 --warmup 1 --cpu-pairs 40 > $OUT/align8wq_bench_line.json 2> $OUT/align8wq_bench_line.err < /dev/null
-timeout -s KILL 600 python bench.py --workload poa --steps 2 --warmup 1 > $OUT/poarec_bench_line.json 2> $OUT/poarec_bench_line.err < /dev/null
-timeout -s KILL 600 python bench.py --workload poa --pairs 4096 --steps 2 --warmup 1 > $OUT/poarec4096_bench_line.json 2> $OUT/poarec4096_bench_line.err < /dev/null
-timeout -s KILL 600 python bench.py --workload edit --steps 3 --warmup 1 > $OUT/edit_bench_line.json 2> $OUT/edit_bench_line.err < /dev/null
+timeout -s KILL 600 python bench.py --full --steps 3 --warmup 1 > $OUT/align8_bench_line.json 2> $OUT/align8_bench_line.err < /dev/null
+timeout -s KILL 600 python bench.py --full $WQ --steps 3 --warmup 1 --cpu-pairs 40 > $OUT/align8wq_bench_line.json 2> $OUT/align8wq_bench_line.err < /dev/null
+timeout -s KILL 600 python bench.py --full --workload poa --steps 2 --warmup 1 > $OUT/poarec_bench_line.json 2> $OUT/poarec_bench_line.err < /dev/null
+timeout -s KILL 600 python bench.py --full --workload poa --pairs 4096 --steps 2 --warmup 1 > $OUT/poarec4096_bench_line.json 2> $OUT/poarec4096_bench_line.err < /dev/null
+timeout -s KILL 600 python bench.py --full --workload edit --steps 3 --warmup 1 > $OUT/edit_bench_line.json 2> $OUT/edit_bench_line.err < /dev/null
 find $OUT -name '*.db' -delete
 find $OUT -name '*_kernel_trace.csv' -delete
 find $OUT -name '*agent_info.csv' -delete

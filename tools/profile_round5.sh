@@ -25,7 +25,7 @@ for name in $NAMES; do
 		timeout -s KILL 900 rocprofv3 --pmc $ctr --output-format csv -d $OUT -o ${name}_pmc_${ctr} -- python bench.py $args --steps 1 --warmup 0 --cpu-pairs -1 > $OUT/${name}_pmc_${ctr}.log 2>&1 < /dev/null
 	done
 	timeout -s KILL 900 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d $OUT -o ${name}_pmc_SQ -- python bench.py $args --steps 1 --warmup 0 --cpu-pairs -1 > $OUT/${name}_pmc_SQ.log 2>&1 < /dev/null
-	timeout -s KILL 900 python bench.py $args --steps 5 --warmup 2 > $OUT/${name}_bench_line.json 2> $OUT/${name}_bench_line.err < /dev/null
+	timeout -s KILL 900 python bench.py --full $args --steps 5 --warmup 2 > $OUT/${name}_bench_line.json 2> $OUT/${name}_bench_line.err < /dev/null
 done
 find $OUT -name '*.db' -delete
 find $OUT -name '*_kernel_trace.csv' -delete
