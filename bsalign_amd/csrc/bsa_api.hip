@@ -1534,6 +1534,12 @@ extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *c, int slot, size_t bytes, vo
 	return BSA_OK;
 }
 
+// the POA graph launchers (bsa_poa_wf.hip, bsa_poa_gen.hip) report the instantiation they launched, for bsa_ctx_last_kernel_name
+extern "C" void bsa_ctx_set_kernel_names_internal(bsa_ctx_t *c, const char *fwd, const char *trace){
+	if(!c) return;
+	c->fwd_name = fwd ? fwd : ""; c->trace_name = trace ? trace : "";
+}
+
 extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *c, hipStream_t *st){
 	if(!c || !st) return BSA_E_ARG;
 	(void)hipSetDevice(c->device);

@@ -25,11 +25,13 @@
 #include <vector>
 #include <cstring>
 #include <cstdlib>
+#include <string>
 
 extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
 extern "C" int bsa_ctx_time_begin_internal(bsa_ctx_t *ctx, double cells, void **stop_event);
 extern "C" int bsa_ctx_time_end_internal(bsa_ctx_t *ctx, void *stop_event);
 extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
+extern "C" void bsa_ctx_set_kernel_names_internal(bsa_ctx_t *ctx, const char *fwd, const char *trace);
 
 #define GEN_NT 1024
 #define GEN_NEG (2 * BSA_SCORE_MIN)
@@ -450,6 +452,12 @@ extern "C" int bsa_poa_graph_gen_supported(const bsa_sweep_params_t *par){
 	}
 	if(m + 3 * g > 64 || n + m + g > 100 || m + 2 * n > 128) return 0;      // (m + 2 n: the head row's seed (min - max) + S stays a byte on a mismatch, bsalign.h:2899-2910)
 	if(std::min((int)rp->X, -g) - 1 - m - g < -100) return 0;
+	// the seed of band cell 0 over the head's row (bsalign.h:2899-2910) is kept down to t = us[0] + e = -(go + ge + m + n) + (-63, or gape1 without an
+	// open cost) and then goes into a byte lane (mm_insert_epi8): rh = the cost of toff leading nodes brings it anywhere above t, so t must be a byte
+	if(go + ge + m + n + (pw == 0 ? ge : 63) > 128) return 0;
+	// ... and the vertical difference of that cell, h0 - us[0] with the head's us[0] = -(go + ge + m + n) and h0 up to m, saturates: the lane-exact rows
+	// differ from the absolute ones from 127 on (tests/test_poa_random_cpu.py), not below
+	if(2 * m + n + go + ge > 126) return 0;
 	return 1;
 }
 
@@ -492,7 +500,8 @@ int bsa_poa_graph_gen_run(bsa_ctx_t *ctx, const bsa_poa_node_t *d_nodes, size_t 
 	rc = bsa_ctx_time_begin_internal(ctx, 0.0, &stop);
 	if(rc != BSA_OK) return rc;
 	auto fail = [&](int code){ (void)bsa_ctx_time_end_internal(ctx, stop); return code; };
-	size_t k0 = 0;
+	size_t k0 = 0, launches = 0;
+	const char *kname = "";
 	while(k0 < nprogs){
 		// as many programs side by side as the row budget holds (at least one)
 		size_t k1 = k0, rowsn = 0;
@@ -510,15 +519,20 @@ int bsa_poa_graph_gen_run(bsa_ctx_t *ctx, const bsa_poa_node_t *d_nodes, size_t 
 		a.rows = (int2*)((uint8_t*)ws + o_rows); a.u0 = (int32_t*)((uint8_t*)ws + o_u0); a.rowbase = (const uint64_t*)((uint8_t*)ws + o_base);
 		a.first_prog = (uint32_t)k0;
 		const dim3 grid((uint32_t)(k1 - k0)), block(GEN_NT);
-#define GEN_LAUNCH(PWV, CV) hipLaunchKernelGGL((k_poa_gen<PWV, CV>), grid, block, 0, st, a)
+#define GEN_LAUNCH(PWV, CV) do { hipLaunchKernelGGL((k_poa_gen<PWV, CV>), grid, block, 0, st, a); kname = "k_poa_gen<" #PWV ", " #CV ">"; } while(0)
 #define GEN_LAUNCH_C(PWV) do { switch(C){ case 1: GEN_LAUNCH(PWV, 1); break; case 2: GEN_LAUNCH(PWV, 2); break; case 4: GEN_LAUNCH(PWV, 4); break; case 8: GEN_LAUNCH(PWV, 8); break; \
 			case 16: GEN_LAUNCH(PWV, 16); break; default: GEN_LAUNCH(PWV, 32); break; } } while(0)
 		if(pw == 0) GEN_LAUNCH_C(0); else if(pw == 1) GEN_LAUNCH_C(1); else GEN_LAUNCH_C(2);
 #undef GEN_LAUNCH_C
 #undef GEN_LAUNCH
 		if(hipGetLastError() != hipSuccess) return fail(BSA_E_HIP);
-		k0 = k1;
+		k0 = k1; launches++;
 		if(k0 < nprogs && hipStreamSynchronize(st) != hipSuccess) return fail(BSA_E_HIP);          // (the next group reuses the rows)
+	}
+	{
+		// (the instantiation and into how many row-budget groups the call was split, for bsa_ctx_last_kernel_name)
+		const std::string nm = std::string(kname) + " x " + std::to_string(launches);
+		bsa_ctx_set_kernel_names_internal(ctx, nm.c_str(), nm.c_str());
 	}
 	return bsa_ctx_time_end_internal(ctx, stop);
 }

@@ -689,7 +689,7 @@ __global__ void __launch_bounds__(64) k_poa_wf(const PoaArgs a){
 	rs.reserved = (int)(wall_clock64() - tick0);        // forward pass + best end cell, in ticks of the 100 MHz counter
 	if(a.mode & 0x100) rs.reserved = (ROWS != 0) ? fwd_ticks : iters;
 	rs.nevents = 0; rs.fin_node = -1; rs.fin_x = -1; rs.status = BSA_POA_ST_OK;
-	if(bkey == (long long)0x8000000000000000ull){
+	if(bkey == (long long)0x8000000000000000ull || (int)(bkey >> 32) <= BSA_SCORE_MIN){          // (the reference starts at SCORE_MIN and takes a candidate only when strictly greater: dead rows alone are no candidate)
 		rs.maxscr = BSA_SCORE_MIN; rs.maxidx = -1; rs.maxoff = -1; rs.status = BSA_POA_ST_NOCAND;
 		if(lane == 0) a.res[blockIdx.x] = rs;
 		return;
@@ -1270,6 +1270,7 @@ extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
 extern "C" int bsa_ctx_time_begin_internal(bsa_ctx_t *ctx, double cells, void **stop_event);
 extern "C" int bsa_ctx_time_end_internal(bsa_ctx_t *ctx, void *stop_event);
 extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
+extern "C" void bsa_ctx_set_kernel_names_internal(bsa_ctx_t *ctx, const char *fwd, const char *trace);
 // bands wider than 256 columns (bsa_poa_gen.hip)
 extern "C" int bsa_poa_graph_gen_supported(const bsa_sweep_params_t *par);
 int bsa_poa_graph_gen_run(bsa_ctx_t *ctx, const bsa_poa_node_t *d_nodes, size_t nnodes, const bsa_poa_edge_t *d_edges, const bsa_poa_cand_t *d_cands,
@@ -1320,6 +1321,12 @@ extern "C" int bsa_poa_graph_supported(const bsa_sweep_params_t *par, uint32_t m
 	}
 	if(m + 3 * g > 64 || n + m + g > 100 || m + 2 * n > 128) return 0;      // (m + 2 n: the head row's seed (min - max) + S stays a byte on a mismatch, bsalign.h:2899-2910)
 	if(std::min((int)rp->X, -g) - 1 - m - g < -100) return 0;
+	// the seed of band cell 0 over the head's row (bsalign.h:2899-2910) is kept down to t = us[0] + e = -(go + ge + m + n) + (-63, or gape1 without an
+	// open cost) and then goes into a byte lane (mm_insert_epi8): rh = the cost of toff leading nodes brings it anywhere above t, so t must be a byte
+	if(go + ge + m + n + (pw == 0 ? ge : 63) > 128) return 0;
+	// ... and the vertical difference of that cell, h0 - us[0] with the head's us[0] = -(go + ge + m + n) and h0 up to m, saturates: the lane-exact rows
+	// differ from the absolute ones from 127 on (tests/test_poa_random_cpu.py), not below
+	if(2 * m + n + go + ge > 126) return 0;
 	if((int)(bw / 16) * ge > 60) return 0;
 	for(uint32_t nl = 64; nl >= 8; nl >>= 1)
 		if(poa_front_bytes(bw, nl) + poa_qn_bytes(bw, max_slen) + POA_NQ * sizeof(bsa_poa_node_t) <= POA_LDS_MAX) return (int)nl;
@@ -1394,7 +1401,8 @@ extern "C" int bsa_poa_graph_run(bsa_ctx_t *ctx, const bsa_poa_node_t *d_nodes, 
 		if(lds > lds_set){                                                                                                                \
 			if(hipFuncSetAttribute((const void*)k_poa_wf<PWV, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess){ (void)bsa_ctx_time_end_internal(ctx, stop); return BSA_E_HIP; } \
 			lds_set = lds; }                                                                                                              \
-		hipLaunchKernelGGL((k_poa_wf<PWV, RV>), dim3((uint32_t)nprogs), dim3(64), lds, st, a); } while(0)
+		hipLaunchKernelGGL((k_poa_wf<PWV, RV>), dim3((uint32_t)nprogs), dim3(64), lds, st, a);                                            \
+		bsa_ctx_set_kernel_names_internal(ctx, "k_poa_wf<" #PWV ", " #RV ">", "k_poa_wf<" #PWV ", " #RV ">"); } while(0)
 #define POA_LAUNCH_R(RV) do { if(pw == 0) POA_LAUNCH(0, RV); else if(pw == 1) POA_LAUNCH(1, RV); else POA_LAUNCH(2, RV); } while(0)
 	if(!rows_fwd) POA_LAUNCH_R(0);
 	else if(bw <= 64) POA_LAUNCH_R(1);

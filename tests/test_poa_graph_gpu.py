@@ -145,7 +145,10 @@ def _attach(lib, ctx):
 
 
 @pytest.mark.skipif(not P.have_ref_trace(), reason="oracle/_ref/libbsref_trace.so not built")
-@pytest.mark.parametrize("kw", [dict(), dict(alnmode=0, bandwidth=64), dict(alnmode=2, Q=0, P=0), dict(deep=48)])
+# (the last three: non-default scorings inside the score guard -- small scores with refbonus 0; m + 3 g = 64, two-piece; the head-seed term
+# go + ge + m + n + 63 = 128 met with equality -- so that the real end_bspoa pins the guard's boundary as well)
+@pytest.mark.parametrize("kw", [dict(), dict(alnmode=0, bandwidth=64), dict(alnmode=2, Q=0, P=0), dict(deep=48),
+                                dict(M=1, X=-4, O=-2, E=-1, Q=-6, P=-1, refbonus=0), dict(alnmode=0, Q=-19), dict(alnmode=2, X=-56)])
 def test_device_in_the_shadow_of_the_reference(ctx, kw):
     """harness mode 5 with the MI355X as backend: inside a real end_bspoa, read after read, the device's best end cell and every
     step of its walk against what the reference's own align_rd_bspoacore + alignment2graph_bspoa do on the same graph.  `deep`: a

@@ -26,7 +26,10 @@ def _attach(lib, ctx):
     lib.ref_poa_set_device(C.cast(b.bsa_sweep_host, C.c_void_p), ctx.h)
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(alnmode=0, bandwidth=64), dict(alnmode=2, Q=0, P=0), dict(nrec=3, bandwidth=256), dict(deep=40)])
+# (the last three: non-default scorings inside the score guard -- small scores with refbonus 0; m + 3 g = 64, two-piece; the head-seed term
+# go + ge + m + n + 63 = 128 met with equality)
+@pytest.mark.parametrize("kw", [dict(), dict(alnmode=0, bandwidth=64), dict(alnmode=2, Q=0, P=0), dict(nrec=3, bandwidth=256), dict(deep=40),
+                                dict(M=1, X=-4, O=-2, E=-1, Q=-6, P=-1, refbonus=0), dict(alnmode=0, Q=-19), dict(alnmode=2, X=-56)])
 def test_every_step_in_the_shadow_of_the_reference_with_the_device_between(ctx, kw):
     lib = P.ref_poa()
     _attach(lib, ctx)
