@@ -284,25 +284,29 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	constexpr bool OWNSTG = !EXT && !SCORE;
 	__shared__ uint32_t x_stage[OWNSTG ? NWV : 1][OWNSTG ? 4 * ND : 1][64];       // [wave][4 q + row of the group (CWD == 1) | ND row + dword (CWD >= 2)][lane]
 	uint32_t *const stg = EXT ? ext_stage + (size_t)(lt >> 6) * (4 * ND * 64) + (lt & 63) : &x_stage[(OWNSTG && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
-	// QUERY WINDOW (round 5).  A lane needs the W query codes of each of its two blocks on every row, at a band offset that moves by about one base a
+	// QUERY WINDOW.  A lane needs S~ of the W cells of each of its two blocks on every row, at a band offset that moves by about one base a
 	// row: loaded from memory row by row that is one full round trip the wave waits for per row -- and `vmcnt` also holds the row's wait back behind the
 	// code-row stores in flight (a second such round trip per row, added as an experiment, cost 5.4 ms of the 61: 9 %).  Instead the lane keeps, in LDS
-	// slots of its own (no synchronisation, like the staging above), KD dwords per block starting at the band offset of the last refill: a row reads
-	// NQ + 1 of them at the dword its offset has reached and shifts them into place (v_alignbyte), and only every 4 KD - W - 3 bases of band movement
-	// (about 45 rows) the window is loaded again.  The staged query is padded far enough behind its end (plan: bandwidth + 32 bytes).
+	// slots of its own (no synchronisation, like the staging above), one dword per band column of its block pair, starting at the band offset of the last
+	// refill: the byte-permute SELECTOR {0x0C, code of the low block's column, 0x0C, code of the high block's column}.  v_perm_b32(PADS, mr, selector) is then
+	// the cell register's S~ {0, S~ low, 0, S~ high} in one instruction (0x0C selects a zero byte, code 4 the PADS byte): a row reads the W selectors at
+	// the dword its offset has reached -- no shifting into place, no lookup of packed codes, no spreading of the looked-up bytes.  The selectors depend on
+	// the query alone; they are built when the window is loaded, every 2 KD - W columns of band movement (about 15 rows), for all the live pairs of the wave at
+	// once (below).  The staged query is padded far enough behind its end (plan: bandwidth + BSA_QPAD_TAIL bytes).
 #ifdef XQ_NO_QWIN
 	constexpr bool QWIN = false;
 #else
 	constexpr bool QWIN = !STATIC && PW != 2 && W == 16;      // (measured: two-piece gaps at 251 registers lose 3 % with it, eight cells a half gain nothing)
 #endif
-	// band offsets leave sixteen rows at a time through four LDS dwords a lane (below, "band offsets"); the window gives them up -- 40 instead of 48 bytes of
+	// band offsets leave sixteen rows at a time through four LDS dwords a lane (below, "band offsets"); the window gives them up -- 12 instead of 16 columns of
 	// band movement between refills -- so that the block's LDS stays what three waves per SIMD allow (one KB more a wave cost 5 % of the launch)
 	constexpr bool BQ16 = XQ_BEGS16 && L == 4 && !EXT;
 	__shared__ uint32_t x_bq[BQ16 ? NWV : 1][BQ16 ? 4 : 1][64];
 	uint32_t *const bqp = &x_bq[(BQ16 && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
-	constexpr int KD = NQ + ((BQ16 && QWIN) ? 10 : 12);   // dwords per block in the window
-	constexpr uint32_t QOFFMAX = 4u * (uint32_t)(KD - NQ - 1) + 3u;      // the last offset at which dwords k .. k + NQ are all inside
-	static_assert(!QWIN || 4 * KD - W <= BSA_QPAD_TAIL, "the window reads 4 KD - W bytes behind the band's last block: the staged query's padding (bsa_api.hip: qpad = bandwidth + BSA_QPAD_TAIL) must cover it");
+	constexpr int KD = NQ + ((BQ16 && QWIN) ? 10 : 12);   // the window is 2 KD dwords a lane
+	constexpr int NSEL = 2 * KD;                          // selectors (band columns) in the window
+	constexpr uint32_t QOFFMAX = (uint32_t)(NSEL - W);    // the last offset at which selectors off .. off + W - 1 are all inside
+	static_assert(!QWIN || (NSEL % 4 == 0 && NSEL - W <= BSA_QPAD_TAIL), "a refill reads NSEL - W bytes behind the band's last block: the staged query's padding (bsa_api.hip: qpad = bandwidth + BSA_QPAD_TAIL) must cover it");
 	__shared__ uint32_t x_qwin[(QWIN && !EXT) ? NWV : 1][(QWIN && !EXT) ? 2 * KD : 1][64];
 	uint32_t *const qwp = EXT ? ext_qwin + (size_t)(lt >> 6) * (2 * KD * 64) + (lt & 63) : &x_qwin[(QWIN && !EXT && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
 	uint32_t wbase = 0x40000000u;                          // band offset the window starts at (this value: no window yet)
@@ -339,21 +343,16 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 			mov = min(mov, __builtin_elementwise_sub_sat(qlen, rbeg + (uint32_t)BW));
 			rbeg += mov;
 		}
-		int rh;
-		if(rbeg) rh = BSA_SCORE_MIN;
-		else if(mode == BSA_MODE_OVERLAP || i == 0) rh = 0;
-		else if(PW < 2) rh = gapo1 + gape1 * (int)i;
-		else rh = max(gapo1 + gape1 * (int)i, gapo2 + gape2 * (int)i);
+		int rhj = 0;          // a band that jumps past everything it held: H at the last cell of the previous row (set in that branch, read for the first cell below)
 		// ---- row_movx (bsalign.h:2244-2392): the row is held slid by one cell; correct what did not move that way
 		if(!STATIC && __builtin_expect((__builtin_amdgcn_ballot_w64(mov != 1u) & actm) != 0ull, 0)){
 			if(__any(act && mov >= (uint32_t)BW)){
 				// the band jumped past everything it held: zero rows, every ubegs = SCORE_MIN (bsalign.h:2253-2259);
-				// rh = H at the last cell of the previous row (getscore(bw - 1))
 				const bool z = act && mov >= (uint32_t)BW;
 				const uint32_t bc = x_bcast_last<L>(PN);
 				const int rhz = HB + (x_hi16(bc) - cfirst) + BW * GE;
 				if(z){
-					rh = rhz;
+					rhj = rhz;
 #pragma unroll
 					for(int k = 0; k < W; k++){ U[k] = NGEQ; NE[k] = NEWNE; if constexpr (PW == 2) NQ2[k] = NEWNE; }
 					HB = BSA_SCORE_MIN;
@@ -403,7 +402,6 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 				}
 			}
 		}
-		if(!STATIC && mov != 0u && mov < (uint32_t)BW) rh = HB;   // getscore(mov - 1) of the previous row
 		// ---- sequences, S~(x, y)
 		uint32_t S[W];
 		{
@@ -411,33 +409,42 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 			// (the window holds the bases times four: a base is 0 .. 3, so nothing crosses a byte)
 			const uint32_t tw32 = (i & 4u) ? (uint32_t)(twin >> 32) : (uint32_t)twin;
 			const uint32_t tb4 = __builtin_amdgcn_ubfe(tw32, 8u * (i & 3u), 4u);
+			if constexpr (QWIN){
+				uint32_t off = rbeg - wbase;
+				if(__builtin_expect((__builtin_amdgcn_ballot_w64(off > QOFFMAX) & actm) != 0ull, 0)){
+					// refill: the selectors of the NSEL columns from the band offset of this row on, for EVERY live pair of the wave, not only the one that has
+					// run out: the sixteen pairs move at about the same rate, so their windows stay in step and this branch runs once in about 13 rows (refilled
+					// each on its own, three in four rows would find some pair at its window's end and run the branch for one active pair)
+					if(act){
+						const uint8_t *pl = qp + rbeg + jl * W, *ph = qp + rbeg + (jl + L) * W;
+						uint32_t bl[NSEL / 4], bh[NSEL / 4];
+						__builtin_memcpy(bl, pl, NSEL); __builtin_memcpy(bh, ph, NSEL);
+						// (the two selectors below have to be in vector registers -- the 0x0C dword takes the instruction's one scalar operand: made here, opaque,
+						// so that they are not kept as invariants across the row loop, which has no register to spare)
+						uint32_t PA = 0x02040004u, PB = 0x03040104u;
+						asm volatile("" : "+v"(PA), "+v"(PB));
+#pragma unroll
+						for(int n = 0; n < NSEL / 4; n++){
+							// {lo0, lo1, hi0, hi1} and {lo2, lo3, hi2, hi3} of the four columns, then each column's two codes between the 0x0C bytes
+							const uint32_t y0 = __builtin_amdgcn_perm(bh[n], bl[n], 0x05040100u), y1 = __builtin_amdgcn_perm(bh[n], bl[n], 0x07060302u);
+							qwp[64 * (4 * n)] = __builtin_amdgcn_perm(0x0C0C0C0Cu, y0, PA);
+							qwp[64 * (4 * n + 1)] = __builtin_amdgcn_perm(0x0C0C0C0Cu, y0, PB);
+							qwp[64 * (4 * n + 2)] = __builtin_amdgcn_perm(0x0C0C0C0Cu, y1, PA);
+							qwp[64 * (4 * n + 3)] = __builtin_amdgcn_perm(0x0C0C0C0Cu, y1, PB);
+						}
+						wbase = rbeg; off = 0u;
+					}
+				}
+				// (a lane whose pair has no row left computes on whatever its window holds: nothing of it is stored)
+				const uint32_t *wl = qwp + 64u * (act ? off : 0u);
+				const uint32_t mr = *(const uint32_t*)((const uint8_t*)x_mtab + tb4);
+#pragma unroll
+				for(int k = 0; k < W; k++) S[k] = __builtin_amdgcn_perm(PADS, mr, wl[64 * k]);
+			} else {
 			uint32_t qlo[NQ], qhi[NQ];
 			if constexpr (STATIC){
 #pragma unroll
 				for(int n = 0; n < NQ; n++){ qlo[n] = act ? sqlo[n] : 0x04040404u; qhi[n] = act ? sqhi[n] : 0x04040404u; }
-			} else if constexpr (QWIN){
-				uint32_t off = rbeg - wbase;
-				if(__builtin_expect((__builtin_amdgcn_ballot_w64(off > QOFFMAX) & actm) != 0ull, 0)){
-					// refill: KD dwords of each block from the band offset of this row
-					if(act && off > QOFFMAX){
-						const uint8_t *pl = qp + rbeg + jl * W, *ph = qp + rbeg + (jl + L) * W;
-						uint32_t bl[KD], bh[KD];
-						__builtin_memcpy(bl, pl, 4 * KD); __builtin_memcpy(bh, ph, 4 * KD);
-#pragma unroll
-						for(int m = 0; m < KD; m++){ qwp[64 * m] = bl[m]; qwp[64 * (KD + m)] = bh[m]; }
-						wbase = rbeg; off = 0u;
-					}
-				}
-				const uint32_t kq = act ? (off >> 2) : 0u;
-				const uint32_t *wl = qwp + 64u * kq;
-				uint32_t dl[NQ + 1], dh[NQ + 1];
-#pragma unroll
-				for(int n = 0; n <= NQ; n++){ dl[n] = wl[64 * n]; dh[n] = wl[64 * (KD + n)]; }
-#pragma unroll
-				for(int n = 0; n < NQ; n++){
-					const uint32_t vl = __builtin_amdgcn_alignbyte(dl[n + 1], dl[n], off), vh = __builtin_amdgcn_alignbyte(dh[n + 1], dh[n], off);
-					qlo[n] = vl; qhi[n] = vh;          // (a lane whose pair has no row left computes on whatever its window holds: nothing of it is stored)
-				}
 			} else if(act){ x_load_qcodes<W>(qp + rbeg + jl * W, qlo); x_load_qcodes<W>(qp + rbeg + (jl + L) * W, qhi); }
 			else {
 #pragma unroll
@@ -453,6 +460,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 				const uint32_t sel = 0x000C000Cu | ((uint32_t)(k & 3) << 8) | ((uint32_t)(4 + (k & 3)) << 24);   // {0, lo.byte[k], 0, hi.byte[k]}
 				S[k] = __builtin_amdgcn_perm(shi[k >> 2], slo[k >> 2], sel);
 			}
+			}
 		}
 		// ---- first cell of the band (bsalign.h:2899-2907): h0 = rh - ubegs[0] + S, kept if >= u + e, else -63.  After a
 		// slide inside the band rh == ubegs[0] and the rule changes neither h nor any flag, so only rows that stayed
@@ -460,6 +468,14 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 		uint32_t hc0 = S[0];
 		uint32_t q0m = 0, q0d = 0, q0d2 = 0;          // rows starting at query column 0: what h is compared with for M and D (bsalign.h:3763-3767)
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u) & actm) != 0ull, 0)){          // mov == 0 or mov >= BW
+			// rh = H of the previous row left of the band's first cell: of its last cell after a jump, the row's own start value where the band has not moved
+			// (a slide inside the band -- getscore(mov - 1) = ubegs[0] -- needs none: nothing below is used for such a pair)
+			int rh;
+			if(!STATIC && mov >= (uint32_t)BW) rh = rhj;
+			else if(rbeg) rh = BSA_SCORE_MIN;
+			else if(mode == BSA_MODE_OVERLAP || i == 0) rh = 0;
+			else if(PW < 2) rh = gapo1 + gape1 * (int)i;
+			else rh = max(gapo1 + gape1 * (int)i, gapo2 + gape2 * (int)i);
 			const int s0 = x_lo8(S[0]) + 2 * GE, u0 = x_lo8(U[0]) + GE, e0 = GE - x_lo8(NE[0]);
 			const int qq0 = (PW == 2) ? GE - x_lo8(NQ2[0]) : e0;
 			const int t0 = u0 + max(e0, qq0);
