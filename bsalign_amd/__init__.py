@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("BSA_LIB_PATH") or os.path.join(_HERE, "libbsalign_hip
 
 MODE_GLOBAL, MODE_OVERLAP, MODE_EXTEND = 0, 1, 2
 MODE_ROWRECORDS, MODE_SCORE_ONLY, MODE_SEQ2BIT = 0x100, 0x400, 0x800       # flags OR-ed into the mode (include/bsalign_hip.h)
+MODE_CIGAR_EQX = 0x1000                                                   # ... M words leave as runs of = and X
+CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
@@ -257,6 +259,54 @@ def pack_pairs(pairs, seq2bit=False):
     return seqs, qoff, qlen, toff, tlen
 
 
+def expand_eqx(words, q, t, qb=0, tb=0):
+    """the BSA_MODE_CIGAR_EQX form of a plain CIGAR (include/bsalign_hip.h): every M word replaced, in place, by the maximal runs of
+    CIGAR_EQ and CIGAR_X over its columns -- column j of an M word that starts at query position qp and target position tp is = when
+    q[qp + j] == t[tp + j].  Positions start at the record's qb, tb; M / = / X consume a base of both, I a query base, D a target base.
+    Pure numpy; words: uint32 (len << 4 | op)."""
+    q = np.asarray(q, dtype=np.uint8)
+    t = np.asarray(t, dtype=np.uint8)
+    out = []
+    qp, tp = int(qb), int(tb)
+    for w in np.asarray(words, dtype=np.uint32).tolist():
+        op, ln = w & 15, w >> 4
+        if op == CIGAR_M and ln:
+            mis = q[qp:qp + ln] != t[tp:tp + ln]
+            if len(mis) != ln:
+                raise ValueError("expand_eqx: an M word runs past the end of a sequence")
+            cut = np.flatnonzero(mis[1:] != mis[:-1]) + 1
+            edges = np.concatenate([[0], cut, [ln]])
+            for a, b in zip(edges[:-1].tolist(), edges[1:].tolist()):
+                out.append(((b - a) << 4) | (CIGAR_X if mis[a] else CIGAR_EQ))
+        else:
+            out.append(w)
+        if op in (CIGAR_M, CIGAR_EQ, CIGAR_X):
+            qp += ln
+            tp += ln
+        elif op == CIGAR_I:
+            qp += ln
+        elif op == CIGAR_D:
+            tp += ln
+    return np.array(out, dtype=np.uint32)
+
+
+def collapse_eqx(words):
+    """every run of neighbouring = / X words merged back into one M word: the plain CIGAR of the same alignment"""
+    out = []
+    run = 0
+    for w in np.asarray(words, dtype=np.uint32).tolist():
+        if (w & 15) in (CIGAR_EQ, CIGAR_X):
+            run += w >> 4
+            continue
+        if run:
+            out.append((run << 4) | CIGAR_M)
+            run = 0
+        out.append(w)
+    if run:
+        out.append((run << 4) | CIGAR_M)
+    return np.array(out, dtype=np.uint32)
+
+
 DIAGDP_WALK_DTYPE = np.dtype([("nsteps", "<u4"), ("score", "<i4"), ("xi", "<i4"), ("yi", "<i4"), ("status", "<u4"), ("reserved", "<u4"), ("first_word", "<u8")])
 
 
@@ -325,12 +375,13 @@ class Context:
         cigs = [cig[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
         return out, cigs, status[:n]
 
-    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False):
+    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False, eqx=False):
         """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status); seq2bit: the sequences go down
-        2-bit packed (pack_pairs(..., seq2bit=True), BSA_MODE_SEQ2BIT OR-ed into par.mode)"""
-        if seq2bit:
+        2-bit packed (pack_pairs(..., seq2bit=True), BSA_MODE_SEQ2BIT OR-ed into par.mode); eqx: BSA_MODE_CIGAR_EQX OR-ed in,
+        the CIGARs come back with = / X words (the default cigar_cap holds them: a word covers at least one column)"""
+        if seq2bit or eqx:
             par = AlignParams.from_buffer_copy(par)
-            par.mode |= MODE_SEQ2BIT
+            par.mode |= (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0)
         return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit)
 
     def align_scores(self, pairs, par, seq2bit=False):
@@ -417,9 +468,10 @@ class Context:
     def diagdp_last_ms(self):
         return float(lib().bsa_diagdp_last_ms(self.h))
 
-    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None, seq2bit=False):
+    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None, seq2bit=False, eqx=False):
+        """host-pointer form of bsa_edit_batch; seq2bit / eqx as in align_batch"""
         p = EditParams()
-        p.mode, p.bandwidth = mode | (MODE_SEQ2BIT if seq2bit else 0), bandwidth
+        p.mode, p.bandwidth = mode | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0), bandwidth
         return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap, seq2bit)
 
     def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0, seq2bit=False):
@@ -466,7 +518,8 @@ def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):
 class AlignPlan:
     """two-phase form (bsa_align_plan_create / bsa_align_run): host metadata once, device-resident data per run.
     Device buffers are torch tensors (plumbing only); the run is asynchronous on the context's stream.  With MODE_SEQ2BIT in
-    par.mode, d_seqs holds 2-bit packed words (pack2bit) and the offsets are base offsets."""
+    par.mode, d_seqs holds 2-bit packed words (pack2bit) and the offsets are base offsets; with MODE_CIGAR_EQX the CIGAR words
+    are = / X runs and d_cigar must hold the expanded words."""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, par):
         self.ctx = ctx
@@ -510,7 +563,7 @@ class AlignPlan:
 
 class EditPlan:
     """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device); mode may carry MODE_SCORE_ONLY, then run with d_cigar=None,
-    and MODE_SEQ2BIT (d_seqs 2-bit packed words, base offsets)"""
+    MODE_SEQ2BIT (d_seqs 2-bit packed words, base offsets) and MODE_CIGAR_EQX (= / X words)"""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, mode=MODE_GLOBAL, bandwidth=0):
         self.ctx = ctx

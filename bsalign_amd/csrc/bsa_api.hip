@@ -518,6 +518,9 @@ struct PlanBase {
 	uint32_t *d_cnt_pos = nullptr, *d_cnt_pair = nullptr, *d_status_own = nullptr;
 	uint64_t *d_off_pos = nullptr, *d_src_pair = nullptr, *d_carry = nullptr, *d_scan_tmp = nullptr;
 	uint32_t *d_tmp = nullptr; size_t tmp_words = 0;
+	bool eqx = false;               // BSA_MODE_CIGAR_EQX: M words leave as = / X runs (bsa_cigar_eqx.hip; run_pipeline)
+	uint32_t *d_cnt_plain = nullptr;        // ... the plain word counts by position, beside the expanded ones in d_cnt_pos
+	const bsa_result_t *eqx_out = nullptr;  // ... the records of the run in progress (qb / tb seed the walk)
 	void *pool = nullptr;           // one allocation behind all the metadata pointers above (plan_common_alloc)
 	bool pool_kept = false;         // ... which is the context's kept buffer (ctx_buf_get)
 	std::vector<void*> extra;       // path-specific device allocations
@@ -662,7 +665,7 @@ static int plan_common_alloc(PlanBase *p, const uint64_t *qoff, const uint32_t *
 		{(void**)&p->d_qst, nullptr, std::max<size_t>(qst_bytes, 1), 0}, {(void**)&p->d_tst, nullptr, std::max<size_t>(tst_bytes, 1), 0},
 		{(void**)&p->d_cnt_pos, nullptr, m * 4, 0}, {(void**)&p->d_cnt_pair, nullptr, m * 4, 0}, {(void**)&p->d_status_own, nullptr, m * 4, 0},
 		{(void**)&p->d_off_pos, nullptr, (m + 1) * 8, 0}, {(void**)&p->d_src_pair, nullptr, m * 8, 0}, {(void**)&p->d_carry, nullptr, 8, 0},
-		{(void**)&p->d_scan_tmp, nullptr, (m / SCAN_TILE + 2) * 8, 0},
+		{(void**)&p->d_scan_tmp, nullptr, (m / SCAN_TILE + 2) * 8, 0}, {(void**)&p->d_cnt_plain, nullptr, p->eqx ? m * 4 : 0, 0},
 	};
 	size_t total = 0, upload = 0;
 	for(Part &q : parts){ q.off = total; total += (std::max<size_t>(q.bytes, 8) + 255) & ~(size_t)255; if(q.src) upload = total; }
@@ -687,6 +690,10 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 	int rc;
 	c->sev_used = 0;
 	const bool direct = want_cig && p->chunks.size() == 1 && !p->two_halves && !bsa_env("BSA_CIGAR_VIA_ARENA");      // (see k_cigar_final_direct)
+	// BSA_MODE_CIGAR_EQX: after a chunk's traceback the expanded word counts take the place of the plain ones, so the scans, the arena guard and
+	// cigar_off count expanded words; the two kernels that read the slot tails expand on the way (k_cigar_final copies expanded words as they are)
+	const bool eqx = want_cig && p->eqx;
+	const EqxSeqs es = { p->d_qst, p->d_tst, p->d_qpoff, p->d_tpoff, p->d_qlen, p->d_tlen, p->d_order, p->eqx_out };
 	HIPCHK(c, hipMemsetAsync(p->d_carry, 0, sizeof(uint64_t), sf));
 	std::vector<hipEvent_t> trace_done(p->chunks.size());
 	if(p->two_halves){
@@ -709,9 +716,11 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 		HIPCHK(c, hipEventRecord(t0, stt));
 		rc = trace(ch, half, stt); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(t1, stt));
+		if(eqx) HIPCHK(c, bsa_launch_cigar_eqx_count(half, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_cnt_plain, es, stt));
 		if(want_cig && !direct){
 			HIPCHK(c, launch_excl_scan(stt, p->d_cnt_pos + ch.first, p->d_off_pos + ch.first, ch.count, p->d_carry, p->d_scan_tmp));
-			hipLaunchKernelGGL(k_cigar_collect, dim3((ch.count + 3) / 4), dim3(256), 0, stt, half, p->d_slot_end,
+			if(eqx) HIPCHK(c, bsa_launch_cigar_collect_eqx(half, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_cnt_plain, p->d_off_pos, p->d_tmp, (uint64_t)cigar_cap_words, es, stt));
+			else hipLaunchKernelGGL(k_cigar_collect, dim3((ch.count + 3) / 4), dim3(256), 0, stt, half, p->d_slot_end,
 				ch.first, ch.count, p->d_cnt_pos, p->d_off_pos, p->d_tmp, (uint64_t)cigar_cap_words);
 			HIPCHK(c, hipGetLastError());
 		}
@@ -729,7 +738,8 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 		hipLaunchKernelGGL(k_cnt_by_pair, dim3((n + 255) / 256), dim3(256), 0, sf, p->d_order, p->d_cnt_pos, direct ? (const uint64_t*)nullptr : p->d_off_pos, p->d_cnt_pair, p->d_src_pair, n);
 		HIPCHK(c, hipGetLastError());
 		HIPCHK(c, launch_excl_scan(sf, p->d_cnt_pair, d_cigar_off, n, (uint64_t*)nullptr, p->d_scan_tmp));
-		if(direct) hipLaunchKernelGGL(k_cigar_final_direct, dim3((n + 3) / 4), dim3(256), 0, sf, c->ws, p->d_slot_end, p->d_cnt_pair, p->d_src_pair, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n);
+		if(direct && eqx) HIPCHK(c, bsa_launch_cigar_final_direct_eqx(c->ws, p->d_slot_end, p->d_cnt_pair, p->d_src_pair, p->d_cnt_plain, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n, es, sf));
+		else if(direct) hipLaunchKernelGGL(k_cigar_final_direct, dim3((n + 3) / 4), dim3(256), 0, sf, c->ws, p->d_slot_end, p->d_cnt_pair, p->d_src_pair, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n);
 		else hipLaunchKernelGGL(k_cigar_final, dim3((n + 3) / 4), dim3(256), 0, sf, p->d_tmp, p->d_cnt_pair, p->d_src_pair, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n);
 		HIPCHK(c, hipGetLastError());
 	} else if(d_cigar_off){
@@ -884,6 +894,11 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	if(!c || !out || !par || (n && (!qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;
 	*out = nullptr;
 	if(n > 0xFFFFFFF0ull) { c->err = "too many pairs"; return BSA_E_ARG; }
+	// BSA_MODE_CIGAR_EQX is the plan's business alone (PlanBase::eqx): the dispatch below and every kernel see the mode without it
+	const bool eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0;
+	bsa_align_params_t par_plain = *par;
+	par_plain.mode &= ~BSA_MODE_CIGAR_EQX;
+	par = &par_plain;
 	const int type = par->mode & 3;
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
 	if((par->mode & BSA_MODE_SCORE_ONLY) && (par->mode & BSA_MODE_ROWRECORDS)){ c->err = "BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS exclude each other"; return BSA_E_ARG; }
@@ -941,6 +956,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	bsa_align_plan *p = new bsa_align_plan();
 	p->ctx = c; p->n = n; p->par = *par; p->bw = bw;
 	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
+	p->eqx = eqx;
 	p->sys = sys; p->sys_chk = sys && sys_chk; p->max_qlen = max_qlen;
 	p->ref_bw = widened ? (bw_req ? bw_req : 1u) : sys ? bw_req : 0u;
 	p->static_band = bw != 0 && n > 0;
@@ -1009,6 +1025,7 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;          // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
 	if(rc != BSA_OK) return rc;
+	p->eqx_out = d_out;
 	hipStream_t st = c->stream;
 	if(n == 0){
 		if(d_cigar_off) HIPCHK(c, hipMemsetAsync(d_cigar_off, 0, sizeof(uint64_t), st));
@@ -1575,6 +1592,8 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	bsa_edit_plan *p = new bsa_edit_plan();
 	p->ctx = c; p->n = n; p->par = *par;
 	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
+	p->eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0;          // (the plan's business alone: the kernels see the mode without it)
+	p->par.mode &= ~BSA_MODE_CIGAR_EQX;
 	const auto tp0 = std::chrono::steady_clock::now();
 	std::vector<uint32_t> bwk(n), order(n), qwords(n);
 	double cells = 0;
@@ -1660,6 +1679,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;        // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
 	if(rc != BSA_OK) return rc;
+	p->eqx_out = d_out;
 	hipStream_t st = c->stream;
 	if(n == 0){
 		if(d_cigar_off) HIPCHK(c, hipMemsetAsync(d_cigar_off, 0, sizeof(uint64_t), st));

@@ -299,3 +299,12 @@ hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, cons
 hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st);
 hipError_t bsa_launch_edit_trace(const EditArgs &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
 hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st);        // BSA_MODE_SCORE_ONLY: records -> results
+// BSA_MODE_CIGAR_EQX (bsa_cigar_eqx.hip): the pass that splits M words into = / X runs on their way out of the slots.  What it needs of a plan:
+// the staged 1 B/base copies and their offsets and lengths by pair, the processing order, the result records (qb / tb seed the walk)
+struct EqxSeqs { const uint8_t *qst, *tst; const uint64_t *qpoff, *tpoff; const uint32_t *qlen, *tlen, *order; const bsa_result_t *out; };
+hipError_t bsa_launch_cigar_eqx_count(const uint8_t *rows, const uint64_t *slot_end, uint32_t first, uint32_t count, uint32_t *cnt, uint32_t *cnt_plain,
+		const EqxSeqs &s, hipStream_t st);
+hipError_t bsa_launch_cigar_collect_eqx(const uint8_t *rows, const uint64_t *slot_end, uint32_t first, uint32_t count, const uint32_t *cnt, const uint32_t *cnt_plain,
+		const uint64_t *off, uint32_t *tmp, uint64_t cap, const EqxSeqs &s, hipStream_t st);
+hipError_t bsa_launch_cigar_final_direct_eqx(const uint8_t *rows, const uint64_t *slot_end, const uint32_t *cnt_pair, const uint64_t *pos_pair, const uint32_t *cnt_plain,
+		const uint64_t *dst_off, uint32_t *dst, uint64_t cap, uint32_t n, const EqxSeqs &s, hipStream_t st);

@@ -69,11 +69,37 @@ extern "C" {
                                       1 B/base copy as without the flag.  Not taken by bsa_kmer_edit_batch, the compat single-pair layer,
                                       the bsalign-hip CLI, bsa_shard_*, the POA or the rows API.  bsa_seq_pack2bit packs device-resident
                                       1 B/base codes. */
+#define BSA_MODE_CIGAR_EQX 0x1000 /* flag: = / X CIGAR words -- for bsa_align_batch / _plan_create / _run and bsa_edit_batch / _plan_create /
+                                      _run.  The reference defines the two ops (SEQALIGN_CIGAR_E / _X, bsalign.h:68-69) and prints them, but
+                                      none of its aligners produce them: a diagonal step is always M (bsalign.h:3788).  With the flag the
+                                      CIGAR of pair k is the CIGAR of the same call without it with every M word replaced, in place and in
+                                      order, by the maximal runs of BSA_CIGAR_EQ and BSA_CIGAR_X that cover the same columns: column j of
+                                      an M word that starts at query position qp and target position tp is = when query[qp + j] ==
+                                      target[tp + j] as base codes, X otherwise.  Positions start at the record's qb, tb; M / = / X
+                                      consume one base of both sequences, I one query base, D one target base.  I and D words are
+                                      unchanged.  No word has length 0, no two neighbouring words have the same op, and merging every run
+                                      of = / X words back into one M word gives the plain call's words exactly; the = lengths of a pair sum
+                                      to its record's mat, the X lengths to its mis.  out[k] and status[k] are bit-identical to the call
+                                      without the flag.  cigar_off, cigar_cap_words and BSA_E_CIGAR_CAP count the EXPANDED words (on
+                                      BSA_E_CIGAR_CAP cigar_off[n] is the number of expanded words needed); a caller can bound them:
+                                      expanded words <= plain words + 2 * mis, and never more than qlen + tlen.  A pair that returns no
+                                      CIGAR without the flag (empty, bad base, BSA_ST_TRACE, BSA_ST_DEVICE) returns none with it.
+                                      Combines with BSA_MODE_SEQ2BIT and BSA_MODE_ROWRECORDS; with BSA_MODE_SCORE_ONLY there is no CIGAR and
+                                      the flag has no effect (not an error).  bsa_align_batch keeps it on every route it takes (two
+                                      slices, width classes of whole-query bands, pairs handed over to the literal kernels).  The split
+                                      is a pass over the words the traceback kernels leave, on the device, against the staged sequences
+                                      (bsa_cigar_eqx.hip): without the flag no kernel of it is launched and nothing else changes.
+                                      Not taken by bsa_kmer_edit_batch (its parameters have no mode, and bsa_kmer_assemble would have to
+                                      merge = runs across anchors), the compat single-pair layer (its mode bits 4 / 8 / 16 are the
+                                      reference's), the bsalign-hip CLI (its alignment strings already mark mismatches), the POA or the
+                                      rows API.  bsa_shard_gather carries CIGAR words as opaque data and needs no flag. */
 
 /* CIGAR op codes (bsalign.h:61-69) */
 #define BSA_CIGAR_M 0
 #define BSA_CIGAR_I 1
 #define BSA_CIGAR_D 2
+#define BSA_CIGAR_EQ 7      /* bsalign.h:68; only with BSA_MODE_CIGAR_EQX */
+#define BSA_CIGAR_X  8      /* bsalign.h:69; only with BSA_MODE_CIGAR_EQX */
 
 /* error codes */
 #define BSA_OK            0
