@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("BSA_LIB_PATH") or os.path.join(_HERE, "libbsalign_hip
 MODE_GLOBAL, MODE_OVERLAP, MODE_EXTEND = 0, 1, 2
 MODE_ROWRECORDS, MODE_SCORE_ONLY, MODE_SEQ2BIT = 0x100, 0x400, 0x800       # flags OR-ed into the mode (include/bsalign_hip.h)
 MODE_CIGAR_EQX = 0x1000                                                   # ... M words leave as runs of = and X
+MODE_QSTRAND = 0x2000                                                     # ... bit 63 of qoff[k] is the query's strand
+QOFF_REVCOMP = 1 << 63                                                    # in qoff[k], with MODE_QSTRAND: align the reverse complement of the stored query
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 
@@ -219,10 +221,25 @@ def unpack2bit(words, off, n):
     return ((w >> (np.uint64(62) - np.uint64(2) * (i & np.uint64(31)))) & np.uint64(3)).astype(np.uint8)
 
 
-def pack_pairs(pairs, seq2bit=False):
+def revcomp(codes):
+    """the reverse complement of base codes (A 0, C 1, G 2, T 3): out[i] = 3 - codes[len - 1 - i], what BSA_MODE_QSTRAND aligns for a
+    marked query.  Codes above 3 are not bases: they come back as (3 - c) mod 256, above 3 as well."""
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    return (np.uint8(3) - c[::-1]).astype(np.uint8)
+
+
+def pack_pairs(pairs, seq2bit=False, strands=None, lead=3):
     """[(q, t), ...] of uint8 code arrays -> (seqs blob, qoff, qlen, toff, tlen).
-    seq2bit: the blob is uint64 words (pack2bit) and the offsets are base offsets; the sequences start 3 bases into the first word and
-    have 3 bases between them, so that they start at every position in a word, as a caller's reads do (the last one ends in the last word)"""
+    seq2bit: the blob is uint64 words (pack2bit) and the offsets are base offsets; the sequences start `lead` bases into the first word
+    and have 3 bases between them, so that they start at every position in a word, as a caller's reads do (the last one ends in the last word).
+    strands (a bool per pair, BSA_MODE_QSTRAND): every query is stored once, forward, as given; where strands[k] is true QOFF_REVCOMP
+    is OR-ed into qoff[k] -- the call then aligns revcomp(q) for that pair."""
+    if strands is not None:
+        if len(strands) != len(pairs):
+            raise ValueError("pack_pairs: one strand per pair")
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, None, lead)
+        qoff = qoff | np.where(np.asarray(strands, dtype=bool), np.uint64(QOFF_REVCOMP), np.uint64(0)).astype(np.uint64)
+        return seqs, qoff, qlen, toff, tlen
     if seq2bit:
         n = len(pairs)
         qlen = np.array([len(q) for q, _ in pairs], dtype=np.uint32)
@@ -230,7 +247,7 @@ def pack_pairs(pairs, seq2bit=False):
         qoff = np.zeros(n, dtype=np.uint64)
         toff = np.zeros(n, dtype=np.uint64)
         gap = np.zeros(3, dtype=np.uint8)
-        parts, acc = [gap], 3
+        parts, acc = [np.zeros(lead, dtype=np.uint8)], lead
         for k, (q, t) in enumerate(pairs):
             qoff[k] = acc
             parts += [_np(q, np.uint8), gap]
@@ -360,8 +377,8 @@ class Context:
     def last_kernel_names(self):
         return lib().bsa_ctx_last_kernel_name(self.h, 0).decode(), lib().bsa_ctx_last_kernel_name(self.h, 1).decode()
 
-    def _batch(self, fn, pairs, par, cigar_cap=None, seq2bit=False):
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
+    def _batch(self, fn, pairs, par, cigar_cap=None, seq2bit=False, strands=None):
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, strands)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
@@ -375,21 +392,22 @@ class Context:
         cigs = [cig[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
         return out, cigs, status[:n]
 
-    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False, eqx=False):
+    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False, eqx=False, strands=None):
         """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status); seq2bit: the sequences go down
         2-bit packed (pack_pairs(..., seq2bit=True), BSA_MODE_SEQ2BIT OR-ed into par.mode); eqx: BSA_MODE_CIGAR_EQX OR-ed in,
-        the CIGARs come back with = / X words (the default cigar_cap holds them: a word covers at least one column)"""
-        if seq2bit or eqx:
+        the CIGARs come back with = / X words (the default cigar_cap holds them: a word covers at least one column); strands (a bool
+        per pair): BSA_MODE_QSTRAND OR-ed in, the queries go down as given and pair k aligns revcomp(q) where strands[k] is true"""
+        if seq2bit or eqx or strands is not None:
             par = AlignParams.from_buffer_copy(par)
-            par.mode |= (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0)
-        return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit)
+            par.mode |= (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0) | (MODE_QSTRAND if strands is not None else 0)
+        return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit, strands)
 
-    def align_scores(self, pairs, par, seq2bit=False):
+    def align_scores(self, pairs, par, seq2bit=False, strands=None):
         """bsa_align_batch with BSA_MODE_SCORE_ONLY OR-ed into par.mode and no CIGAR arena: returns (results, status); score, qe and te as
-        align_batch returns them, the fields only a traceback finds are -1"""
+        align_batch returns them, the fields only a traceback finds are -1; strands as in align_batch"""
         sp = AlignParams.from_buffer_copy(par)
-        sp.mode = par.mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0)
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
+        sp.mode = par.mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, strands)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
@@ -468,18 +486,19 @@ class Context:
     def diagdp_last_ms(self):
         return float(lib().bsa_diagdp_last_ms(self.h))
 
-    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None, seq2bit=False, eqx=False):
-        """host-pointer form of bsa_edit_batch; seq2bit / eqx as in align_batch"""
+    def edit_batch(self, pairs, mode=MODE_GLOBAL, bandwidth=0, cigar_cap=None, seq2bit=False, eqx=False, strands=None):
+        """host-pointer form of bsa_edit_batch; seq2bit / eqx / strands as in align_batch"""
         p = EditParams()
-        p.mode, p.bandwidth = mode | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0), bandwidth
-        return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap, seq2bit)
+        p.mode = mode | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0) | (MODE_QSTRAND if strands is not None else 0)
+        p.bandwidth = bandwidth
+        return self._batch(lib().bsa_edit_batch, pairs, p, cigar_cap, seq2bit, strands)
 
-    def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0, seq2bit=False):
+    def edit_scores(self, pairs, mode=MODE_GLOBAL, bandwidth=0, seq2bit=False, strands=None):
         """bsa_edit_batch with BSA_MODE_SCORE_ONLY OR-ed into the mode and no CIGAR arena: returns (results, status); score, qe and te as
-        edit_batch returns them, the fields only a traceback finds are -1"""
+        edit_batch returns them, the fields only a traceback finds are -1; strands as in align_batch"""
         p = EditParams()
-        p.mode, p.bandwidth = mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0), bandwidth
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit)
+        p.mode, p.bandwidth = mode | MODE_SCORE_ONLY | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0), bandwidth
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, strands)
         n = len(pairs)
         out = np.zeros(n, dtype=RESULT_DTYPE)
         status = np.zeros(max(n, 1), dtype=np.uint32)
@@ -519,7 +538,8 @@ class AlignPlan:
     """two-phase form (bsa_align_plan_create / bsa_align_run): host metadata once, device-resident data per run.
     Device buffers are torch tensors (plumbing only); the run is asynchronous on the context's stream.  With MODE_SEQ2BIT in
     par.mode, d_seqs holds 2-bit packed words (pack2bit) and the offsets are base offsets; with MODE_CIGAR_EQX the CIGAR words
-    are = / X runs and d_cigar must hold the expanded words."""
+    are = / X runs and d_cigar must hold the expanded words; with MODE_QSTRAND a qoff[k] with QOFF_REVCOMP OR-ed in aligns the
+    reverse complement of the stored query."""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, par):
         self.ctx = ctx
@@ -563,7 +583,7 @@ class AlignPlan:
 
 class EditPlan:
     """bsa_edit_plan_create / bsa_edit_run (striped_seqedit_pairwise on the device); mode may carry MODE_SCORE_ONLY, then run with d_cigar=None,
-    MODE_SEQ2BIT (d_seqs 2-bit packed words, base offsets) and MODE_CIGAR_EQX (= / X words)"""
+    MODE_SEQ2BIT (d_seqs 2-bit packed words, base offsets), MODE_CIGAR_EQX (= / X words) and MODE_QSTRAND (QOFF_REVCOMP in qoff[k])"""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, mode=MODE_GLOBAL, bandwidth=0):
         self.ctx = ctx

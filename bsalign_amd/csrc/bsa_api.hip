@@ -248,31 +248,40 @@ static int ctx_ws_reserve(bsa_ctx *c, size_t bytes){
 
 // stage one pair per TPP threads -- a wave for short pairs (a block per pair spent most of its time being launched), the whole block
 // for long ones: copy query codes (padded with BSA_QPAD_CODE) and target bytes, validate codes
-template<int TPP>
+// QS (plans with BSA_MODE_QSTRAND): bit 63 of qoff[k] asks for the query's reverse complement -- piece i of it is the 16 stored bytes that
+// end at qlen - i, byte-reversed and complemented, and the piece done byte by byte is the one that holds the START of the stored query
+template<int TPP, bool QS = false>
 __global__ void __launch_bounds__(256) k_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
 		uint8_t *qst, uint8_t *tst, uint32_t qpad, uint32_t tpad, uint32_t *status, uint32_t n){
 	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
 	if(k >= n) return;
 	const uint32_t ql = qlen[k], tl = tlen[k];
-	const uint8_t *q = seqs + qoff[k], *t = seqs + toff[k];
+	const uint64_t qo = qoff[k];
+	const bool qrev = QS && (qo & BSA_QOFF_REVCOMP) != 0;
+	const uint8_t *q = seqs + (QS ? qo & ~BSA_QOFF_REVCOMP : qo), *t = seqs + toff[k];
 	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
 	uint32_t bad = 0;
 	// 16 bytes per thread and trip (the staged regions are 16-byte aligned and a whole number of 16-byte pieces, the source is
 	// not aligned and ends with the sequence): whole pieces with two 8-byte loads, the piece that holds the end byte by byte
-	auto copy = [&](const uint8_t *src, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode){
+	auto copy = [&](const uint8_t *src, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode, bool rev){
 		const uint32_t total = (len + pad + 15u) & ~15u;
 		for(uint32_t i = lane * 16u; i < total; i += (uint32_t)TPP * 16u){
 			uint64_t v0, v1;
 			if(i + 16u <= len){
-				__builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8);
+				if(QS && rev){
+					__builtin_memcpy(&v1, src + (len - i - 16u), 8); __builtin_memcpy(&v0, src + (len - i - 8u), 8);
+					v0 = __builtin_bswap64(v0); v1 = __builtin_bswap64(v1);
+				} else { __builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8); }
 				if((v0 | v1) & 0xFCFCFCFCFCFCFCFCull){ bad = 1; v0 &= 0x0303030303030303ull; v1 &= 0x0303030303030303ull; }
+				if(QS && rev){ v0 ^= 0x0303030303030303ull; v1 ^= 0x0303030303030303ull; }
 			} else {
 				v0 = v1 = 0;
 #pragma unroll
 				for(uint32_t b = 0; b < 16u; b++){
-					uint8_t c = (i + b < len) ? src[i + b] : padcode;
+					uint8_t c = (i + b < len) ? ((QS && rev) ? src[len - 1u - i - b] : src[i + b]) : padcode;
 					if(i + b < len && c > 3){ bad = 1; c &= 3; }
+					if(QS && rev && i + b < len) c ^= 3;
 					if(b < 8u) v0 |= (uint64_t)c << (8u * b); else v1 |= (uint64_t)c << (8u * (b - 8u));
 				}
 			}
@@ -280,8 +289,8 @@ __global__ void __launch_bounds__(256) k_stage(const uint8_t *seqs, const uint64
 			*(uint4*)(dst + i) = o;
 		}
 	};
-	copy(q, dq, ql, qpad, (uint8_t)BSA_QPAD_CODE);
-	copy(t, dt, tl, tpad, (uint8_t)0);
+	copy(q, dq, ql, qpad, (uint8_t)BSA_QPAD_CODE, qrev);
+	copy(t, dt, tl, tpad, (uint8_t)0, false);
 	uint32_t st = 0;
 	if((TPP == 64) ? __any((int)bad) : __syncthreads_or((int)bad)) st |= BSA_ST_BAD_BASE;
 	if(ql == 0 || tl == 0) st |= BSA_ST_EMPTY;
@@ -289,8 +298,8 @@ __global__ void __launch_bounds__(256) k_stage(const uint8_t *seqs, const uint64
 }
 
 // k_stage for BSA_MODE_SEQ2BIT blobs: the offsets are base offsets into 2-bit packed words (bsa_bits16); the staged bytes, the padding
-// and the empty-pair flag are k_stage's.  No code is above 3, so no BSA_ST_BAD_BASE.
-template<int TPP>
+// and the empty-pair flag are k_stage's.  No code is above 3, so no BSA_ST_BAD_BASE.  QS: a marked query comes through bsa_bits16_rc.
+template<int TPP, bool QS = false>
 __global__ void __launch_bounds__(256) k_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
 		uint8_t *qst, uint8_t *tst, uint32_t qpad, uint32_t tpad, uint32_t *status, uint32_t n){
@@ -299,18 +308,19 @@ __global__ void __launch_bounds__(256) k_stage2b(const uint64_t *seqs, const uin
 	const uint32_t ql = qlen[k], tl = tlen[k];
 	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
 	// 16 bases per thread and trip from at most two words, expanded to one 16-byte store
-	auto copy = [&](uint64_t off, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode){
+	auto copy = [&](uint64_t off, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode, bool rev){
 		const uint32_t total = (len + pad + 15u) & ~15u;
 		for(uint32_t i = lane * 16u; i < total; i += (uint32_t)TPP * 16u){
-			const uint32_t x = bsa_bits16(seqs, off + i, off + len);
+			const uint32_t x = (QS && rev) ? (i < len ? bsa_bits16_rc(seqs, off, off + len - i) : 0u) : bsa_bits16(seqs, off + i, off + len);
 			uint64_t v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
 			if(i + 16u > len){ v0 = bsa_pad_bytes(v0, (int64_t)len - i, padcode); v1 = bsa_pad_bytes(v1, (int64_t)len - i - 8, padcode); }
 			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32);
 			*(uint4*)(dst + i) = o;
 		}
 	};
-	copy(qoff[k], dq, ql, qpad, (uint8_t)BSA_QPAD_CODE);
-	copy(toff[k], dt, tl, tpad, (uint8_t)0);
+	const uint64_t qo = qoff[k];
+	copy(QS ? qo & ~BSA_QOFF_REVCOMP : qo, dq, ql, qpad, (uint8_t)BSA_QPAD_CODE, QS && (qo & BSA_QOFF_REVCOMP) != 0);
+	copy(toff[k], dt, tl, tpad, (uint8_t)0, false);
 	if(lane == 0) status[k] = (ql == 0 || tl == 0) ? BSA_ST_EMPTY : 0u;
 }
 
@@ -853,6 +863,7 @@ struct bsa_align_plan : PlanBase {
 	bool score_only = false;                     // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
 	bool score_fast = false;                     // ... on the SCORE forward kernels (a record a pair); otherwise the full path, its results trimmed
 	bool seq2bit = false;                        // BSA_MODE_SEQ2BIT: d_seqs holds 2-bit packed words, offsets in bases (k_stage2b)
+	bool qstrand = false;                        // BSA_MODE_QSTRAND: bit 63 of qoff[k] asks for the query's reverse complement (the staging kernels' QS forms)
 };
 
 // BSA_MODE_SCORE_ONLY: what the traceback would find is not returned (include/bsalign_hip.h)
@@ -895,9 +906,10 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	*out = nullptr;
 	if(n > 0xFFFFFFF0ull) { c->err = "too many pairs"; return BSA_E_ARG; }
 	// BSA_MODE_CIGAR_EQX is the plan's business alone (PlanBase::eqx): the dispatch below and every kernel see the mode without it
-	const bool eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0;
+	// (BSA_MODE_QSTRAND likewise: the staging kernels are the only code that sees qoff, which is uploaded as given -- nothing below reads it)
+	const bool eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0, qstrand = (par->mode & BSA_MODE_QSTRAND) != 0;
 	bsa_align_params_t par_plain = *par;
-	par_plain.mode &= ~BSA_MODE_CIGAR_EQX;
+	par_plain.mode &= ~(BSA_MODE_CIGAR_EQX | BSA_MODE_QSTRAND);
 	par = &par_plain;
 	const int type = par->mode & 3;
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
@@ -956,7 +968,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	bsa_align_plan *p = new bsa_align_plan();
 	p->ctx = c; p->n = n; p->par = *par; p->bw = bw;
 	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
-	p->eqx = eqx;
+	p->eqx = eqx; p->qstrand = qstrand;
 	p->sys = sys; p->sys_chk = sys && sys_chk; p->max_qlen = max_qlen;
 	p->ref_bw = widened ? (bw_req ? bw_req : 1u) : sys ? bw_req : 0u;
 	p->static_band = bw != 0 && n > 0;
@@ -1033,19 +1045,23 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	}
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
-	if(p->seq2bit){
-		if(p->stage_bytes / std::max<size_t>(n, 1) >= 8192)
-			hipLaunchKernelGGL(k_stage2b<256>, dim3(n), dim3(256), 0, st, (const uint64_t*)d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
-				p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
-		else
-			hipLaunchKernelGGL(k_stage2b<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, (const uint64_t*)d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
-				p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
-	} else if(p->stage_bytes / std::max<size_t>(n, 1) >= 8192)         // long pairs: a block per pair
-		hipLaunchKernelGGL(k_stage<256>, dim3(n), dim3(256), 0, st, d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
-			p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
-	else
-		hipLaunchKernelGGL(k_stage<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen,
-			p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n);
+	{
+		// which staging kernel: 1 B/base or 2-bit words, a block per pair for long pairs (>= 8192 staged bytes) or a wave, and -- only in
+		// plans with BSA_MODE_QSTRAND -- the instantiations that look at bit 63 of qoff[k]
+		const bool blk = p->stage_bytes / std::max<size_t>(n, 1) >= 8192;
+		const dim3 grid(blk ? n : (n + 3u) / 4u);
+#define BSA_STAGE(K, SEQS) hipLaunchKernelGGL(K, grid, dim3(256), 0, st, SEQS, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, \
+			p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n)
+		const uint64_t *d_words = (const uint64_t*)d_seqs;
+		if(p->seq2bit){
+			if(p->qstrand){ if(blk) BSA_STAGE((k_stage2b<256, true>), d_words); else BSA_STAGE((k_stage2b<64, true>), d_words); }
+			else if(blk) BSA_STAGE(k_stage2b<256>, d_words); else BSA_STAGE(k_stage2b<64>, d_words);
+		} else {
+			if(p->qstrand){ if(blk) BSA_STAGE((k_stage<256, true>), d_seqs); else BSA_STAGE((k_stage<64, true>), d_seqs); }
+			else if(blk) BSA_STAGE(k_stage<256>, d_seqs); else BSA_STAGE(k_stage<64>, d_seqs);
+		}
+#undef BSA_STAGE
+	}
 	HIPCHK(c, hipGetLastError());
 	Align8Args a;
 	memset(&a, 0, sizeof(a));
@@ -1164,8 +1180,11 @@ static int check_blob(bsa_ctx *c, int mode, size_t seqs_bytes, const uint64_t *q
 		if(seqs_bytes % 8u){ c->err = "BSA_MODE_SEQ2BIT: seqs_bytes must be a multiple of 8"; return BSA_E_ARG; }
 		lim = 4u * (uint64_t)seqs_bytes;
 	}
-	for(size_t k = 0; k < n; k++)
-		if(qoff[k] > lim || toff[k] > lim || qoff[k] + qlen[k] > lim || toff[k] + tlen[k] > lim){ c->err = "sequence offsets outside the blob"; return BSA_E_ARG; }
+	const uint64_t qmask = (mode & BSA_MODE_QSTRAND) ? ~BSA_QOFF_REVCOMP : ~0ull;         // (without the flag bit 63 is part of the offset: outside every blob)
+	for(size_t k = 0; k < n; k++){
+		const uint64_t qo = qoff[k] & qmask;
+		if(qo > lim || toff[k] > lim || qo + qlen[k] > lim || toff[k] + tlen[k] > lim){ c->err = "sequence offsets outside the blob"; return BSA_E_ARG; }
+	}
 	return BSA_OK;
 }
 
@@ -1203,7 +1222,8 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	};
 	auto intervals = [&](size_t k0, size_t k1, std::vector<Iv> &v) -> bool {
 		std::vector<Iv> raw; raw.reserve(2 * (k1 - k0));
-		for(size_t k = k0; k < k1; k++){ if(qlen[k]) raw.push_back(bytes_of(qoff[k], qlen[k])); if(tlen[k]) raw.push_back(bytes_of(toff[k], tlen[k])); }
+		const uint64_t qmask = (par->mode & BSA_MODE_QSTRAND) ? ~BSA_QOFF_REVCOMP : ~0ull;          // (a marked query is read from the same bytes)
+		for(size_t k = k0; k < k1; k++){ if(qlen[k]) raw.push_back(bytes_of(qoff[k] & qmask, qlen[k])); if(tlen[k]) raw.push_back(bytes_of(toff[k], tlen[k])); }
 		std::sort(raw.begin(), raw.end(), [](const Iv &a, const Iv &b){ return a.lo < b.lo; });
 		for(const Iv &x : raw){
 			if(!v.empty() && x.lo <= v.back().hi + ((size_t)64 << 10)) v.back().hi = std::max(v.back().hi, x.hi);
@@ -1576,6 +1596,7 @@ struct bsa_edit_plan : PlanBase {
 	bool score_only = false;        // BSA_MODE_SCORE_ONLY: no traceback results, no CIGAR
 	bool score_fast = false;        // ... on the SCORE forward kernels and k_edit_score_finish (global / extend: a last row a pair); overlap: the full path, trimmed
 	bool seq2bit = false;           // BSA_MODE_SEQ2BIT: d_seqs holds 2-bit packed words, offsets in bases (k_edit_stage2b)
+	bool qstrand = false;           // BSA_MODE_QSTRAND: bit 63 of qoff[k] asks for the query's reverse complement (the staging kernels' QS forms)
 };
 
 extern "C" void bsa_edit_plan_destroy(bsa_edit_plan_t *p){ plan_free(p); }
@@ -1593,7 +1614,8 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	p->ctx = c; p->n = n; p->par = *par;
 	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
 	p->eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0;          // (the plan's business alone: the kernels see the mode without it)
-	p->par.mode &= ~BSA_MODE_CIGAR_EQX;
+	p->qstrand = (par->mode & BSA_MODE_QSTRAND) != 0;        // (likewise; qoff is uploaded as given and read by the staging kernels alone)
+	p->par.mode &= ~(BSA_MODE_CIGAR_EQX | BSA_MODE_QSTRAND);
 	const auto tp0 = std::chrono::steady_clock::now();
 	std::vector<uint32_t> bwk(n), order(n), qwords(n);
 	double cells = 0;
@@ -1688,7 +1710,7 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
 	HIPCHK(c, bsa_launch_edit_stage(d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, p->d_qpoff, p->d_tpoff, p->d_qboff, p->d_qwords,
-		p->d_qst, p->d_tst, p->d_qbits, status, n, st, p->seq2bit));
+		p->d_qst, p->d_tst, p->d_qbits, status, n, st, p->seq2bit, p->qstrand));
 	EditArgs a;
 	memset(&a, 0, sizeof(a));
 	a.qst = p->d_qst; a.tst = p->d_tst; a.qpoff = p->d_qpoff; a.tpoff = p->d_tpoff;

@@ -30,6 +30,20 @@ __device__ __forceinline__ uint32_t bsa_bits16(const uint64_t *w, uint64_t pos, 
 	if(rem < 16u) x &= (1u << (2u * (uint32_t)rem)) - 1u;
 	return x;
 }
+// BSA_MODE_QSTRAND: the reverse twin -- the 16 bases [end - 16, end) read backwards and complemented (3 - c), LSB first: base end - 1 - j at
+// bits 2j, 2j + 1, bases before `beg` zero.  Inside a word the MSB-first order IS the wanted order read from the other end (base p + 1 sits
+// two bits below base p), so there is no bit reversal: a funnel shift, a NOT and a mask.  Loads the word of base end - 1 and, only when a
+// base at or after `beg` lies in it, the one in front -- never a word in front of the one that holds base `beg`.
+__device__ __forceinline__ uint32_t bsa_bits16_rc(const uint64_t *w, uint64_t beg, uint64_t end){
+	if(end <= beg) return 0u;
+	const uint64_t last = end - 1u, idx = last >> 5, rem = end - beg;
+	const uint32_t r = (uint32_t)(last & 31u);
+	uint32_t x = (uint32_t)(w[idx] >> (62u - 2u * r));              // base end - 1 at bits 1:0, the r bases in front of it above
+	if(r < 15u && ((end - (rem < 16u ? rem : 16u)) >> 5) != idx) x |= (uint32_t)w[idx - 1] << (2u * r + 2u);      // (funnel shift across the word boundary)
+	x = ~x;
+	if(rem < 16u) x &= (1u << (2u * (uint32_t)rem)) - 1u;
+	return x;
+}
 // 8 codes (2 bits each, LSB first) -> 8 bytes
 __device__ __forceinline__ uint64_t bsa_spread8(uint32_t x){
 	uint64_t v = x & 0xFFFFu;
@@ -295,7 +309,8 @@ bool bsa_edit_supported_bw(uint32_t bw);
 bool bsa_edit_tiled_ok(uint32_t bw, uint32_t count, int mode);       // row format 1 for a launch class that fills its chunk alone (bsa_edit.hip)
 hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
-		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit = false);     // seq2bit: BSA_MODE_SEQ2BIT words
+		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit = false,       // seq2bit: BSA_MODE_SEQ2BIT words
+		bool qstrand = false);                                                                                          // qstrand: BSA_MODE_QSTRAND, bit 63 of qoff[k] asks for the reverse complement
 hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st);
 hipError_t bsa_launch_edit_trace(const EditArgs &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
 hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st);        // BSA_MODE_SCORE_ONLY: records -> results

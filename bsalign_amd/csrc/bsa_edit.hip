@@ -1387,29 +1387,38 @@ __global__ void __launch_bounds__(256) k_edit_score_finish(const EditArgs a, bsa
 // stage one pair per block: query -> two bit planes (bit p of plane b = bit b of base p; zero beyond qlen),
 // query and target bytes copied (the traceback compares bases), codes validated
 // (TPP threads per pair: the block for few long pairs, a wave for batches of many -- the k-mer path stages 1.5 M pieces of ~26 bp)
-template<int TPP>
+// QS (plans with BSA_MODE_QSTRAND): bit 63 of qoff[k] asks for the query's reverse complement -- piece i of it is the 16 stored bytes that
+// end at qlen - i, byte-reversed and complemented; bytes and planes are then those of the reverse complement
+template<int TPP, bool QS = false>
 __global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
 		const uint64_t *qboff, const uint32_t *qwords, uint8_t *qst, uint8_t *tst, u64 *qbits, uint32_t *status, uint32_t n){
 	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
 	if(k >= n) return;
 	const uint32_t ql = qlen[k], tl = tlen[k], nw = qwords[k];
-	const uint8_t *q = seqs + qoff[k], *t = seqs + toff[k];
+	const uint64_t qo = qoff[k];
+	const bool qrev = QS && (qo & BSA_QOFF_REVCOMP) != 0;
+	const uint8_t *q = seqs + (QS ? qo & ~BSA_QOFF_REVCOMP : qo), *t = seqs + toff[k];
 	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
 	u64 *p0 = qbits + qboff[k], *p1 = p0 + nw;
 	uint32_t bad = 0;
 	// 16 bases per thread and trip: two 8-byte loads (the piece that holds the end byte by byte), the staged bytes as one 16-byte
 	// store, the two planes as 16 bits each (bit 0 / bit 1 of eight bytes gathered by a multiplication)
-	auto piece = [&](const uint8_t *src, uint32_t len, uint32_t i, u64 &v0, u64 &v1){
+	auto piece = [&](const uint8_t *src, uint32_t len, uint32_t i, u64 &v0, u64 &v1, bool rev){
 		if(i + 16u <= len){
-			__builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8);
+			if(QS && rev){
+				__builtin_memcpy(&v1, src + (len - i - 16u), 8); __builtin_memcpy(&v0, src + (len - i - 8u), 8);
+				v0 = __builtin_bswap64(v0); v1 = __builtin_bswap64(v1);
+			} else { __builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8); }
 			if((v0 | v1) & 0xFCFCFCFCFCFCFCFCull){ bad = 1; v0 &= 0x0303030303030303ull; v1 &= 0x0303030303030303ull; }
+			if(QS && rev){ v0 ^= 0x0303030303030303ull; v1 ^= 0x0303030303030303ull; }
 		} else {
 			v0 = v1 = 0;
 #pragma unroll
 			for(uint32_t b = 0; b < 16u; b++){
-				uint8_t c = (i + b < len) ? src[i + b] : (uint8_t)0;
+				uint8_t c = (i + b < len) ? ((QS && rev) ? src[len - 1u - i - b] : src[i + b]) : (uint8_t)0;
 				if(c > 3){ bad = 1; c &= 3; }
+				if(QS && rev && i + b < len) c ^= 3;
 				if(b < 8u) v0 |= (u64)c << (8u * b); else v1 |= (u64)c << (8u * (b - 8u));
 			}
 		}
@@ -1418,7 +1427,7 @@ __global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const u
 	const uint32_t qbytes = (ql + 16u + 15u) & ~15u, qplane = nw * 64u;
 	for(uint32_t i = lane * 16u; i < max(qbytes, qplane); i += (uint32_t)TPP * 16u){
 		u64 v0, v1;
-		piece(q, ql, i, v0, v1);
+		piece(q, ql, i, v0, v1, qrev);
 		if(i < qbytes){ uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dq + i) = o; }
 		if(i < qplane){
 			((uint16_t*)p0)[i >> 4] = (uint16_t)(gather(v0) | (gather(v1) << 8));
@@ -1428,7 +1437,7 @@ __global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const u
 	const uint32_t tbytes = (tl + 16u + 15u) & ~15u;
 	for(uint32_t i = lane * 16u; i < tbytes; i += (uint32_t)TPP * 16u){
 		u64 v0, v1;
-		piece(t, tl, i, v0, v1);
+		piece(t, tl, i, v0, v1, false);
 		uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dt + i) = o;
 	}
 	uint32_t st = 0;
@@ -1439,20 +1448,22 @@ __global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const u
 
 // k_edit_stage for BSA_MODE_SEQ2BIT blobs: base offsets into 2-bit packed words (bsa_common.h, bsa_bits16).  The two planes come straight
 // from the bits (bit 0 / bit 1 of each base de-interleaved), the staged bytes from spreading them; zero beyond the sequence, no
-// BSA_ST_BAD_BASE (no code is above 3)
-template<int TPP>
+// BSA_ST_BAD_BASE (no code is above 3).  QS: a marked query comes through bsa_bits16_rc.
+template<int TPP, bool QS = false>
 __global__ void __launch_bounds__(256) k_edit_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
 		const uint64_t *qboff, const uint32_t *qwords, uint8_t *qst, uint8_t *tst, u64 *qbits, uint32_t *status, uint32_t n){
 	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
 	if(k >= n) return;
 	const uint32_t ql = qlen[k], tl = tlen[k], nw = qwords[k];
-	const uint64_t qo = qoff[k], to = toff[k];
+	const uint64_t qraw = qoff[k], to = toff[k];
+	const bool qrev = QS && (qraw & BSA_QOFF_REVCOMP) != 0;
+	const uint64_t qo = QS ? qraw & ~BSA_QOFF_REVCOMP : qraw;
 	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
 	u64 *p0 = qbits + qboff[k], *p1 = p0 + nw;
 	const uint32_t qbytes = (ql + 16u + 15u) & ~15u, qplane = nw * 64u;
 	for(uint32_t i = lane * 16u; i < max(qbytes, qplane); i += (uint32_t)TPP * 16u){
-		const uint32_t x = bsa_bits16(seqs, qo + i, qo + ql);
+		const uint32_t x = (QS && qrev) ? (i < ql ? bsa_bits16_rc(seqs, qo, qo + ql - i) : 0u) : bsa_bits16(seqs, qo + i, qo + ql);
 		if(i < qbytes){
 			const u64 v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
 			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dq + i) = o;
@@ -1477,16 +1488,21 @@ bool bsa_edit_supported_bw(uint32_t bw){       // register kernels up to 16 word
 
 hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
-		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit){
+		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit, bool qstrand){
 	if(n == 0) return hipSuccess;
+	// a wave per pair from 65 536 pairs on, a block below; the QS instantiations only for plans with BSA_MODE_QSTRAND
+	const bool wave = n >= 65536u;
+	const dim3 grid(wave ? (n + 3u) / 4u : n);
+#define BSA_ESTAGE(K, SEQS) hipLaunchKernelGGL(K, grid, dim3(256), 0, st, SEQS, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n)
 	if(seq2bit){
 		const uint64_t *w = (const uint64_t*)seqs;
-		if(n >= 65536u) hipLaunchKernelGGL(k_edit_stage2b<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, w, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
-		else hipLaunchKernelGGL(k_edit_stage2b<256>, dim3(n), dim3(256), 0, st, w, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
-		return hipGetLastError();
+		if(qstrand){ if(wave) BSA_ESTAGE((k_edit_stage2b<64, true>), w); else BSA_ESTAGE((k_edit_stage2b<256, true>), w); }
+		else if(wave) BSA_ESTAGE(k_edit_stage2b<64>, w); else BSA_ESTAGE(k_edit_stage2b<256>, w);
+	} else {
+		if(qstrand){ if(wave) BSA_ESTAGE((k_edit_stage<64, true>), seqs); else BSA_ESTAGE((k_edit_stage<256, true>), seqs); }
+		else if(wave) BSA_ESTAGE(k_edit_stage<64>, seqs); else BSA_ESTAGE(k_edit_stage<256>, seqs);
 	}
-	if(n >= 65536u) hipLaunchKernelGGL(k_edit_stage<64>, dim3((n + 3u) / 4u), dim3(256), 0, st, seqs, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
-	else hipLaunchKernelGGL(k_edit_stage<256>, dim3(n), dim3(256), 0, st, seqs, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n);
+#undef BSA_ESTAGE
 	return hipGetLastError();
 }
 

@@ -94,6 +94,37 @@ extern "C" {
                                       reference's), the bsalign-hip CLI (its alignment strings already mark mismatches), the POA or the
                                       rows API.  bsa_shard_gather carries CIGAR words as opaque data and needs no flag. */
 
+#define BSA_MODE_QSTRAND  0x2000  /* flag: bit 63 of qoff[k] is the query's strand -- for bsa_align_batch / _plan_create / _run and bsa_edit_batch /
+                                      _plan_create / _run.  With the flag, qoff[k] & ~BSA_QOFF_REVCOMP is the offset of the stored query (bytes,
+                                      or bases with BSA_MODE_SEQ2BIT) and qoff[k] & BSA_QOFF_REVCOMP says that pair k aligns the REVERSE
+                                      COMPLEMENT q' of the stored qlen[k] bases: q'[i] = 3 - q[qlen - 1 - i] (codes A 0, C 1, G 2, T 3, so the
+                                      complement is (~c) & 3 -- what the reference's dna.h does; its revseq_basebank builds such a copy on the
+                                      host).  toff is untouched: only queries have a strand (reverse-complementing both sides is the mirrored
+                                      forward alignment).  A read that takes part in many pairs, on either strand, is stored once.
+                                      Everything returned for a marked pair is bit-identical to the same call WITHOUT the flag on a blob in
+                                      which the caller stored q': all ten fields of bsa_result_t, the CIGAR words (read along q', also with
+                                      BSA_MODE_CIGAR_EQX), cigar_off, status.  qb / qe are positions in q'; the interval on the stored strand
+                                      is [qlen - qe, qlen - qb).  Example: a stored query of 100 bases, marked, comes back with qb = 10,
+                                      qe = 95 -- the alignment covers q'[10, 95), which is the reverse complement of stored bases [5, 90);
+                                      the first CIGAR word speaks of stored base 89, the last one of stored base 5.
+                                      A marked pair whose stored 1 B/base query holds a code above 3 gets BSA_ST_BAD_BASE, exactly when the
+                                      unmarked pair would; a marked query of length 0 is BSA_ST_EMPTY.  A batch with the flag in which no
+                                      pair is marked returns what the call without the flag returns.  Without the flag nothing changes: bit
+                                      63 stays part of the offset (bsa_*_batch answers BSA_E_ARG, offsets outside the blob), the staging
+                                      kernels launched are the ones without the strand test, no extra kernel runs and no extra workspace is
+                                      taken.  Bounds are tested on, and reads made from, the masked offset; with BSA_MODE_SEQ2BIT nothing is
+                                      read in front of the word that holds the stored query's first base nor behind the one that holds its
+                                      last.  Combines with BSA_MODE_SCORE_ONLY, BSA_MODE_SEQ2BIT, BSA_MODE_ROWRECORDS, BSA_MODE_CIGAR_EQX and
+                                      all three alignment modes; bsa_align_batch keeps it on every route it takes (two slices, width classes
+                                      of whole-query bands, pairs handed over to the literal kernels, the checked whole-query kernel's
+                                      re-runs).  Only the four staging kernels see the strand: they stage q' and everything behind them reads
+                                      the staged copy as before.  Not taken by bsa_kmer_edit_batch (anchors are chained on the host from the
+                                      stored bytes), the compat single-pair layer, the bsalign-hip CLI (the reference's command line has no
+                                      strand option), the POA or the rows API.  Shards: the local_qoff arrays bsa_shard_scatter hands back
+                                      are the caller's; OR-ing BSA_QOFF_REVCOMP into them before bsa_align_plan_create / bsa_edit_plan_create
+                                      (with the flag in the mode) is the supported way to use strands with shards. */
+#define BSA_QOFF_REVCOMP  (1ull << 63) /* only with BSA_MODE_QSTRAND */
+
 /* CIGAR op codes (bsalign.h:61-69) */
 #define BSA_CIGAR_M 0
 #define BSA_CIGAR_I 1
