@@ -18,6 +18,8 @@ MODE_GLOBAL, MODE_OVERLAP, MODE_EXTEND = 0, 1, 2
 MODE_ROWRECORDS, MODE_SCORE_ONLY, MODE_SEQ2BIT = 0x100, 0x400, 0x800       # flags OR-ed into the mode (include/bsalign_hip.h)
 MODE_CIGAR_EQX = 0x1000                                                   # ... M words leave as runs of = and X
 MODE_QSTRAND = 0x2000                                                     # ... bit 63 of qoff[k] is the query's strand
+MODE_BAND_MARGIN = 0x4000                                                 # ... status[k] >> ST_MARGIN_SHIFT is the pair's band margin (8-bit aligner only)
+ST_MARGIN_SHIFT, ST_MARGIN_NONE = 16, 0xFFFF                              # ST_MARGIN_NONE: no band edge constrained the path, or the pair has no CIGAR
 QOFF_REVCOMP = 1 << 63                                                    # in qoff[k], with MODE_QSTRAND: align the reverse complement of the stored query
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
@@ -122,6 +124,7 @@ def lib():
         L.bsa_last_error.restype = C.c_char_p
         L.bsa_ctx_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_double)]
         L.bsa_ctx_last_trace_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        L.bsa_ctx_last_margin_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.bsa_ctx_last_kernel_name.argtypes = [vp, C.c_int]
         L.bsa_ctx_last_kernel_name.restype = C.c_char_p
         L.bsa_ctx_last_handover.argtypes = [vp]
@@ -370,6 +373,12 @@ class Context:
         self._chk(lib().bsa_ctx_last_trace_ms(self.h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def last_margin_ms(self):
+        """average duration of the BSA_MODE_BAND_MARGIN pass's launches in the last run (0 launches without the flag)"""
+        ms, n = C.c_double(), C.c_long()
+        self._chk(lib().bsa_ctx_last_margin_ms(self.h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def last_handover(self):
         """pairs of the last align_batch call that were re-run through the literal kernels"""
         return int(lib().bsa_ctx_last_handover(self.h))
@@ -392,15 +401,20 @@ class Context:
         cigs = [cig[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
         return out, cigs, status[:n]
 
-    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False, eqx=False, strands=None):
+    def align_batch(self, pairs, par, cigar_cap=None, seq2bit=False, eqx=False, strands=None, margins=False):
         """host-pointer form of bsa_align_batch: returns (results, [cigar arrays], status); seq2bit: the sequences go down
         2-bit packed (pack_pairs(..., seq2bit=True), BSA_MODE_SEQ2BIT OR-ed into par.mode); eqx: BSA_MODE_CIGAR_EQX OR-ed in,
         the CIGARs come back with = / X words (the default cigar_cap holds them: a word covers at least one column); strands (a bool
-        per pair): BSA_MODE_QSTRAND OR-ed in, the queries go down as given and pair k aligns revcomp(q) where strands[k] is true"""
-        if seq2bit or eqx or strands is not None:
+        per pair): BSA_MODE_QSTRAND OR-ed in, the queries go down as given and pair k aligns revcomp(q) where strands[k] is true;
+        margins: BSA_MODE_BAND_MARGIN OR-ed in, returns (results, [cigar arrays], status, margins) -- the band margins as a uint16 array of
+        their own (ST_MARGIN_NONE where no band edge constrained the path) beside the status masked to its low half"""
+        if seq2bit or eqx or strands is not None or margins:
             par = AlignParams.from_buffer_copy(par)
-            par.mode |= (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0) | (MODE_QSTRAND if strands is not None else 0)
-        return self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit, strands)
+            par.mode |= (MODE_SEQ2BIT if seq2bit else 0) | (MODE_CIGAR_EQX if eqx else 0) | (MODE_QSTRAND if strands is not None else 0) | (MODE_BAND_MARGIN if margins else 0)
+        out, cigs, status = self._batch(lib().bsa_align_batch, pairs, par, cigar_cap, seq2bit, strands)
+        if margins:
+            return out, cigs, status & np.uint32(0xFFFF), (status >> np.uint32(ST_MARGIN_SHIFT)).astype(np.uint16)
+        return out, cigs, status
 
     def align_scores(self, pairs, par, seq2bit=False, strands=None):
         """bsa_align_batch with BSA_MODE_SCORE_ONLY OR-ed into par.mode and no CIGAR arena: returns (results, status); score, qe and te as
@@ -539,7 +553,8 @@ class AlignPlan:
     Device buffers are torch tensors (plumbing only); the run is asynchronous on the context's stream.  With MODE_SEQ2BIT in
     par.mode, d_seqs holds 2-bit packed words (pack2bit) and the offsets are base offsets; with MODE_CIGAR_EQX the CIGAR words
     are = / X runs and d_cigar must hold the expanded words; with MODE_QSTRAND a qoff[k] with QOFF_REVCOMP OR-ed in aligns the
-    reverse complement of the stored query."""
+    reverse complement of the stored query; with MODE_BAND_MARGIN d_status is required and d_status[k] >> ST_MARGIN_SHIFT is the
+    pair's band margin."""
 
     def __init__(self, ctx, qoff, qlen, toff, tlen, par):
         self.ctx = ctx

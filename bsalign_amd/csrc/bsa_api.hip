@@ -36,6 +36,8 @@ struct bsa_ctx {
 	double last_cells = 0;
 	std::vector<hipEvent_t> tev;     // the same for the traceback launches (on the stream they run on)
 	size_t tev_used = 0;
+	std::vector<hipEvent_t> mev;     // ... and for the BSA_MODE_BAND_MARGIN pass
+	size_t mev_used = 0;
 	std::string fwd_name, trace_name;    // kernels behind those two timings
 	long last_handover = 0;              // pairs the last bsa_align_batch re-ran through the literal kernels
 	double diagdp_ms = 0;
@@ -141,6 +143,7 @@ extern "C" void bsa_ctx_destroy(bsa_ctx_t *c){
 	for(hipEvent_t e : c->ev) (void)hipEventDestroy(e);
 	for(hipEvent_t e : c->sev) (void)hipEventDestroy(e);
 	for(hipEvent_t e : c->tev) (void)hipEventDestroy(e);
+	for(hipEvent_t e : c->mev) (void)hipEventDestroy(e);
 	if(c->ws) (void)hipFree(c->ws);
 	for(int k = 0; k < 2; k++) if(c->keep[k]) (void)hipFree(c->keep[k]);
 	for(int k = 0; k < 3; k++) if(c->scratch[k]) (void)hipFree(c->scratch[k]);
@@ -186,6 +189,21 @@ extern "C" int bsa_ctx_last_trace_ms(bsa_ctx_t *c, double *ms, long *launches){
 	if(launches) *launches = n;
 	return BSA_OK;
 }
+extern "C" int bsa_ctx_last_margin_ms(bsa_ctx_t *c, double *ms, long *launches){
+	if(!c) return BSA_E_ARG;
+	(void)hipSetDevice(c->device);
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
+	double tot = 0; long n = 0;
+	for(size_t i = 0; i + 1 < c->mev_used; i += 2){
+		float t = 0;
+		HIPCHK(c, hipEventElapsedTime(&t, c->mev[i], c->mev[i + 1]));
+		tot += t; n++;
+	}
+	if(ms) *ms = n ? tot / (double)n : 0.0;
+	if(launches) *launches = n;
+	return BSA_OK;
+}
 thread_local const char *bsa_last_fwd_kernel = nullptr, *bsa_last_trace_kernel = nullptr;
 extern "C" long bsa_ctx_last_handover(bsa_ctx_t *c){ return c ? c->last_handover : 0; }
 extern "C" const char *bsa_ctx_last_kernel_name(bsa_ctx_t *c, int traceback){ return !c ? "" : traceback ? c->trace_name.c_str() : c->fwd_name.c_str(); }
@@ -198,6 +216,17 @@ static int ctx_trace_event_pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
 	}
 	*a = c->tev[c->tev_used]; *b = c->tev[c->tev_used + 1];
 	c->tev_used += 2;
+	return BSA_OK;
+}
+
+static int ctx_margin_event_pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
+	while(c->mev.size() < c->mev_used + 2){
+		hipEvent_t e;
+		HIPCHK(c, hipEventCreate(&e));
+		c->mev.push_back(e);
+	}
+	*a = c->mev[c->mev_used]; *b = c->mev[c->mev_used + 1];
+	c->mev_used += 2;
 	return BSA_OK;
 }
 
@@ -531,6 +560,9 @@ struct PlanBase {
 	bool eqx = false;               // BSA_MODE_CIGAR_EQX: M words leave as = / X runs (bsa_cigar_eqx.hip; run_pipeline)
 	uint32_t *d_cnt_plain = nullptr;        // ... the plain word counts by position, beside the expanded ones in d_cnt_pos
 	const bsa_result_t *eqx_out = nullptr;  // ... the records of the run in progress (qb / tb seed the walk)
+	bool margin = false;            // BSA_MODE_BAND_MARGIN: status[k] >> 16 = the pair's band margin (bsa_band_margin.hip; run_pipeline)
+	uint32_t margin_bandwidth = 0;  // ... the caller's bandwidth parameter
+	uint32_t *margin_status = nullptr;      // ... the status array of the run in progress
 	void *pool = nullptr;           // one allocation behind all the metadata pointers above (plan_common_alloc)
 	bool pool_kept = false;         // ... which is the context's kept buffer (ctx_buf_get)
 	std::vector<void*> extra;       // path-specific device allocations
@@ -726,6 +758,15 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 		HIPCHK(c, hipEventRecord(t0, stt));
 		rc = trace(ch, half, stt); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(t1, stt));
+		if(p->margin){
+			// BSA_MODE_BAND_MARGIN: behind the chunk's walkers on their stream, in front of everything that replaces the plain word counts or reuses the slots
+			hipEvent_t m0, m1;
+			rc = ctx_margin_event_pair(c, &m0, &m1); if(rc != BSA_OK) return rc;
+			HIPCHK(c, hipEventRecord(m0, stt));
+			HIPCHK(c, bsa_launch_band_margin(half, p->d_slot, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_order, p->d_qlen, p->d_tlen, p->eqx_out,
+				p->margin_bandwidth, p->margin_status, stt));
+			HIPCHK(c, hipEventRecord(m1, stt));
+		}
 		if(eqx) HIPCHK(c, bsa_launch_cigar_eqx_count(half, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_cnt_plain, es, stt));
 		if(want_cig && !direct){
 			HIPCHK(c, launch_excl_scan(stt, p->d_cnt_pos + ch.first, p->d_off_pos + ch.first, ch.count, p->d_carry, p->d_scan_tmp));
@@ -761,7 +802,7 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 static int run_prologue(PlanBase *p, bool want_cig, size_t cigar_cap_words){
 	bsa_ctx *c = p->ctx;
 	(void)hipSetDevice(c->device);
-	c->ev_used = 0; c->tev_used = 0; c->last_cells = 0;
+	c->ev_used = 0; c->tev_used = 0; c->mev_used = 0; c->last_cells = 0;
 	int rc = ctx_ws_reserve(c, p->half_bytes * p->nbuf);
 	if(rc != BSA_OK) return rc;
 	const bool direct = p->chunks.size() == 1 && !p->two_halves && !bsa_env("BSA_CIGAR_VIA_ARENA");          // (run_pipeline: no pass through the arena)
@@ -907,9 +948,11 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	if(n > 0xFFFFFFF0ull) { c->err = "too many pairs"; return BSA_E_ARG; }
 	// BSA_MODE_CIGAR_EQX is the plan's business alone (PlanBase::eqx): the dispatch below and every kernel see the mode without it
 	// (BSA_MODE_QSTRAND likewise: the staging kernels are the only code that sees qoff, which is uploaded as given -- nothing below reads it)
-	const bool eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0, qstrand = (par->mode & BSA_MODE_QSTRAND) != 0;
+	// (BSA_MODE_BAND_MARGIN likewise: a pass behind the walkers -- run_pipeline)
+	const bool eqx = (par->mode & BSA_MODE_CIGAR_EQX) != 0, qstrand = (par->mode & BSA_MODE_QSTRAND) != 0, margin = (par->mode & BSA_MODE_BAND_MARGIN) != 0;
+	if(margin && (par->mode & BSA_MODE_SCORE_ONLY)){ c->err = "BSA_MODE_BAND_MARGIN and BSA_MODE_SCORE_ONLY exclude each other (no path)"; return BSA_E_ARG; }
 	bsa_align_params_t par_plain = *par;
-	par_plain.mode &= ~(BSA_MODE_CIGAR_EQX | BSA_MODE_QSTRAND);
+	par_plain.mode &= ~(BSA_MODE_CIGAR_EQX | BSA_MODE_QSTRAND | BSA_MODE_BAND_MARGIN);
 	par = &par_plain;
 	const int type = par->mode & 3;
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
@@ -969,6 +1012,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	p->ctx = c; p->n = n; p->par = *par; p->bw = bw;
 	p->seq2bit = (par->mode & BSA_MODE_SEQ2BIT) != 0;
 	p->eqx = eqx; p->qstrand = qstrand;
+	p->margin = margin; p->margin_bandwidth = par->bandwidth;
 	p->sys = sys; p->sys_chk = sys && sys_chk; p->max_qlen = max_qlen;
 	p->ref_bw = widened ? (bw_req ? bw_req : 1u) : sys ? bw_req : 0u;
 	p->static_band = bw != 0 && n > 0;
@@ -1033,6 +1077,8 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	if(!p || !d_out) return BSA_E_ARG;
 	bsa_ctx *c = p->ctx;
 	if(p->seq2bit && ((uintptr_t)d_seqs & 7u)){ c->err = "BSA_MODE_SEQ2BIT: d_seqs must be 8-byte aligned"; return BSA_E_ARG; }
+	if(p->margin && !d_status){ c->err = "BSA_MODE_BAND_MARGIN needs a status array"; return BSA_E_ARG; }
+	p->margin_status = d_status;
 	const uint32_t n = (uint32_t)p->n;
 	const bool want_cig = !p->score_only && d_cigar != nullptr && d_cigar_off != nullptr;          // (score only: d_cigar_off gets zeros -- run_pipeline)
 	int rc = run_prologue(p, want_cig, cigar_cap_words);
@@ -1355,6 +1401,10 @@ extern "C" int bsa_align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_by
 		const bsa_align_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
 		uint64_t *cigar_off, uint32_t *status){
 	if(!c || !out || !par) return BSA_E_ARG;
+	if(par->mode & BSA_MODE_BAND_MARGIN){
+		if(par->mode & BSA_MODE_SCORE_ONLY){ c->err = "BSA_MODE_BAND_MARGIN and BSA_MODE_SCORE_ONLY exclude each other (no path)"; return BSA_E_ARG; }
+		if(!status){ c->err = "BSA_MODE_BAND_MARGIN needs a status array"; return BSA_E_ARG; }
+	}
 	if(!(par->mode & BSA_MODE_SCORE_ONLY)) return align_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status);
 	if(par->mode & BSA_MODE_ROWRECORDS){ c->err = "BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS exclude each other"; return BSA_E_ARG; }
 	const int rc = align_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, nullptr, 0, nullptr, status);
@@ -1467,7 +1517,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 	};
 	size_t left_flagged = 0;                           // undecided pairs the literal kernels cannot take: they keep BSA_ST_TRACE and a zeroed result
 	for(size_t k = 0; k < n; k++){
-		const bool want = (st[k] & BSA_ST_TRACE) || (every > 0 && k % (size_t)every == 0 && st[k] == 0);
+		const bool want = (st[k] & BSA_ST_TRACE) || (every > 0 && k % (size_t)every == 0 && (st[k] & 0xFFFFu) == 0);          // (the low half: the upper one is the band margin's)
 		if(!want) continue;
 		if(literal_can_take(k)) idx.push_back(k);
 		else if(st[k] & BSA_ST_TRACE) left_flagged ++;
@@ -1609,6 +1659,7 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	if(n > 0xFFFFFFF0ull){ c->err = "too many pairs"; return BSA_E_ARG; }
 	const int type = par->mode & 3;
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
+	if(par->mode & BSA_MODE_BAND_MARGIN){ c->err = "BSA_MODE_BAND_MARGIN is not taken by the edit aligner"; return BSA_E_ARG; }
 	(void)hipSetDevice(c->device);
 	bsa_edit_plan *p = new bsa_edit_plan();
 	p->ctx = c; p->n = n; p->par = *par;
@@ -1759,6 +1810,7 @@ extern "C" int bsa_edit_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_byt
 		const bsa_edit_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
 		uint64_t *cigar_off, uint32_t *status){
 	if(!c || !out || !par) return BSA_E_ARG;
+	if(par->mode & BSA_MODE_BAND_MARGIN){ c->err = "BSA_MODE_BAND_MARGIN is not taken by the edit aligner"; return BSA_E_ARG; }
 	if(!(par->mode & BSA_MODE_SCORE_ONLY)) return edit_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status);
 	const int rc = edit_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, nullptr, 0, nullptr, status);
 	if(rc == BSA_OK && cigar_off) memset(cigar_off, 0, (n + 1) * sizeof(uint64_t));

@@ -323,3 +323,7 @@ hipError_t bsa_launch_cigar_collect_eqx(const uint8_t *rows, const uint64_t *slo
 		const uint64_t *off, uint32_t *tmp, uint64_t cap, const EqxSeqs &s, hipStream_t st);
 hipError_t bsa_launch_cigar_final_direct_eqx(const uint8_t *rows, const uint64_t *slot_end, const uint32_t *cnt_pair, const uint64_t *pos_pair, const uint32_t *cnt_plain,
 		const uint64_t *dst_off, uint32_t *dst, uint64_t cap, uint32_t n, const EqxSeqs &s, hipStream_t st);
+// BSA_MODE_BAND_MARGIN (bsa_band_margin.hip): after a chunk's traceback, status[pair] |= margin << BSA_ST_MARGIN_SHIFT from the band offsets at the front of
+// every slot and the plain CIGAR words at its tail (cnt: the plain word counts by position -- before k_cigar_eqx_count replaces them); bandwidth: the caller's
+hipError_t bsa_launch_band_margin(const uint8_t *rows, const uint64_t *slot_off, const uint64_t *slot_end, uint32_t first, uint32_t count, const uint32_t *cnt,
+		const uint32_t *order, const uint32_t *qlen, const uint32_t *tlen, const bsa_result_t *out, uint32_t bandwidth, uint32_t *status, hipStream_t st);

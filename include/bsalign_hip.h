@@ -124,6 +124,46 @@ extern "C" {
                                       are the caller's; OR-ing BSA_QOFF_REVCOMP into them before bsa_align_plan_create / bsa_edit_plan_create
                                       (with the flag in the mode) is the supported way to use strands with shards. */
 #define BSA_QOFF_REVCOMP  (1ull << 63) /* only with BSA_MODE_QSTRAND */
+#define BSA_MODE_BAND_MARGIN 0x4000 /* flag: status[k] >> BSA_ST_MARGIN_SHIFT is the BAND MARGIN of pair k -- how close its alignment came to the edge
+                                      of its band -- for bsa_align_batch / _plan_create / _run.  The 8-bit aligner is a heuristic: its band of
+                                      `bandwidth` columns slides with the scores (bsalign.h:3331-3349, 4007-4021), and where the true alignment drifts
+                                      further than the band can follow the call still returns a well-formed record and CIGAR, of an alignment
+                                      squeezed along the band's edge.  The margin says which pairs those are.
+                                      status[k] & 0xFFFF, out[k], the CIGAR words and cigar_off are bit-identical to the same call without the flag.
+                                      Definition.  B = roundup16(bandwidth ? bandwidth : qlen), the reference's effective width (bsalign.h:3861-3862),
+                                      whatever width the kernel that runs has.  The path is the sequence of vertices (i, j) = (target bases, query
+                                      bases consumed): it starts at (tb, qb), which counts, and follows the CIGAR of the plain call -- an M (or
+                                      = / X) word of length L visits (i + k, j + k) for k = 1..L, an I word (i, j + k), a D word (i + k, j).  A
+                                      vertex with i >= 1 and j >= 1 is the DP cell of target row r = i - 1 and query column c = j - 1; other
+                                      vertices are skipped.  With b = the band offset of row r (the band covers columns [b, b + B)) the cell
+                                      contributes c - b, its distance to the low edge, only if b > 0, and b + B - 1 - c, to the high edge, only
+                                      if b + B < qlen: an edge that lies on an end of the query constrains nothing.  The margin is the minimum
+                                      of all contributions (one below 0 -- a cell outside its row's band, which no traceback visits -- counts
+                                      as 0), clamped to 0xFFFE.  It is BSA_ST_MARGIN_NONE when nothing contributed -- always so for whole-query
+                                      bands, B >= qlen -- and when the pair returns no CIGAR (empty, bad base, BSA_ST_TRACE, BSA_ST_DEVICE).
+                                      Margin 0: the path ran on an edge cell of a band that could have been somewhere else -- the pair to run
+                                      again at a wider band.
+                                      Example: bandwidth 16, query and target of 24 bases, qb = tb = 0, CIGAR 24M -- the cells (r, r) --, band
+                                      offsets of rows 0..23 = 0 0 0 0 0 0 0 0 1 2 3 4 5 6 7 8 8 8 8 8 8 8 8 8.  The low edge counts on rows 8..23
+                                      (b > 0): r - b = 7 on rows 8..15, then 8..15.  The high edge counts on rows 0..14 (b + 16 < 24):
+                                      b + 15 - r = 15 down to 8 on rows 0..7, 8 on rows 8..14.  The margin is 7.  Had the CIGAR been 12M 4D 4I 8M,
+                                      the deletion would run down column 11 to row 15 (b = 8: low 3) and the margin would be 3.
+                                      status == NULL / d_status == NULL with the flag is BSA_E_ARG (the margin has nowhere else to go);
+                                      BSA_MODE_BAND_MARGIN | BSA_MODE_SCORE_ONLY is BSA_E_ARG (there is no path).  Combines with all three alignment
+                                      modes and with BSA_MODE_ROWRECORDS, BSA_MODE_SEQ2BIT, BSA_MODE_QSTRAND and BSA_MODE_CIGAR_EQX (= / X words
+                                      count as M: the margin is the one without it).  bsa_align_batch keeps it on every route it takes (two
+                                      slices, width classes of whole-query bands, pairs handed over to the literal kernels -- their margin comes
+                                      from the re-run's own band --, the checked whole-query kernel's re-runs) and decides its hand-over from the
+                                      low status half alone.  The margin is a pass over the band offsets and CIGAR words the forward and traceback
+                                      kernels leave in a pair's workspace slot (bsa_band_margin.hip), after each chunk's traceback: without the
+                                      flag no kernel of it is launched, no workspace is taken, no existing kernel changes and the upper status
+                                      half stays 0.  bsa_ctx_last_margin_ms times it.
+                                      bsa_edit_batch / bsa_edit_plan_create answer BSA_E_ARG to the flag for now: the test oracle has no hook for
+                                      the edit aligner's band trajectory, so a value there could not be pinned against the reference.  Not taken
+                                      by bsa_kmer_edit_batch, the compat single-pair layer, the bsalign-hip CLI, the POA or the rows API;
+                                      bsa_shard_* carry status as the caller's own array. */
+#define BSA_ST_MARGIN_SHIFT 16
+#define BSA_ST_MARGIN_NONE  0xFFFFu
 
 /* CIGAR op codes (bsalign.h:61-69) */
 #define BSA_CIGAR_M 0
@@ -193,6 +233,8 @@ int         bsa_ctx_last_kernel_ms(bsa_ctx_t *ctx, double *ms, long *launches, d
  * (traceback = 0: forward DP, 1: traceback) */
 int         bsa_ctx_last_trace_ms(bsa_ctx_t *ctx, double *ms, long *launches);
 const char *bsa_ctx_last_kernel_name(bsa_ctx_t *ctx, int traceback);
+/* the same for the BSA_MODE_BAND_MARGIN pass of the last bsa_align_run call (one launch a workspace chunk; 0 launches without the flag) */
+int         bsa_ctx_last_margin_ms(bsa_ctx_t *ctx, double *ms, long *launches);
 /* pairs of the last bsa_align_batch call that the compact (code) path left undecided and the literal kernels re-ran
  * (the hand-over described at bsa_align_batch; with scores outside the static guard: the pairs the checked whole-query
  * kernel flagged) */
