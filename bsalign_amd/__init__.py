@@ -23,6 +23,7 @@ ST_MARGIN_SHIFT, ST_MARGIN_NONE = 16, 0xFFFF                              # ST_M
 QOFF_REVCOMP = 1 << 63                                                    # in qoff[k], with MODE_QSTRAND: align the reverse complement of the stored query
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
+KMER_CHAIN_DEVICE = 1                                                      # bsa_kmer_edit_batch2: the anchors come from the device chainer
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
            -5: "BSA_E_CIGAR_CAP", -6: "BSA_E_UNSUPPORTED"}
@@ -155,6 +156,11 @@ def lib():
             L.bsa_edit_run.argtypes = [vp, u8p, vp, u32p, C.c_size_t, u64p, u32p]
         L.bsa_kmer_edit_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
                                           vp, u32p, C.c_size_t, u64p, u32p]
+        L.bsa_kmer_edit_batch2.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
+                                           vp, u32p, C.c_size_t, u64p, u32p, C.c_uint32]
+        L.bsa_kmer_chain_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.c_uint32,
+                                           u64p, C.c_size_t, u64p, u32p]
+        L.bsa_ctx_last_kmer_chain_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -530,11 +536,35 @@ class Context:
         self._chk(lib().bsa_seq_pack2bit(self.h, C.c_void_p(d_codes.data_ptr()), n, C.c_void_p(d_bits.data_ptr()),
                                          C.c_void_p(d_bad.data_ptr() if d_bad is not None else 0)))
 
-    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None):
-        """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch"""
+    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None, device_chain=False):
+        """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch;
+        device_chain: the anchors come from the device chainer (bsa_kmer_edit_batch2 with KMER_CHAIN_DEVICE), same results"""
         p = KmerParams()
         p.ksz, p.threads = ksz, threads
-        return self._batch(lib().bsa_kmer_edit_batch, pairs, p, cigar_cap)
+        if not device_chain:
+            return self._batch(lib().bsa_kmer_edit_batch, pairs, p, cigar_cap)
+        fn = lib().bsa_kmer_edit_batch2
+        return self._batch(lambda *a: fn(*a, KMER_CHAIN_DEVICE), pairs, p, cigar_cap)
+
+    def kmer_chain_batch(self, pairs, ksz=13, with_status=False):
+        """bsa_kmer_chain_batch: the anchors of every pair (query offset << 32 | target offset, in query order) as a list of uint64 arrays,
+        chained on the device; with_status: (anchors, status) -- ST_EMPTY / ST_BAD_BASE pairs have none"""
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        n = len(pairs)
+        cap = int(np.minimum(qlen, tlen).sum()) + 1
+        maps = np.zeros(cap, dtype=np.uint64)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self._chk(lib().bsa_kmer_chain_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
+                                             _p(maps), cap, _p(off), _p(status)))
+        res = [maps[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
+        return (res, status[:n]) if with_status else res
+
+    def last_kmer_chain_ms(self):
+        """(kernel ms, pairs chained on the device, pairs chained on the host) of the last kmer_chain_batch / kmer_edit_batch(device_chain=True)"""
+        ms, a, b = C.c_double(), C.c_long(), C.c_long()
+        self._chk(lib().bsa_ctx_last_kmer_chain_ms(self.h, C.byref(ms), C.byref(a), C.byref(b)))
+        return ms.value, a.value, b.value
 
 
 def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):

@@ -41,6 +41,7 @@ struct bsa_ctx {
 	std::string fwd_name, trace_name;    // kernels behind those two timings
 	long last_handover = 0;              // pairs the last bsa_align_batch re-ran through the literal kernels
 	double diagdp_ms = 0;
+	double kmer_chain_ms = 0; long kmer_on_device = 0, kmer_on_host = 0;      // last bsa_kmer_chain_batch / bsa_kmer_edit_batch2 (bsa_ctx_last_kmer_chain_ms)
 	// small device buffers kept between calls (slot 0: a plan's metadata pool, slot 1: the host-pointer wrapper's buffers): a batch
 	// of one pair otherwise spends more time in hipMalloc / hipFree than in its kernels
 	size_t budget_last = 0;          // last answer of ctx_ws_budget
@@ -1631,6 +1632,20 @@ extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *c, hipStream_t *st){
 	if(!c || !st) return BSA_E_ARG;
 	(void)hipSetDevice(c->device);
 	*st = c->stream;
+	return BSA_OK;
+}
+
+// the device k-mer chainer (bsa_kmer_dev.hip, driven from bsa_kmer.cpp): the caller's workspace limit (0 = none set) and what the last chaining did
+extern "C" size_t bsa_ctx_workspace_limit_internal(bsa_ctx_t *c){ return c ? c->ws_limit : 0; }
+extern "C" void bsa_ctx_set_kmer_chain_stats_internal(bsa_ctx_t *c, double ms, long on_device, long on_host){
+	if(!c) return;
+	c->kmer_chain_ms = ms; c->kmer_on_device = on_device; c->kmer_on_host = on_host;
+}
+extern "C" int bsa_ctx_last_kmer_chain_ms(bsa_ctx_t *c, double *ms, long *pairs_on_device, long *pairs_on_host){
+	if(!c) return BSA_E_ARG;
+	if(ms) *ms = c->kmer_chain_ms;
+	if(pairs_on_device) *pairs_on_device = c->kmer_on_device;
+	if(pairs_on_host) *pairs_on_host = c->kmer_on_host;
 	return BSA_OK;
 }
 

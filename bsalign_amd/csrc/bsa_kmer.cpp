@@ -282,23 +282,123 @@ extern "C" int bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, cons
 	return assemble(segs, nseg, seg_out, ptr.data(), cnt.data(), out, cigar, cigar_cap_words, cigar_words);
 }
 
-static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
-		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
-		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status);
+/* the device chainer (bsa_kmer_dev.hip) and the context's record of what the last chaining did (bsa_api.hip) */
+extern "C" uint32_t bsa_kmer_dev_max_internal(void);
+extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms);
+extern "C" void bsa_ctx_set_kmer_chain_stats_internal(bsa_ctx_t *ctx, double ms, long on_device, long on_host);
 
-extern "C" int bsa_kmer_edit_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
-		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
-		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status){
+namespace {
+/* anchors of the pairs of a batch that the device chained: pair k's are arena[off[pos[k]] .. off[pos[k] + 1]), pos[k] == NONE = left to the host
+ * (qlen + tlen above bsa_kmer_dev_max_internal(), or a pair that alone does not fit the workspace limit) */
+struct DevChains {
+	uint64_t *arena = nullptr;
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> pos, st;
+	long on_device = 0, on_host = 0;
+	double ms = 0;
+	~DevChains(){ free(arena); }
+};
+/* literal: pairs with a base code above 3 are chained on their bytes as chain() does (0: no anchors for them) */
+int device_chains(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		uint32_t ksz, uint32_t literal, DevChains &D){
+	if(n > 0xFFFFFFF0ull) return BSA_E_ARG;
+	const uint64_t lim = bsa_kmer_dev_max_internal();
+	std::vector<uint32_t> idx;
+	D.pos.assign(n, NONE);
+	for(size_t k = 0; k < n; k++) if((uint64_t)qlen[k] + tlen[k] <= lim){ D.pos[k] = (uint32_t)idx.size(); idx.push_back((uint32_t)k); }
+	const size_t m = idx.size();
+	D.off.assign(m + 1, 0); D.st.assign(m, 0);
+	std::vector<uint8_t> fits(m, 0);
+	const int rc = bsa_kmer_chain_dev_internal(ctx, seqs, qoff, qlen, toff, tlen, idx.data(), m, ksz, literal, &D.arena, D.off.data(), D.st.data(), fits.data(), &D.ms);
+	if(rc != BSA_OK) return rc;
+	for(size_t j = 0; j < m; j++) if(!fits[j]) D.pos[idx[j]] = NONE; else D.on_device ++;
+	D.on_host = (long)n - D.on_device;
+	bsa_ctx_set_kmer_chain_stats_internal(ctx, D.ms, D.on_device, D.on_host);
+	return BSA_OK;
+}
+} // namespace
+
+static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status){
+	if(!ctx || !maps_off || (n && (!seqs || !qoff || !qlen || !toff || !tlen)) || (maps_cap && !maps)) return BSA_E_ARG;
+	for(size_t k = 0; k < n; k++)
+		if(qoff[k] + qlen[k] > seqs_bytes || toff[k] + tlen[k] > seqs_bytes) return BSA_E_ARG;
+	if(ksz > 15) ksz = 15;
+	DevChains D;
+	if(ksz){
+		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 0, D);
+		if(rc != BSA_OK) return rc;
+	} else {
+		D.pos.assign(n, NONE);
+		bsa_ctx_set_kmer_chain_stats_internal(ctx, 0.0, 0, (long)n);
+	}
+	/* the pairs left to the host, with the same answers: no anchors for an empty pair or one with a base code above 3 */
+	std::vector<size_t> hk;
+	for(size_t k = 0; k < n; k++) if(D.pos[k] == NONE) hk.push_back(k);
+	std::vector<std::vector<uint64_t>> hmaps(hk.size());
+	std::vector<uint32_t> hst(hk.size(), 0);
+	parallel_for(hk.size(), 0, [&](size_t j){
+		const size_t k = hk[j];
+		uint8_t any = 0;
+		for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qoff[k] + i];
+		for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
+		hst[j] = (any > 3 ? BSA_ST_BAD_BASE : 0u) | ((qlen[k] == 0 || tlen[k] == 0) ? BSA_ST_EMPTY : 0u);
+		if(hst[j] || ksz == 0) return;
+		std::vector<Hit> hits;
+		chain(ksz, seqs + qoff[k], qlen[k], seqs + toff[k], tlen[k], hits);
+		hmaps[j].resize(hits.size());
+		for(size_t i = 0; i < hits.size(); i++) hmaps[j][i] = ((uint64_t)hits[i].qoff << 32) | hits[i].toff;
+	});
+	uint64_t w = 0;
+	for(size_t k = 0, j = 0; k < n; k++){
+		maps_off[k] = w;
+		if(D.pos[k] == NONE){ w += hmaps[j].size(); if(status) status[k] = hst[j]; j ++; }
+		else { w += D.off[D.pos[k] + 1] - D.off[D.pos[k]]; if(status) status[k] = D.st[D.pos[k]]; }
+	}
+	maps_off[n] = w;
+	if(w > maps_cap) return BSA_E_CIGAR_CAP;                  /* maps_off[n]: the words a retry needs */
+	for(size_t k = 0, j = 0; k < n; k++){
+		const uint64_t c = maps_off[k + 1] - maps_off[k];
+		const uint64_t *s = D.pos[k] == NONE ? hmaps[j ++].data() : D.arena + D.off[D.pos[k]];
+		if(c) memcpy(maps + maps_off[k], s, c * sizeof(uint64_t));
+	}
+	return BSA_OK;
+}
+
+extern "C" int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status){
 	try {
-		return kmer_edit_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status);
-	} catch(...){                               // host allocations (vectors, worker threads): no exception crosses the C ABI
+		return kmer_chain_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, ksz, maps, maps_cap, maps_off, status);
+	} catch(...){
 		return BSA_E_NOMEM;
 	}
 }
 
 static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status, uint32_t flags);
+
+extern "C" int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status, uint32_t flags){
+	if(flags & ~BSA_KMER_CHAIN_DEVICE) return BSA_E_ARG;
+	try {
+		return kmer_edit_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status, flags);
+	} catch(...){                               // host allocations (vectors, worker threads): no exception crosses the C ABI
+		return BSA_E_NOMEM;
+	}
+}
+
+extern "C" int bsa_kmer_edit_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status){
+	return bsa_kmer_edit_batch2(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status, 0);
+}
+
+static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status, uint32_t flags){
 	if(!ctx || !par || !out || (n && (!seqs || !qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;
 	if(par->ksz == 0) return BSA_E_ARG;
 	const uint32_t ksz = par->ksz > 15 ? 15 : par->ksz;
@@ -308,7 +408,13 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	auto now = [](){ return std::chrono::steady_clock::now(); };
 	auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b){ return std::chrono::duration<double, std::milli>(b - a).count(); };
 	auto t0 = now();
-	/* 1. chains and segment lists, threads over pairs */
+	/* 1. chains and segment lists, threads over pairs; with BSA_KMER_CHAIN_DEVICE the anchors of every pair the device route takes come from there */
+	DevChains D;
+	const bool dev = (flags & BSA_KMER_CHAIN_DEVICE) != 0;
+	if(dev){
+		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 1, D);
+		if(rc != BSA_OK) return rc;
+	}
 	std::vector<std::vector<bsa_kmer_seg_t>> segs(n);
 	std::vector<uint32_t> flag(n, 0);                      // a base code above 3 on an anchor column never reaches the device: look here
 	parallel_for(n, par->threads, [&](size_t k){
@@ -316,6 +422,13 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 		for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qoff[k] + i];
 		for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
 		if(any > 3) flag[k] = BSA_ST_BAD_BASE;
+		if(dev && D.pos[k] != NONE){
+			const uint64_t *mp = D.arena + D.off[D.pos[k]];
+			const size_t nm = (size_t)(D.off[D.pos[k] + 1] - D.off[D.pos[k]]);
+			segs[k].resize(nm + 1);
+			segs[k].resize(segments(ksz, mp, (uint32_t)nm, qlen[k], tlen[k], segs[k].data()));
+			return;
+		}
 		std::vector<Hit> hits;
 		chain(ksz, seqs + qoff[k], qlen[k], seqs + toff[k], tlen[k], hits);
 		std::vector<uint64_t> maps(hits.size());
@@ -446,6 +559,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	if(bad != BSA_OK) return bad;
 	if(timing) fprintf(stderr, "[bsa_kmer] %zu pairs: chain %.1f ms, pack %.1f ms (%zu heads and tails, %zu gaps), device %.1f ms, stitch %.1f ms\n",
 		n, ms(t0, t1), ms(t1, t2), job[0].ql.size(), job[1].ql.size(), ms(t2, t3), ms(t3, now()));
+	if(timing && dev) fprintf(stderr, "[bsa_kmer]   chained on the device: %ld pairs, kernels %.2f ms; on the host: %ld pairs\n", D.on_device, D.ms, D.on_host);
 	if(want_cig){
 		/* close the gaps left by merged match runs so that pair k owns cigar[cigar_off[k] .. cigar_off[k+1]) */
 		uint64_t w = 0;

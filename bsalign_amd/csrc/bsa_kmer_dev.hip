@@ -1,0 +1,416 @@
+// bsa_kmer_dev.hip -- the k-mer chainer of bsa_kmer.cpp (chain()) on the device: one workgroup per pair, many pairs side by side.
+//
+// The stages are those of the host code and give the same anchors word for word (tests/test_kmer_chain_gpu.py):
+//   (a) every lane rebuilds the canonical k-mer in front of its position from the ksz bytes there (no dependency between positions) and writes
+//       the host's 64-bit record  kmer << 34 | offset << 2 | from-the-target << 1 | reverse-strand-is-canonical;
+//   (b) a stable LSD radix sort of the records by k-mer, five bits a pass, between the two halves of the pair's workspace slice: every lane owns a
+//       contiguous piece of the array and a column of the 32 x 256 counter table in LDS, so neither the counting nor the scatter needs an atomic;
+//       runs of exactly two records from different sequences on the same strand are the hits (with the host's zero-sentinel quirk);
+//   (c) the hits are ordered by query offset by writing target offset + 1 at index `query offset` of a zeroed array (the keys are unique) and
+//       compacting that array in order;
+//   (d) the longest increasing subsequence over the target offsets with the reference's literal predecessor rule: a dependent chain, run by ONE
+//       lane with the tail array (index and target offset) and the first predecessors in the LDS the sort no longer needs;
+//   (e) the backward walk with the first coverage test (the same lane), then the iterated diagonal filter across the workgroup: integer sum and
+//       truncating mean, the element of rank e / 2 by bisection on the diagonal's value, var = max(3 |median - mean|, 50), until nothing is dropped;
+//       an ordered compaction and the second coverage test;
+//   (f) per-pair counts, a scan (k_kmer_scan) and a gather (k_kmer_gather) into the packed arena.
+// A byte above 3 enters the forward k-mer the way the host's rolling update lets it (OR of byte << 2 j under the mask), so that bsa_kmer_edit_batch2
+// can reproduce bsa_kmer_edit_batch on such pairs; bsa_kmer_chain_batch asks for no anchors there instead (`literal` = 0).
+#include "bsa_common.h"
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
+extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
+extern "C" size_t bsa_ctx_workspace_limit_internal(bsa_ctx_t *ctx);
+
+#define KC_THREADS   256
+#define KC_BITS      5u                  // radix digit
+#define KC_TAIL_CAP  3072u               // LIS tail entries (index, target offset) kept in LDS; longer tails go on in the slice
+#define KC_PREV_CAP  4000u               // predecessors of the first hits kept in LDS
+#define KC_LDS_WORDS (2u * KC_TAIL_CAP + KC_PREV_CAP)       // 40 KB: four workgroups a CU
+static_assert((32u * KC_THREADS) + (32u * KC_THREADS) / 32u <= KC_LDS_WORDS, "the padded counter table of the sort fits the same LDS");
+#define KC_NONE 0xFFFFFFFFu
+
+// one pair of a launch: offsets into the packed sequence bytes and into the workspace
+struct KcPair { uint64_t qoff, toff, slot; uint32_t qlen, tlen, cmin, pad; };
+
+// a pair's slice: two halves of this many bytes (each holds qlen + tlen records; what else lives there is smaller, see the kernel)
+static inline __host__ __device__ size_t kc_half_bytes(uint32_t qlen, uint32_t tlen){ return ((((size_t)qlen + tlen) * 8u + 15u) & ~(size_t)15u) + 16u; }
+
+__device__ __forceinline__ uint32_t kc_block_sum(uint32_t v, uint32_t *red){
+	for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+	__syncthreads();
+	if((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = v;
+	__syncthreads();
+	uint32_t s = 0;
+	for(uint32_t k = 0; k < KC_THREADS / 64; k++) s += red[k];
+	return s;
+}
+__device__ __forceinline__ uint32_t kc_block_excl_scan(uint32_t v, uint32_t *red, uint32_t &total){
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	uint32_t inc = v;
+	for(uint32_t o = 1; o < 64; o <<= 1){ const uint32_t t = __shfl_up(inc, o); if(lane >= o) inc += t; }
+	__syncthreads();
+	if(lane == 63) red[w] = inc;
+	__syncthreads();
+	uint32_t base = 0, tot = 0;
+	for(uint32_t k = 0; k < KC_THREADS / 64; k++){ const uint32_t x = red[k]; if(k < w) base += x; tot += x; }
+	total = tot;
+	return base + inc - v;
+}
+__device__ __forceinline__ uint32_t kc_pad(uint32_t i){ return i + (i >> 5); }        // counter table: a lane's 32 consecutive entries start in different banks
+
+__global__ __launch_bounds__(KC_THREADS) void k_kmer_chain(const uint8_t *__restrict__ seqs, const KcPair *__restrict__ pairs, uint8_t *ws, uint32_t ksz,
+		uint32_t literal, uint32_t *cnt_out, uint64_t *res_off, uint32_t *status){
+	__shared__ uint32_t lds[KC_LDS_WORDS];
+	__shared__ uint32_t red[KC_THREADS / 64];
+	__shared__ uint32_t s_flag;
+	const uint32_t tid = threadIdx.x, pair = blockIdx.x;
+	const KcPair P = pairs[pair];
+	const uint8_t *q = seqs + P.qoff, *t = seqs + P.toff;
+	const uint32_t qlen = P.qlen, tlen = P.tlen, cmin = P.cmin;
+	const uint32_t nq = qlen >= ksz ? qlen - ksz + 1u : 0u, nt = tlen >= ksz ? tlen - ksz + 1u : 0u, nrec = nq + nt;
+	const size_t half = kc_half_bytes(qlen, tlen);
+	uint64_t *src = (uint64_t*)(ws + P.slot), *dst = (uint64_t*)(ws + P.slot + half);
+
+	// base codes above 3 (the whole of both sequences, also where no k-mer fits)
+	uint32_t any = 0;
+	for(uint32_t i = tid; i < qlen; i += KC_THREADS) any |= q[i];
+	for(uint32_t i = tid; i < tlen; i += KC_THREADS) any |= t[i];
+	const uint32_t bad = __syncthreads_or(any > 3u) ? 1u : 0u;
+	const uint32_t st = (bad ? BSA_ST_BAD_BASE : 0u) | ((qlen == 0 || tlen == 0) ? BSA_ST_EMPTY : 0u);
+	if(tid == 0){ if(status) status[pair] = st; cnt_out[pair] = 0; res_off[pair] = P.slot; }
+	if(nrec == 0 || nq == 0 || nt == 0 || (bad && !literal)) return;
+
+	// (a) canonical k-mers, lanes over positions
+	{
+		const uint32_t mask = 0xFFFFFFFFu >> ((16u - ksz) << 1);
+		for(uint32_t i = tid; i < nrec; i += KC_THREADS){
+			const uint32_t flg = i >= nq, p = flg ? i - nq : i;
+			const uint8_t *s = (flg ? t : q) + p;
+			uint32_t fwd = 0, rev = 0;
+			for(uint32_t m = 0; m < ksz; m++){
+				const uint32_t b = s[m];
+				fwd |= b << ((ksz - 1u - m) << 1);
+				rev |= ((~b) & 3u) << (m << 1);
+			}
+			fwd &= mask;
+			const uint32_t dir = rev < fwd;
+			const uint64_t kmer = (dir ? rev : fwd) & 0x3FFFFFFFu;
+			src[i] = kmer << 34 | (uint64_t)p << 2 | (uint64_t)(flg << 1) | dir;
+		}
+	}
+	__syncthreads();
+
+	// (b) stable LSD radix sort on the 2 ksz k-mer bits
+	{
+		const uint32_t per = (nrec + KC_THREADS - 1u) / KC_THREADS;
+		const uint32_t b0 = min(tid * per, nrec), e0 = min(b0 + per, nrec);
+		const uint32_t passes = (2u * ksz + KC_BITS - 1u) / KC_BITS;
+		for(uint32_t p = 0; p < passes; p++){
+			const uint32_t sh = 34u + p * KC_BITS;
+			for(uint32_t d = 0; d < 32u; d++) lds[kc_pad(d * KC_THREADS + tid)] = 0;
+			for(uint32_t i = b0; i < e0; i++) lds[kc_pad((uint32_t)((src[i] >> sh) & 31u) * KC_THREADS + tid)] ++;
+			__syncthreads();
+			uint32_t sum = 0;
+			for(uint32_t j = 0; j < 32u; j++){ const uint32_t x = kc_pad(32u * tid + j), v = lds[x]; lds[x] = sum; sum += v; }
+			uint32_t total;
+			const uint32_t base = kc_block_excl_scan(sum, red, total);
+			for(uint32_t j = 0; j < 32u; j++) lds[kc_pad(32u * tid + j)] += base;
+			__syncthreads();
+			for(uint32_t i = b0; i < e0; i++){
+				const uint64_t r = src[i];
+				const uint32_t x = kc_pad((uint32_t)((r >> sh) & 31u) * KC_THREADS + tid);
+				const uint32_t w = lds[x];
+				lds[x] = w + 1u;
+				if(w < nrec) dst[w] = r;
+			}
+			__syncthreads();
+			uint64_t *sw = src; src = dst; dst = sw;
+		}
+	}
+	// src: the sorted records; dst: free
+	uint32_t *slotq = (uint32_t*)dst;
+	for(uint32_t i = tid; i < qlen; i += KC_THREADS) slotq[i] = 0;
+	__syncthreads();
+	// runs of exactly two records with different flg and equal dir; a run of k-mer 0 that reaches the end is never closed (the host's zeroed sentinel)
+	for(uint32_t i = tid; i + 1u < nrec; i += KC_THREADS){
+		const uint64_t r = src[i], r1 = src[i + 1];
+		const uint32_t k = (uint32_t)(r >> 34);
+		if((uint32_t)(r1 >> 34) != k) continue;
+		if(i > 0 && (uint32_t)(src[i - 1] >> 34) == k) continue;
+		if(i + 2u < nrec){ if((uint32_t)(src[i + 2] >> 34) == k) continue; }
+		else if(k == 0) continue;
+		if((((uint32_t)r ^ (uint32_t)r1) & 2u) == 0 || (((uint32_t)r ^ (uint32_t)r1) & 1u) != 0) continue;
+		const uint64_t kq = ((uint32_t)r & 2u) ? r1 : r, kt = ((uint32_t)r & 2u) ? r : r1;
+		const uint32_t qo = (uint32_t)(kq >> 2), to = (uint32_t)(kt >> 2);
+		if(qo < qlen) slotq[qo] = to + 1u;
+	}
+	__syncthreads();
+	// (c) the hits in query order: compact slotq into `src` (the sorted records are no longer needed)
+	uint64_t *hits = src;
+	uint32_t nh;
+	{
+		const uint32_t per = (qlen + KC_THREADS - 1u) / KC_THREADS;
+		const uint32_t b0 = min(tid * per, qlen), e0 = min(b0 + per, qlen);
+		uint32_t c = 0;
+		for(uint32_t i = b0; i < e0; i++) c += slotq[i] != 0;
+		uint32_t w = kc_block_excl_scan(c, red, nh);
+		for(uint32_t i = b0; i < e0; i++){ const uint32_t v = slotq[i]; if(v){ hits[w ++] = (uint64_t)i << 32 | (v - 1u); } }
+	}
+	__syncthreads();
+	if(nh * ksz < cmin) return;
+	// `dst` now: [out: nh u64 (the LIS tail beyond its LDS part until then)] [prev: nh u32] [keep: nh bytes] -- 13 nh <= 6.5 (qlen + tlen) bytes
+	uint64_t *outp = dst;
+	uint32_t *gtail = (uint32_t*)dst;                     // index at [m], target offset at [nh + m]
+	uint32_t *gprev = (uint32_t*)(dst + nh);
+	uint8_t  *keep  = (uint8_t*)(gprev + nh);
+	for(uint32_t i = tid; i < nh; i += KC_THREADS) keep[i] = 0;
+	__syncthreads();
+	// (d) + first half of (e): one lane
+	if(tid == 0){
+		uint32_t *tl_i = lds, *tl_v = lds + KC_TAIL_CAP, *pv = lds + 2u * KC_TAIL_CAP;
+		auto set_tail = [&](uint32_t m, uint32_t i, uint32_t v){ if(m < KC_TAIL_CAP){ tl_i[m] = i; tl_v[m] = v; } else { gtail[m] = i; gtail[nh + m] = v; } };
+		auto tail_v = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_v[m] : gtail[nh + m]; };
+		auto tail_i = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_i[m] : gtail[m]; };
+		auto set_prev = [&](uint32_t i, uint32_t v){ if(i < KC_PREV_CAP) pv[i] = v; else gprev[i] = v; };
+		auto get_prev = [&](uint32_t i){ return i < KC_PREV_CAP ? pv[i] : gprev[i]; };
+		uint32_t len = 1, first_v = (uint32_t)hits[0], last_v = first_v, last_i = 0;
+		set_tail(0, 0, first_v); set_prev(0, KC_NONE);
+		uint32_t nxt = nh > 1 ? (uint32_t)hits[1] : 0;
+		for(uint32_t i = 1; i < nh; i++){
+			const uint32_t tv = nxt;
+			if(i + 1u < nh) nxt = (uint32_t)hits[i + 1];
+			if(tv > last_v){
+				set_prev(i, last_i);
+				set_tail(len, i, tv); len ++;
+				last_v = tv; last_i = i;
+			} else if(tv <= first_v){
+				set_prev(i, KC_NONE);
+				set_tail(0, i, tv);
+				first_v = tv;
+				if(len == 1){ last_v = tv; last_i = i; }
+			} else {
+				uint32_t b = 0, e = len;
+				while(b < e){
+					const uint32_t m = b + ((e - b) >> 1), mv = tail_v(m);
+					if(tv > mv) b = m + 1;
+					else if(tv < mv) e = m;
+					else { b = m; break; }
+				}
+				if(b == 0 || b >= len) b = b == 0 ? 1 : len - 1;       // (cannot happen: first_v < tv <= last_v)
+				set_prev(i, get_prev(tail_i(b - 1)));                // as written in the reference: the predecessor of that tail, not the tail
+				set_tail(b, i, tv);
+				if(b == len - 1u){ last_v = tv; last_i = i; }
+			}
+		}
+		uint32_t cov = 0, e = KC_NONE, m = last_i;
+		while(m != KC_NONE && m < nh){
+			const uint32_t tf = (uint32_t)hits[m];
+			keep[m] = 1;
+			cov += (tf + ksz <= e) ? ksz : e - tf;
+			e = tf;
+			m = get_prev(m);
+		}
+		s_flag = cov >= cmin;
+	}
+	__syncthreads();
+	if(!s_flag) return;
+	// (e) the diagonal filter across the workgroup (a lane always looks at the same hits)
+	for(;;){
+		uint32_t e = 0, tot = 0;
+		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; tot += (uint32_t)(h >> 32) - (uint32_t)h; e ++; }
+		e = kc_block_sum(e, red);
+		tot = kc_block_sum(tot, red);
+		if(e * ksz < cmin) break;
+		const int mean = (int)tot / (int)e;
+		const uint32_t rank = e / 2u;
+		int lo = -(int)tlen, hi = (int)qlen;                    // the element of rank e / 2: the smallest v with more than `rank` diagonals <= v
+		while(lo < hi){
+			const int mid = lo + ((hi - lo) >> 1);
+			uint32_t c = 0;
+			for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; c += (int)((uint32_t)(h >> 32) - (uint32_t)h) <= mid; }
+			c = kc_block_sum(c, red);
+			if(c > rank) hi = mid; else lo = mid + 1;
+		}
+		const int median = lo;
+		const int var = max(abs(median - mean) * 3, 50);
+		uint32_t dropped = 0;
+		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){
+			const uint64_t h = hits[i];
+			const int d = (int)((uint32_t)(h >> 32) - (uint32_t)h);
+			if(abs(d - mean) > var){ keep[i] = 0; dropped ++; }
+		}
+		dropped = kc_block_sum(dropped, red);
+		if(dropped == 0) break;
+	}
+	__syncthreads();
+	// final compaction (in order) and the second coverage test
+	uint32_t w_tot;
+	{
+		const uint32_t per = (nh + KC_THREADS - 1u) / KC_THREADS;
+		const uint32_t b0 = min(tid * per, nh), e0 = min(b0 + per, nh);
+		uint32_t c = 0;
+		for(uint32_t i = b0; i < e0; i++) c += keep[i] != 0;
+		uint32_t w = kc_block_excl_scan(c, red, w_tot);
+		for(uint32_t i = b0; i < e0; i++) if(keep[i]) outp[w ++] = hits[i];
+	}
+	__syncthreads();
+	uint32_t cov = 0;
+	for(uint32_t i = tid; i < w_tot; i += KC_THREADS){
+		const uint32_t tf = (uint32_t)outp[i], e = i ? (uint32_t)outp[i - 1] + ksz : 0u;
+		cov += (tf >= e + ksz) ? ksz : tf + ksz - e;
+	}
+	cov = kc_block_sum(cov, red);
+	if(tid == 0){ cnt_out[pair] = cov < cmin ? 0u : w_tot; res_off[pair] = P.slot + (size_t)((uint8_t*)outp - (ws + P.slot)); }
+}
+
+// (f) exclusive scan of the per-pair counts (one workgroup; off has n + 1 entries) ...
+__global__ __launch_bounds__(KC_THREADS) void k_kmer_scan(const uint32_t *__restrict__ cnt, uint32_t *off, uint32_t n){
+	__shared__ uint32_t red[KC_THREADS / 64];
+	const uint32_t tid = threadIdx.x, per = (n + KC_THREADS - 1u) / KC_THREADS;
+	const uint32_t b0 = min(tid * per, n), e0 = min(b0 + per, n);
+	uint32_t c = 0, total;
+	for(uint32_t i = b0; i < e0; i++) c += cnt[i];
+	uint32_t w = kc_block_excl_scan(c, red, total);
+	for(uint32_t i = b0; i < e0; i++){ off[i] = w; w += cnt[i]; }
+	if(tid == 0) off[n] = total;
+}
+// ... and the gather of every pair's anchors into the packed arena
+__global__ __launch_bounds__(KC_THREADS) void k_kmer_gather(const uint8_t *__restrict__ ws, const uint64_t *__restrict__ res_off, const uint32_t *__restrict__ cnt,
+		const uint32_t *__restrict__ off, uint64_t *arena, uint64_t arena_cap){
+	const uint32_t pair = blockIdx.x, c = cnt[pair];
+	const uint64_t *s = (const uint64_t*)(ws + res_off[pair]);
+	const uint64_t o = off[pair];
+	for(uint32_t i = threadIdx.x; i < c; i += KC_THREADS) if(o + i < arena_cap) arena[o + i] = s[i];
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------------------
+// the largest pair the device route takes (qlen + tlen); longer pairs are chained by the host code in the same call
+extern "C" uint32_t bsa_kmer_dev_max_internal(void){ return 1u << 18; }
+
+static inline size_t kc_up(size_t x){ return (x + 255u) & ~(size_t)255u; }
+static uint32_t kc_min_cover(uint32_t qlen, uint32_t tlen, uint32_t ksz){       // bsa_kmer.cpp: min_cover (double arithmetic on the host, as there)
+	uint32_t c = (uint32_t)(std::min(qlen, tlen) * 0.05 + 1);
+	return std::min(c, 2 * ksz);
+}
+// what one pair needs of the scratch: its slice, its packed bytes, its share of the arena and of the tables
+static size_t kc_pair_bytes(uint32_t qlen, uint32_t tlen){
+	return 2u * kc_half_bytes(qlen, tlen) + 256u + ((size_t)qlen + tlen) + 8u * (size_t)std::min(qlen, tlen) + sizeof(KcPair) + 32u;
+}
+
+// Chains the pairs idx[0 .. m) on the device.  *arena_out (malloc'd, the caller frees it) holds their anchors packed, those of idx[j] at off[j] .. off[j + 1);
+// st (m entries, may be NULL) gets BSA_ST_EMPTY / BSA_ST_BAD_BASE; fits[j] = 0 marks a pair that alone is larger than the workspace (left to the host, no anchors
+// here).  *ms: the kernels' time by HIP events.
+extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms){
+	*arena_out = nullptr; *ms = 0.0;
+	off[0] = 0;
+	if(ksz > 15) ksz = 15;
+	if(m == 0) return BSA_OK;
+	hipStream_t stream;
+	int rc = bsa_ctx_get_stream_internal(ctx, &stream);
+	if(rc != BSA_OK) return rc;
+	size_t budget = bsa_ctx_workspace_limit_internal(ctx);
+	if(budget == 0){
+		size_t fr = 0, tot = 0;
+		budget = (size_t)2 << 30;
+		if(hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::min(budget, fr / 2);
+	}
+	budget = budget > 4096 ? budget - 4096 : 0;
+	std::vector<uint64_t> arena;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	if(hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess){ if(ev0) (void)hipEventDestroy(ev0); return BSA_E_HIP; }
+	std::vector<KcPair> meta;
+	std::vector<uint8_t> pack;
+	std::vector<uint32_t> h_off, h_st;
+	rc = BSA_OK;
+	size_t j0 = 0;
+	while(j0 < m && rc == BSA_OK){
+		// the chunk [j0, j1): as many pairs as the budget holds; a pair that does not fit alone is left to the caller
+		size_t j1 = j0, bytes = 0, seqb = 0, slots = 0, acap = 0;
+		meta.clear();
+		while(j1 < m){
+			const uint32_t k = idx[j1], ql = qlen[k], tl = tlen[k];
+			const size_t need = kc_pair_bytes(ql, tl);
+			if(need > budget){
+				if(j1 > j0) break;                    // close the chunk in front of it
+				fits[j1] = 0; off[j1 + 1] = off[j1]; if(st) st[j1] = 0;
+				j0 = ++j1; continue;
+			}
+			if(bytes + need > budget || acap + std::min(ql, tl) > 0x7FFFFFF0ull || meta.size() >= 0x7FFFFFF0ull) break;
+			fits[j1] = 1;
+			KcPair P; P.qoff = seqb; P.toff = seqb + ql; P.slot = slots; P.qlen = ql; P.tlen = tl; P.cmin = kc_min_cover(ql, tl, ksz); P.pad = 0;
+			meta.push_back(P);
+			seqb += (size_t)ql + tl; slots += 2u * kc_half_bytes(ql, tl); acap += std::min(ql, tl); bytes += need;
+			j1 ++;
+		}
+		const size_t c = meta.size();
+		if(c == 0) continue;
+		// pack the chunk's sequences (the caller's blob may be far larger than what these pairs use)
+		pack.resize(seqb);
+		{
+			const unsigned nth = seqb > ((size_t)4 << 20) ? 8u : 1u;
+			auto body = [&](size_t a, size_t b){
+				for(size_t j = a; j < b; j++){
+					const uint32_t k = idx[j0 + j];
+					if(meta[j].qlen) memcpy(pack.data() + meta[j].qoff, seqs + qoff[k], meta[j].qlen);
+					if(meta[j].tlen) memcpy(pack.data() + meta[j].toff, seqs + toff[k], meta[j].tlen);
+				}
+			};
+			if(nth == 1) body(0, c);
+			else {
+				std::vector<std::thread> pool;
+				for(unsigned w = 0; w < nth; w++) pool.emplace_back(body, c * w / nth, c * (w + 1) / nth);
+				for(auto &th : pool) th.join();
+			}
+		}
+		// carve the scratch
+		size_t o = 0;
+		const size_t o_seq = o;  o += kc_up(seqb + 16);
+		const size_t o_meta = o; o += kc_up(c * sizeof(KcPair));
+		const size_t o_cnt = o;  o += kc_up(c * 4);
+		const size_t o_off = o;  o += kc_up((c + 1) * 4);
+		const size_t o_st = o;   o += kc_up(c * 4);
+		const size_t o_res = o;  o += kc_up(c * 8);
+		const size_t o_ar = o;   o += kc_up((acap + 1) * 8);
+		const size_t o_ws = o;   o += kc_up(slots + 16);
+		void *bufv = nullptr;
+		if((rc = bsa_ctx_scratch_internal(ctx, 1, o, &bufv)) != BSA_OK) break;
+		uint8_t *buf = (uint8_t*)bufv;
+		auto hip_ok = [&](hipError_t e){ if(e != hipSuccess){ rc = BSA_E_HIP; return false; } return true; };
+		if(seqb && !hip_ok(hipMemcpyAsync(buf + o_seq, pack.data(), seqb, hipMemcpyHostToDevice, stream))) break;
+		if(!hip_ok(hipMemcpyAsync(buf + o_meta, meta.data(), c * sizeof(KcPair), hipMemcpyHostToDevice, stream))) break;
+		if(!hip_ok(hipEventRecord(ev0, stream))) break;
+		hipLaunchKernelGGL(k_kmer_chain, dim3((uint32_t)c), dim3(KC_THREADS), 0, stream, (const uint8_t*)(buf + o_seq), (const KcPair*)(buf + o_meta), buf + o_ws, ksz, literal,
+			(uint32_t*)(buf + o_cnt), (uint64_t*)(buf + o_res), (uint32_t*)(buf + o_st));
+		hipLaunchKernelGGL(k_kmer_scan, dim3(1), dim3(KC_THREADS), 0, stream, (const uint32_t*)(buf + o_cnt), (uint32_t*)(buf + o_off), (uint32_t)c);
+		hipLaunchKernelGGL(k_kmer_gather, dim3((uint32_t)c), dim3(KC_THREADS), 0, stream, (const uint8_t*)(buf + o_ws), (const uint64_t*)(buf + o_res), (const uint32_t*)(buf + o_cnt),
+			(const uint32_t*)(buf + o_off), (uint64_t*)(buf + o_ar), (uint64_t)acap);
+		if(!hip_ok(hipGetLastError()) || !hip_ok(hipEventRecord(ev1, stream))) break;
+		h_off.resize(c + 1); h_st.resize(c);
+		if(!hip_ok(hipMemcpyAsync(h_off.data(), buf + o_off, (c + 1) * 4, hipMemcpyDeviceToHost, stream))) break;
+		if(!hip_ok(hipMemcpyAsync(h_st.data(), buf + o_st, c * 4, hipMemcpyDeviceToHost, stream))) break;
+		if(!hip_ok(hipStreamSynchronize(stream))) break;
+		const size_t tot = h_off[c];
+		if(tot > acap){ rc = BSA_E_HIP; break; }                 // (cannot happen: a pair has at most min(qlen, tlen) anchors)
+		const size_t at = arena.size();
+		arena.resize(at + tot);
+		if(tot && !hip_ok(hipMemcpy(arena.data() + at, buf + o_ar, tot * 8, hipMemcpyDeviceToHost))) break;
+		float t = 0;
+		if(hip_ok(hipEventElapsedTime(&t, ev0, ev1))) *ms += t;
+		for(size_t j = 0; j < c; j++){ off[j0 + j + 1] = at + h_off[j + 1]; if(st) st[j0 + j] = h_st[j]; }
+		j0 = j1;
+	}
+	(void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+	if(rc != BSA_OK){ (void)hipGetLastError(); return rc; }
+	uint64_t *a = (uint64_t*)malloc((arena.size() + 1) * sizeof(uint64_t));
+	if(!a) return BSA_E_NOMEM;
+	if(!arena.empty()) memcpy(a, arena.data(), arena.size() * sizeof(uint64_t));
+	*arena_out = a;
+	return BSA_OK;
+}

@@ -178,7 +178,8 @@ extern "C" {
 #define BSA_E_ARG        (-2)   /* invalid argument (NULL pointer, bad mode, W == 0 ...) */
 #define BSA_E_NOMEM      (-3)   /* device allocation failed / workspace limit too small for one pair */
 #define BSA_E_HIP        (-4)   /* a HIP call failed (see bsa_last_error) */
-#define BSA_E_CIGAR_CAP  (-5)   /* cigar arena too small; cigar_off[n] holds the required number of words */
+#define BSA_E_CIGAR_CAP  (-5)   /* cigar arena too small; cigar_off[n] holds the required number of words.  Second use: bsa_kmer_chain_batch with
+                                   an anchor arena that is too small (maps_cap); maps_off[n] then holds the required number of 64-bit words */
 #define BSA_E_UNSUPPORTED (-6)  /* parameter combination not implemented on the device yet */
 
 /* per-pair status bits written to the optional status array */
@@ -239,6 +240,9 @@ int         bsa_ctx_last_margin_ms(bsa_ctx_t *ctx, double *ms, long *launches);
  * (the hand-over described at bsa_align_batch; with scores outside the static guard: the pairs the checked whole-query
  * kernel flagged) */
 long        bsa_ctx_last_handover(bsa_ctx_t *ctx);
+/* the device k-mer chainer in the last bsa_kmer_chain_batch / bsa_kmer_edit_batch2(BSA_KMER_CHAIN_DEVICE) call: time of its kernels (HIP events on the
+ * context stream, summed over the workspace chunks), pairs it chained and pairs the host chained in the same call (any pointer may be NULL) */
+int         bsa_ctx_last_kmer_chain_ms(bsa_ctx_t *ctx, double *ms, long *pairs_on_device, long *pairs_on_host);
 void        bsa_set_score_matrix(int8_t matrix[16], int8_t mat, int8_t mis);   /* bsalign.h:323 */
 
 /* ---- 8-bit banded striped pairwise alignment (A-rows) ------------------------------------------
@@ -329,6 +333,40 @@ uint32_t bsa_kmer_chain(uint32_t ksz, const uint8_t *q, uint32_t qlen, const uin
 uint32_t bsa_kmer_segments(uint32_t ksz, const uint64_t *maps, uint32_t kmap, uint32_t qlen, uint32_t tlen, bsa_kmer_seg_t *segs);
 int      bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, const bsa_result_t *seg_out, const uint32_t *seg_cigar,
                            const uint64_t *seg_cigar_off, bsa_result_t *out, uint32_t *cigar, uint64_t cigar_cap_words, uint64_t *cigar_words);
+
+/* bsa_kmer_chain_batch: the anchors of n pairs, chained on the DEVICE (bsa_kmer_dev.hip: one workgroup a pair -- k-mer extraction, radix sort, unique
+ *                    same-strand hits, longest increasing subsequence, diagonal filter, both coverage tests).  All pointers are HOST memory (uploads,
+ *                    runs, downloads, synchronises).  Pair k's anchors are maps[maps_off[k] .. maps_off[k + 1]) in query order, maps[i] = query
+ *                    offset << 32 | target offset: exactly the count and the words bsa_kmer_chain(ksz, q, qlen, t, tlen, ...) returns for that pair.
+ *                    Example: q = t = 100 random bases, ksz 13: up to 88 anchors i << 32 | i (those of k-mers that occur once).
+ *                    0 anchors = align the whole pair globally.  ksz above 15 means 15; ksz == 0 or a sequence shorter than ksz: no anchors.
+ *                    status (may be NULL): BSA_ST_EMPTY for qlen == 0 or tlen == 0, BSA_ST_BAD_BASE for a base code above 3; both get no anchors
+ *                    (bsa_kmer_chain would chain the bytes of a bad-base pair; bsa_kmer_edit_batch2 does that, see below).
+ *                    maps_cap (64-bit words) too small: BSA_E_CIGAR_CAP, maps_off[n] = the words needed, maps untouched; n = 0 is fine.
+ *                    The device route takes every pair with qlen + tlen <= 262144; a longer pair, or one whose slice (about 17 bytes a base)
+ *                    exceeds bsa_ctx_set_workspace_limit, is chained by the host code inside the same call -- same words, the caller sees no
+ *                    difference but bsa_ctx_last_kmer_chain_ms.  Pairs go in chunks when the workspace does not hold them all.
+ *                    Takes 1 B/base blobs only: no BSA_MODE_SEQ2BIT, BSA_MODE_QSTRAND marks or device pointers. */
+int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+                         const uint64_t *qoff, const uint32_t *qlen,
+                         const uint64_t *toff, const uint32_t *tlen, size_t n,
+                         uint32_t ksz, uint64_t *maps, size_t maps_cap,
+                         uint64_t *maps_off /* n + 1 */, uint32_t *status /* may be NULL */);
+
+#define BSA_KMER_CHAIN_DEVICE 1u    /* flag of bsa_kmer_edit_batch2: step 1 of the batch (chains, then segment lists) takes its anchors from the device
+                                       chainer above instead of the host threads.  Records, CIGAR words, cigar_off and status are bit-identical to
+                                       bsa_kmer_edit_batch for ANY input: a pair with a base code above 3 is chained on its bytes exactly as the host
+                                       code does, an empty pair has no anchors either way, and a pair above the device route's size limit is chained
+                                       by the host inside the call.  bsa_kmer_segments, the two edit batches and bsa_kmer_assemble are the same code.
+                                       Example: bsa_kmer_edit_batch2(ctx, ..., &par, out, cigar, cap, cigar_off, status, BSA_KMER_CHAIN_DEVICE).
+                                       flags == 0 IS bsa_kmer_edit_batch (which calls this function with 0); any other bit is BSA_E_ARG.  Does not
+                                       combine with the BSA_MODE_* flags of the align and edit calls: the kmer calls take none of them. */
+int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+                         const uint64_t *qoff, const uint32_t *qlen,
+                         const uint64_t *toff, const uint32_t *tlen, size_t n,
+                         const bsa_kmer_params_t *par,
+                         bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
+                         uint64_t *cigar_off, uint32_t *status, uint32_t flags);
 
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
