@@ -160,6 +160,8 @@ def lib():
                                            vp, u32p, C.c_size_t, u64p, u32p, C.c_uint32]
         L.bsa_kmer_chain_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.c_uint32,
                                            u64p, C.c_size_t, u64p, u32p]
+        L.bsa_kmer_chain_batch2.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.c_uint32,
+                                            u64p, C.c_size_t, u64p, u32p, C.c_uint32]
         L.bsa_ctx_last_kmer_chain_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long)]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
@@ -536,27 +538,36 @@ class Context:
         self._chk(lib().bsa_seq_pack2bit(self.h, C.c_void_p(d_codes.data_ptr()), n, C.c_void_p(d_bits.data_ptr()),
                                          C.c_void_p(d_bad.data_ptr() if d_bad is not None else 0)))
 
-    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None, device_chain=False):
+    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None, device_chain=False, seq2bit=False, strands=None):
         """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch;
-        device_chain: the anchors come from the device chainer (bsa_kmer_edit_batch2 with KMER_CHAIN_DEVICE), same results"""
+        device_chain: the anchors come from the device chainer (bsa_kmer_edit_batch2 with KMER_CHAIN_DEVICE), same results;
+        seq2bit / strands as in edit_batch (bsa_kmer_edit_batch2 with MODE_SEQ2BIT / MODE_QSTRAND in its flags): the queries are stored as
+        given and pair k aligns revcomp(q) where strands[k] is true"""
         p = KmerParams()
         p.ksz, p.threads = ksz, threads
-        if not device_chain:
+        flags = (KMER_CHAIN_DEVICE if device_chain else 0) | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        if not flags:
             return self._batch(lib().bsa_kmer_edit_batch, pairs, p, cigar_cap)
         fn = lib().bsa_kmer_edit_batch2
-        return self._batch(lambda *a: fn(*a, KMER_CHAIN_DEVICE), pairs, p, cigar_cap)
+        return self._batch(lambda *a: fn(*a, flags), pairs, p, cigar_cap, seq2bit, strands)
 
-    def kmer_chain_batch(self, pairs, ksz=13, with_status=False):
+    def kmer_chain_batch(self, pairs, ksz=13, with_status=False, seq2bit=False, strands=None):
         """bsa_kmer_chain_batch: the anchors of every pair (query offset << 32 | target offset, in query order) as a list of uint64 arrays,
-        chained on the device; with_status: (anchors, status) -- ST_EMPTY / ST_BAD_BASE pairs have none"""
-        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs)
+        chained on the device; with_status: (anchors, status) -- ST_EMPTY / ST_BAD_BASE pairs have none.  seq2bit / strands as in edit_batch
+        (bsa_kmer_chain_batch2): where strands[k] is true the anchors are those of revcomp(q) against t, query offsets in revcomp(q)"""
+        seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, strands)
         n = len(pairs)
         cap = int(np.minimum(qlen, tlen).sum()) + 1
         maps = np.zeros(cap, dtype=np.uint64)
         off = np.zeros(n + 1, dtype=np.uint64)
         status = np.zeros(max(n, 1), dtype=np.uint32)
-        self._chk(lib().bsa_kmer_chain_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
-                                             _p(maps), cap, _p(off), _p(status)))
+        flags = (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        if flags:
+            self._chk(lib().bsa_kmer_chain_batch2(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
+                                                  _p(maps), cap, _p(off), _p(status), flags))
+        else:
+            self._chk(lib().bsa_kmer_chain_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
+                                                 _p(maps), cap, _p(off), _p(status)))
         res = [maps[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
         return (res, status[:n]) if with_status else res
 

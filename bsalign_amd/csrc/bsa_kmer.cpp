@@ -260,6 +260,41 @@ template <typename F> void parallel_for(size_t n, unsigned threads, F body){
 	if(failed.load()) throw std::bad_alloc();  // re-raised on the calling thread, mapped to BSA_E_NOMEM by the entry points
 }
 
+/* The caller's blob as the flags of the batch calls describe it: one base per byte, or BSA_MODE_SEQ2BIT words (32 bases a word from the top bits down,
+ * base offsets); with BSA_MODE_QSTRAND bit 63 of qoff[k] marks a pair that aligns q', q'[i] = 3 - q[qlen - 1 - i].  Workers decode what they need of
+ * ONE pair into their own buffers; the blob is never copied as a whole. */
+struct Blob {
+	const uint8_t *seqs; bool packed, strand;
+	bool plain() const { return !packed && !strand; }
+	uint64_t qo(uint64_t raw) const { return strand ? raw & ~BSA_QOFF_REVCOMP : raw; }
+	bool marked(uint64_t raw) const { return strand && (raw & BSA_QOFF_REVCOMP) != 0; }
+	uint8_t at(uint64_t o) const {                          /* the stored base at offset o */
+		if(!packed) return seqs[o];
+		uint64_t w;
+		memcpy(&w, seqs + (o >> 5) * 8, 8);
+		return (uint8_t)((w >> (62 - 2 * (o & 31))) & 3);
+	}
+	void stored(uint64_t o, uint32_t b, uint32_t e, uint8_t *dst) const {      /* bases [b, e) of the sequence stored at o */
+		if(!packed){ if(e > b) memcpy(dst, seqs + o + b, e - b); return; }
+		for(uint32_t i = b; i < e; i++) *dst ++ = at(o + i);
+	}
+	void query(uint64_t raw, uint32_t qlen, uint32_t b, uint32_t e, uint8_t *dst) const {      /* bases [b, e) of the query the pair aligns */
+		const uint64_t o = qo(raw);
+		if(!marked(raw)){ stored(o, b, e, dst); return; }
+		for(uint32_t i = b; i < e; i++) *dst ++ = (uint8_t)(3 - at(o + qlen - 1 - i));
+	}
+};
+const uint32_t SEQ_FLAGS = BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND;
+
+/* every pair inside the blob; a SEQ2BIT blob is whole words */
+bool blob_args_ok(const Blob &B, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n){
+	if(B.packed && (seqs_bytes & 7)) return false;
+	const uint64_t lim = B.packed ? (uint64_t)seqs_bytes * 4 : (uint64_t)seqs_bytes;
+	for(size_t k = 0; k < n; k++)
+		if(B.qo(qoff[k]) + qlen[k] > lim || toff[k] + tlen[k] > lim) return false;
+	return true;
+}
+
 } // namespace
 
 extern "C" uint32_t bsa_kmer_chain(uint32_t ksz, const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, uint64_t *maps, uint32_t cap){
@@ -285,7 +320,7 @@ extern "C" int bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, cons
 /* the device chainer (bsa_kmer_dev.hip) and the context's record of what the last chaining did (bsa_api.hip) */
 extern "C" uint32_t bsa_kmer_dev_max_internal(void);
 extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms);
+		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint32_t flags, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms);
 extern "C" void bsa_ctx_set_kmer_chain_stats_internal(bsa_ctx_t *ctx, double ms, long on_device, long on_host);
 
 namespace {
@@ -301,7 +336,7 @@ struct DevChains {
 };
 /* literal: pairs with a base code above 3 are chained on their bytes as chain() does (0: no anchors for them) */
 int device_chains(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
-		uint32_t ksz, uint32_t literal, DevChains &D){
+		uint32_t ksz, uint32_t literal, uint32_t flags, DevChains &D){
 	if(n > 0xFFFFFFF0ull) return BSA_E_ARG;
 	const uint64_t lim = bsa_kmer_dev_max_internal();
 	std::vector<uint32_t> idx;
@@ -310,7 +345,7 @@ int device_chains(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, con
 	const size_t m = idx.size();
 	D.off.assign(m + 1, 0); D.st.assign(m, 0);
 	std::vector<uint8_t> fits(m, 0);
-	const int rc = bsa_kmer_chain_dev_internal(ctx, seqs, qoff, qlen, toff, tlen, idx.data(), m, ksz, literal, &D.arena, D.off.data(), D.st.data(), fits.data(), &D.ms);
+	const int rc = bsa_kmer_chain_dev_internal(ctx, seqs, qoff, qlen, toff, tlen, idx.data(), m, ksz, literal, flags & SEQ_FLAGS, &D.arena, D.off.data(), D.st.data(), fits.data(), &D.ms);
 	if(rc != BSA_OK) return rc;
 	for(size_t j = 0; j < m; j++) if(!fits[j]) D.pos[idx[j]] = NONE; else D.on_device ++;
 	D.on_host = (long)n - D.on_device;
@@ -320,14 +355,14 @@ int device_chains(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, con
 } // namespace
 
 static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status){
+		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status, uint32_t flags){
 	if(!ctx || !maps_off || (n && (!seqs || !qoff || !qlen || !toff || !tlen)) || (maps_cap && !maps)) return BSA_E_ARG;
-	for(size_t k = 0; k < n; k++)
-		if(qoff[k] + qlen[k] > seqs_bytes || toff[k] + tlen[k] > seqs_bytes) return BSA_E_ARG;
+	const Blob B = { seqs, (flags & BSA_MODE_SEQ2BIT) != 0, (flags & BSA_MODE_QSTRAND) != 0 };
+	if(!blob_args_ok(B, seqs_bytes, qoff, qlen, toff, tlen, n)) return BSA_E_ARG;
 	if(ksz > 15) ksz = 15;
 	DevChains D;
 	if(ksz){
-		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 0, D);
+		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 0, flags, D);
 		if(rc != BSA_OK) return rc;
 	} else {
 		D.pos.assign(n, NONE);
@@ -340,13 +375,21 @@ static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
 	std::vector<uint32_t> hst(hk.size(), 0);
 	parallel_for(hk.size(), 0, [&](size_t j){
 		const size_t k = hk[j];
+		const uint64_t qo = B.qo(qoff[k]);
 		uint8_t any = 0;
-		for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qoff[k] + i];
-		for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
+		if(!B.packed){
+			for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qo + i];
+			for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
+		}
 		hst[j] = (any > 3 ? BSA_ST_BAD_BASE : 0u) | ((qlen[k] == 0 || tlen[k] == 0) ? BSA_ST_EMPTY : 0u);
 		if(hst[j] || ksz == 0) return;
 		std::vector<Hit> hits;
-		chain(ksz, seqs + qoff[k], qlen[k], seqs + toff[k], tlen[k], hits);
+		if(B.packed || B.marked(qoff[k])){                  /* this pair's bases as the call aligns them, one per byte */
+			std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
+			B.query(qoff[k], qlen[k], 0, qlen[k], own.data());
+			B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
+			chain(ksz, own.data(), qlen[k], own.data() + qlen[k], tlen[k], hits);
+		} else chain(ksz, seqs + qo, qlen[k], seqs + toff[k], tlen[k], hits);
 		hmaps[j].resize(hits.size());
 		for(size_t i = 0; i < hits.size(); i++) hmaps[j][i] = ((uint64_t)hits[i].qoff << 32) | hits[i].toff;
 	});
@@ -366,13 +409,19 @@ static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
 	return BSA_OK;
 }
 
-extern "C" int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status){
+extern "C" int bsa_kmer_chain_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status, uint32_t flags){
+	if(flags & ~SEQ_FLAGS) return BSA_E_ARG;
 	try {
-		return kmer_chain_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, ksz, maps, maps_cap, maps_off, status);
+		return kmer_chain_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, ksz, maps, maps_cap, maps_off, status, flags);
 	} catch(...){
 		return BSA_E_NOMEM;
 	}
+}
+
+extern "C" int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status){
+	return bsa_kmer_chain_batch2(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, ksz, maps, maps_cap, maps_off, status, 0);
 }
 
 static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
@@ -382,7 +431,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 extern "C" int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status, uint32_t flags){
-	if(flags & ~BSA_KMER_CHAIN_DEVICE) return BSA_E_ARG;
+	if(flags & ~(BSA_KMER_CHAIN_DEVICE | SEQ_FLAGS)) return BSA_E_ARG;
 	try {
 		return kmer_edit_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status, flags);
 	} catch(...){                               // host allocations (vectors, worker threads): no exception crosses the C ABI
@@ -402,8 +451,8 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	if(!ctx || !par || !out || (n && (!seqs || !qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;
 	if(par->ksz == 0) return BSA_E_ARG;
 	const uint32_t ksz = par->ksz > 15 ? 15 : par->ksz;
-	for(size_t k = 0; k < n; k++)
-		if(qoff[k] + qlen[k] > seqs_bytes || toff[k] + tlen[k] > seqs_bytes) return BSA_E_ARG;
+	const Blob B = { seqs, (flags & BSA_MODE_SEQ2BIT) != 0, (flags & BSA_MODE_QSTRAND) != 0 };
+	if(!blob_args_ok(B, seqs_bytes, qoff, qlen, toff, tlen, n)) return BSA_E_ARG;
 	const bool timing = getenv("BSA_KMER_TIMING") != nullptr;          /* phase times on stderr */
 	auto now = [](){ return std::chrono::steady_clock::now(); };
 	auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b){ return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -412,15 +461,19 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	DevChains D;
 	const bool dev = (flags & BSA_KMER_CHAIN_DEVICE) != 0;
 	if(dev){
-		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 1, D);
+		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 1, flags, D);
 		if(rc != BSA_OK) return rc;
 	}
 	std::vector<std::vector<bsa_kmer_seg_t>> segs(n);
 	std::vector<uint32_t> flag(n, 0);                      // a base code above 3 on an anchor column never reaches the device: look here
 	parallel_for(n, par->threads, [&](size_t k){
+		const uint64_t qo = B.qo(qoff[k]);
 		uint8_t any = 0;
-		for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qoff[k] + i];
-		for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
+		if(!B.packed){
+			for(uint32_t i = 0; i < qlen[k]; i++) any |= seqs[qo + i];
+			if(any > 3 && B.marked(qoff[k])){ flag[k] = BSA_ST_BAD_BASE; return; }      /* no q': no segments -- an all-zero record and no CIGAR words */
+			for(uint32_t i = 0; i < tlen[k]; i++) any |= seqs[toff[k] + i];
+		}
 		if(any > 3) flag[k] = BSA_ST_BAD_BASE;
 		if(dev && D.pos[k] != NONE){
 			const uint64_t *mp = D.arena + D.off[D.pos[k]];
@@ -430,7 +483,12 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 			return;
 		}
 		std::vector<Hit> hits;
-		chain(ksz, seqs + qoff[k], qlen[k], seqs + toff[k], tlen[k], hits);
+		if(B.packed || B.marked(qoff[k])){                  /* this pair's bases as the call aligns them, one per byte */
+			std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
+			B.query(qoff[k], qlen[k], 0, qlen[k], own.data());
+			B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
+			chain(ksz, own.data(), qlen[k], own.data() + qlen[k], tlen[k], hits);
+		} else chain(ksz, seqs + qo, qlen[k], seqs + toff[k], tlen[k], hits);
 		std::vector<uint64_t> maps(hits.size());
 		for(size_t i = 0; i < hits.size(); i++) maps[i] = ((uint64_t)hits[i].qoff << 32) | hits[i].toff;
 		segs[k].resize(hits.size() + 1);
@@ -474,7 +532,16 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 				const int w = ((s.mode & 3) == BSA_MODE_GLOBAL) ? 1 : 0;
 				Job &J = job[w];
 				size_t &ix = w ? i1 : i0;
-				if(w == 0){
+				if(w == 0 && !B.plain()){
+					/* decoded bases of q' (or q) and t; a reversed head of a marked pair is the complement of stored bases [qlen - qe, qlen) in forward order */
+					uint8_t *hq = heads.data() + base, *ht = hq + ql;
+					B.query(qoff[k], qlen[k], s.qb, s.qe, hq);
+					B.stored(toff[k], s.tb, s.te, ht);
+					if(s.mode & BSA_KMER_SEG_REVERSED){ std::reverse(hq, hq + ql); std::reverse(ht, ht + tl); }
+					J.qo[ix] = base; J.to[ix] = base + ql;
+					base += (size_t)ql + tl;
+					cap0 += (size_t)ql + tl + 2;
+				} else if(w == 0){
 					if(s.mode & BSA_KMER_SEG_REVERSED){
 						std::reverse_copy(seqs + qoff[k], seqs + qoff[k] + s.qe, heads.begin() + base);
 						std::reverse_copy(seqs + toff[k], seqs + toff[k] + s.te, heads.begin() + base + ql);
@@ -486,7 +553,9 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 					base += (size_t)ql + tl;
 					cap0 += (size_t)ql + tl + 2;
 				} else {
-					J.qo[ix] = qoff[k] + s.qb; J.to[ix] = toff[k] + s.tb;
+					/* a view into the caller's blob: q'[qb, qe) of a marked pair is the reverse complement of stored bases [qlen - qe, qlen - qb) */
+					J.qo[ix] = B.marked(qoff[k]) ? ((B.qo(qoff[k]) + qlen[k] - s.qe) | BSA_QOFF_REVCOMP) : B.qo(qoff[k]) + s.qb;
+					J.to[ix] = toff[k] + s.tb;
 					cap1 += (size_t)ql + tl + 2;
 				}
 				J.ql[ix] = ql; J.tl[ix] = tl;
@@ -505,7 +574,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 		if(m == 0) continue;
 		J.rs.resize(m); J.cig.reset(new uint32_t[J.cap]); J.coff.resize(m + 1); J.st.assign(m, 0);       // the arena is not zero-filled
 		bsa_edit_params_t ep;
-		ep.mode = (w == 1) ? BSA_MODE_GLOBAL : BSA_MODE_EXTEND;
+		ep.mode = (w == 1) ? (int32_t)(BSA_MODE_GLOBAL | (flags & SEQ_FLAGS)) : BSA_MODE_EXTEND;
 		ep.bandwidth = 0;
 		const uint8_t *blob = (w == 0) ? heads.data() : seqs;
 		const size_t bytes = (w == 0) ? heads.size() : seqs_bytes;

@@ -16,6 +16,15 @@
 //   (f) per-pair counts, a scan (k_kmer_scan) and a gather (k_kmer_gather) into the packed arena.
 // A byte above 3 enters the forward k-mer the way the host's rolling update lets it (OR of byte << 2 j under the mask), so that bsa_kmer_edit_batch2
 // can reproduce bsa_kmer_edit_batch on such pairs; bsa_kmer_chain_batch asks for no anchors there instead (`literal` = 0).
+//
+// BSA_MODE_SEQ2BIT / BSA_MODE_QSTRAND (bsa_kmer_chain_batch2, bsa_kmer_edit_batch2): k_kmer_chain<PK, QS> -- only the bad-base scan and stage (a) differ,
+// everything from the sort on reads the same records.  <false, false> is the kernel without flags, statement for statement.
+//   QS  a marked query stands for q', q'[i] = 3 - q[qlen - 1 - i]: the k-mer of q' at position p is the reverse complement of the stored k-mer at
+//       nq - 1 - p, so the lane reads the mirrored position and swaps the roles of its two k-mers.  A marked query with a code above 3 has no q':
+//       BSA_ST_BAD_BASE and no anchors, whatever `literal` says.
+//   PK  the sequences are 2-bit words, 32 bases each from the top bit down (bsa_common.h), offsets are base offsets: the forward k-mer comes from the
+//       one or two words that hold it (funnel shift), its reverse complement from a bit reversal with the bits of each pair swapped back -- no
+//       loop over bases, no bad-base scan, no word read that holds no base of the read.
 #include "bsa_common.h"
 #include <algorithm>
 #include <cstdlib>
@@ -36,7 +45,7 @@ static_assert((32u * KC_THREADS) + (32u * KC_THREADS) / 32u <= KC_LDS_WORDS, "th
 #define KC_NONE 0xFFFFFFFFu
 
 // one pair of a launch: offsets into the packed sequence bytes and into the workspace
-struct KcPair { uint64_t qoff, toff, slot; uint32_t qlen, tlen, cmin, pad; };
+struct KcPair { uint64_t qoff, toff, slot; uint32_t qlen, tlen, cmin, rc; };       // rc: the query is marked (QS kernels only)
 
 // a pair's slice: two halves of this many bytes (each holds qlen + tlen records; what else lives there is smaller, see the kernel)
 static inline __host__ __device__ size_t kc_half_bytes(uint32_t qlen, uint32_t tlen){ return ((((size_t)qlen + tlen) * 8u + 15u) & ~(size_t)15u) + 16u; }
@@ -64,6 +73,22 @@ __device__ __forceinline__ uint32_t kc_block_excl_scan(uint32_t v, uint32_t *red
 }
 __device__ __forceinline__ uint32_t kc_pad(uint32_t i){ return i + (i >> 5); }        // counter table: a lane's 32 consecutive entries start in different banks
 
+// the 2 ksz bits (ksz <= 15) of a packed sequence from base offset o on; the second word is read only where the k-mer reaches into it
+__device__ __forceinline__ uint32_t kc_kmer2bit(const uint64_t *__restrict__ W, uint64_t o, uint32_t ksz){
+	const uint64_t wi = o >> 5;
+	const uint32_t s = ((uint32_t)o & 31u) << 1;
+	uint64_t x = W[wi] << s;
+	if(s + 2u * ksz > 64u) x |= W[wi + 1] >> (64u - s);           // (s > 0 here)
+	return (uint32_t)(x >> (64u - 2u * ksz));
+}
+// reverse complement of a k-mer: the 2-bit groups in reverse order (bit reversal, then the two bits of every group swapped back), complemented
+__device__ __forceinline__ uint32_t kc_revcomp2bit(uint32_t fwd, uint32_t ksz){
+	uint32_t r = __brev(fwd);
+	r = ((r & 0xAAAAAAAAu) >> 1) | ((r & 0x55555555u) << 1);
+	return (~r) >> ((16u - ksz) << 1);
+}
+
+template <bool PK, bool QS>
 __global__ __launch_bounds__(KC_THREADS) void k_kmer_chain(const uint8_t *__restrict__ seqs, const KcPair *__restrict__ pairs, uint8_t *ws, uint32_t ksz,
 		uint32_t literal, uint32_t *cnt_out, uint64_t *res_off, uint32_t *status){
 	__shared__ uint32_t lds[KC_LDS_WORDS];
@@ -78,16 +103,45 @@ __global__ __launch_bounds__(KC_THREADS) void k_kmer_chain(const uint8_t *__rest
 	uint64_t *src = (uint64_t*)(ws + P.slot), *dst = (uint64_t*)(ws + P.slot + half);
 
 	// base codes above 3 (the whole of both sequences, also where no k-mer fits)
-	uint32_t any = 0;
-	for(uint32_t i = tid; i < qlen; i += KC_THREADS) any |= q[i];
-	for(uint32_t i = tid; i < tlen; i += KC_THREADS) any |= t[i];
-	const uint32_t bad = __syncthreads_or(any > 3u) ? 1u : 0u;
+	uint32_t bad = 0, noq = 0;                                 // noq: a marked query that has no reverse complement
+	if constexpr (!PK){
+		uint32_t any = 0;
+		for(uint32_t i = tid; i < qlen; i += KC_THREADS) any |= q[i];
+		if constexpr (QS) noq = (P.rc && __syncthreads_or(any > 3u)) ? 1u : 0u;
+		for(uint32_t i = tid; i < tlen; i += KC_THREADS) any |= t[i];
+		bad = __syncthreads_or(any > 3u) ? 1u : 0u;
+	}
 	const uint32_t st = (bad ? BSA_ST_BAD_BASE : 0u) | ((qlen == 0 || tlen == 0) ? BSA_ST_EMPTY : 0u);
 	if(tid == 0){ if(status) status[pair] = st; cnt_out[pair] = 0; res_off[pair] = P.slot; }
-	if(nrec == 0 || nq == 0 || nt == 0 || (bad && !literal)) return;
+	if(nrec == 0 || nq == 0 || nt == 0 || (bad && !literal) || noq) return;
 
 	// (a) canonical k-mers, lanes over positions
-	{
+	if constexpr (PK || QS){
+		const uint32_t mask = 0xFFFFFFFFu >> ((16u - ksz) << 1);
+		const uint64_t *W = (const uint64_t*)seqs;
+		for(uint32_t i = tid; i < nrec; i += KC_THREADS){
+			const uint32_t flg = i >= nq, p = flg ? i - nq : i;
+			const bool mir = QS && !flg && P.rc;
+			const uint32_t ps = mir ? nq - 1u - p : p;           // the stored k-mer that is the reverse complement of q' at p
+			uint32_t fwd = 0, rev = 0;
+			if constexpr (PK){
+				fwd = kc_kmer2bit(W, (flg ? P.toff : P.qoff) + ps, ksz);
+				rev = kc_revcomp2bit(fwd, ksz);
+			} else {
+				const uint8_t *s = (flg ? t : q) + ps;
+				for(uint32_t m = 0; m < ksz; m++){
+					const uint32_t b = s[m];
+					fwd |= b << ((ksz - 1u - m) << 1);
+					rev |= ((~b) & 3u) << (m << 1);
+				}
+				fwd &= mask;
+			}
+			if(mir){ const uint32_t x = fwd; fwd = rev; rev = x; }
+			const uint32_t dir = rev < fwd;
+			const uint64_t kmer = (dir ? rev : fwd) & 0x3FFFFFFFu;
+			src[i] = kmer << 34 | (uint64_t)p << 2 | (uint64_t)(flg << 1) | dir;
+		}
+	} else {
 		const uint32_t mask = 0xFFFFFFFFu >> ((16u - ksz) << 1);
 		for(uint32_t i = tid; i < nrec; i += KC_THREADS){
 			const uint32_t flg = i >= nq, p = flg ? i - nq : i;
@@ -306,8 +360,13 @@ static size_t kc_pair_bytes(uint32_t qlen, uint32_t tlen){
 // Chains the pairs idx[0 .. m) on the device.  *arena_out (malloc'd, the caller frees it) holds their anchors packed, those of idx[j] at off[j] .. off[j + 1);
 // st (m entries, may be NULL) gets BSA_ST_EMPTY / BSA_ST_BAD_BASE; fits[j] = 0 marks a pair that alone is larger than the workspace (left to the host, no anchors
 // here).  *ms: the kernels' time by HIP events.
+// flags: BSA_MODE_SEQ2BIT -- seqs are 2-bit words and the offsets base offsets: a chunk uploads, for every read, the words that hold it, as they are (a
+// quarter of the bytes); BSA_MODE_QSTRAND -- bit 63 of qoff[k] marks the pair, the stored bytes or words go up unchanged and the kernel reads them mirrored.
 extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms){
+		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint32_t flags, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms){
+	const bool pk = (flags & BSA_MODE_SEQ2BIT) != 0, qs = (flags & BSA_MODE_QSTRAND) != 0;
+	const uint64_t qmask = qs ? ~BSA_QOFF_REVCOMP : ~0ull;
+	auto kern = pk ? (qs ? k_kmer_chain<true, true> : k_kmer_chain<true, false>) : (qs ? k_kmer_chain<false, true> : k_kmer_chain<false, false>);
 	*arena_out = nullptr; *ms = 0.0;
 	off[0] = 0;
 	if(ksz > 15) ksz = 15;
@@ -344,9 +403,15 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 			}
 			if(bytes + need > budget || acap + std::min(ql, tl) > 0x7FFFFFF0ull || meta.size() >= 0x7FFFFFF0ull) break;
 			fits[j1] = 1;
-			KcPair P; P.qoff = seqb; P.toff = seqb + ql; P.slot = slots; P.qlen = ql; P.tlen = tl; P.cmin = kc_min_cover(ql, tl, ksz); P.pad = 0;
+			KcPair P; P.slot = slots; P.qlen = ql; P.tlen = tl; P.cmin = kc_min_cover(ql, tl, ksz); P.rc = (qs && (qoff[k] & BSA_QOFF_REVCOMP)) ? 1u : 0u;
+			if(pk){
+				// the words [off / 32, (off + len + 31) / 32) of each read, the read at the same place inside its first word
+				const uint64_t qo = qoff[k] & qmask, to = toff[k];
+				P.qoff = (uint64_t)seqb * 4u + (qo & 31u); if(ql) seqb += (size_t)(((qo & 31u) + ql + 31u) >> 5) * 8u;
+				P.toff = (uint64_t)seqb * 4u + (to & 31u); if(tl) seqb += (size_t)(((to & 31u) + tl + 31u) >> 5) * 8u;
+			} else { P.qoff = seqb; P.toff = seqb + ql; seqb += (size_t)ql + tl; }
 			meta.push_back(P);
-			seqb += (size_t)ql + tl; slots += 2u * kc_half_bytes(ql, tl); acap += std::min(ql, tl); bytes += need;
+			slots += 2u * kc_half_bytes(ql, tl); acap += std::min(ql, tl); bytes += need;
 			j1 ++;
 		}
 		const size_t c = meta.size();
@@ -358,7 +423,13 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 			auto body = [&](size_t a, size_t b){
 				for(size_t j = a; j < b; j++){
 					const uint32_t k = idx[j0 + j];
-					if(meta[j].qlen) memcpy(pack.data() + meta[j].qoff, seqs + qoff[k], meta[j].qlen);
+					const uint64_t qo = qoff[k] & qmask, to = toff[k];
+					if(pk){
+						if(meta[j].qlen) memcpy(pack.data() + (meta[j].qoff >> 5) * 8u, seqs + (qo >> 5) * 8u, (size_t)(((qo & 31u) + meta[j].qlen + 31u) >> 5) * 8u);
+						if(meta[j].tlen) memcpy(pack.data() + (meta[j].toff >> 5) * 8u, seqs + (to >> 5) * 8u, (size_t)(((to & 31u) + meta[j].tlen + 31u) >> 5) * 8u);
+						continue;
+					}
+					if(meta[j].qlen) memcpy(pack.data() + meta[j].qoff, seqs + qo, meta[j].qlen);
 					if(meta[j].tlen) memcpy(pack.data() + meta[j].toff, seqs + toff[k], meta[j].tlen);
 				}
 			};
@@ -386,7 +457,7 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 		if(seqb && !hip_ok(hipMemcpyAsync(buf + o_seq, pack.data(), seqb, hipMemcpyHostToDevice, stream))) break;
 		if(!hip_ok(hipMemcpyAsync(buf + o_meta, meta.data(), c * sizeof(KcPair), hipMemcpyHostToDevice, stream))) break;
 		if(!hip_ok(hipEventRecord(ev0, stream))) break;
-		hipLaunchKernelGGL(k_kmer_chain, dim3((uint32_t)c), dim3(KC_THREADS), 0, stream, (const uint8_t*)(buf + o_seq), (const KcPair*)(buf + o_meta), buf + o_ws, ksz, literal,
+		hipLaunchKernelGGL(kern, dim3((uint32_t)c), dim3(KC_THREADS), 0, stream, (const uint8_t*)(buf + o_seq), (const KcPair*)(buf + o_meta), buf + o_ws, ksz, literal,
 			(uint32_t*)(buf + o_cnt), (uint64_t*)(buf + o_res), (uint32_t*)(buf + o_st));
 		hipLaunchKernelGGL(k_kmer_scan, dim3(1), dim3(KC_THREADS), 0, stream, (const uint32_t*)(buf + o_cnt), (uint32_t*)(buf + o_off), (uint32_t)c);
 		hipLaunchKernelGGL(k_kmer_gather, dim3((uint32_t)c), dim3(KC_THREADS), 0, stream, (const uint8_t*)(buf + o_ws), (const uint64_t*)(buf + o_res), (const uint32_t*)(buf + o_cnt),

@@ -66,8 +66,9 @@ extern "C" {
                                       Results, CIGAR words and status are bit-identical to the same call on the unpacked bytes, except that
                                       BSA_ST_BAD_BASE cannot occur.  Combines with BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS.  Only the
                                       upload and the staging kernels see the packed form: the kernels behind them read the same staged
-                                      1 B/base copy as without the flag.  Not taken by bsa_kmer_edit_batch, the compat single-pair layer,
-                                      the bsalign-hip CLI, bsa_shard_*, the POA or the rows API.  bsa_seq_pack2bit packs device-resident
+                                      1 B/base copy as without the flag.  Also taken by the k-mer calls bsa_kmer_chain_batch2 and
+                                      bsa_kmer_edit_batch2 (in their `flags`, see there; bsa_kmer_edit_batch has no flags).  Not taken by the
+                                      compat single-pair layer, the bsalign-hip CLI, bsa_shard_*, the POA or the rows API.  bsa_seq_pack2bit packs device-resident
                                       1 B/base codes. */
 #define BSA_MODE_CIGAR_EQX 0x1000 /* flag: = / X CIGAR words -- for bsa_align_batch / _plan_create / _run and bsa_edit_batch / _plan_create /
                                       _run.  The reference defines the two ops (SEQALIGN_CIGAR_E / _X, bsalign.h:68-69) and prints them, but
@@ -118,8 +119,9 @@ extern "C" {
                                       all three alignment modes; bsa_align_batch keeps it on every route it takes (two slices, width classes
                                       of whole-query bands, pairs handed over to the literal kernels, the checked whole-query kernel's
                                       re-runs).  Only the four staging kernels see the strand: they stage q' and everything behind them reads
-                                      the staged copy as before.  Not taken by bsa_kmer_edit_batch (anchors are chained on the host from the
-                                      stored bytes), the compat single-pair layer, the bsalign-hip CLI (the reference's command line has no
+                                      the staged copy as before.  Also taken by the k-mer calls bsa_kmer_chain_batch2 and bsa_kmer_edit_batch2 (in
+                                      their `flags`: both chainers read a marked query mirrored and complemented, see there; bsa_kmer_edit_batch
+                                      has no flags).  Not taken by the compat single-pair layer, the bsalign-hip CLI (the reference's command line has no
                                       strand option), the POA or the rows API.  Shards: the local_qoff arrays bsa_shard_scatter hands back
                                       are the caller's; OR-ing BSA_QOFF_REVCOMP into them before bsa_align_plan_create / bsa_edit_plan_create
                                       (with the flag in the mode) is the supported way to use strands with shards. */
@@ -300,7 +302,7 @@ int  bsa_edit_run(bsa_edit_plan_t *plan, const uint8_t *d_seqs,
                   uint64_t *d_cigar_off, uint32_t *d_status);
 
 /* ---- k-mer anchored edit alignment (reference: kmer_striped_seqedit_pairwise, bsalign.h:1209-1536; CLI `edit -m kmer`) ---
- * Unique same-strand k-mers (ksz <= 15) shared by the two sequences are chained on the host; only the stretches
+ * Unique same-strand k-mers (ksz <= 15) shared by the two sequences are chained on the host (bsa_kmer_edit_batch2: or on the device); only the stretches
  * between consecutive anchors are aligned, every one of them by the device edit path (two bsa_edit_batch calls for
  * the whole batch: reversed heads and tails in EXTEND mode, gaps in GLOBAL mode), and the CIGAR of each pair is stitched together exactly as the
  * reference does it (including where it puts the anchor matches).  A pair without a usable chain is aligned globally.
@@ -346,12 +348,39 @@ int      bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, const bsa_
  *                    The device route takes every pair with qlen + tlen <= 262144; a longer pair, or one whose slice (about 17 bytes a base)
  *                    exceeds bsa_ctx_set_workspace_limit, is chained by the host code inside the same call -- same words, the caller sees no
  *                    difference but bsa_ctx_last_kmer_chain_ms.  Pairs go in chunks when the workspace does not hold them all.
- *                    Takes 1 B/base blobs only: no BSA_MODE_SEQ2BIT, BSA_MODE_QSTRAND marks or device pointers. */
+ *                    Takes 1 B/base blobs and no strand marks: it IS bsa_kmer_chain_batch2 with flags 0, which takes BSA_MODE_SEQ2BIT blobs and
+                    BSA_MODE_QSTRAND marks.  Neither takes device pointers.
+ * bsa_kmer_chain_batch2: the same call with `flags`, a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND (any other bit: BSA_E_ARG), meaning exactly what they
+ *                    mean for bsa_align_batch.  SEQ2BIT: seqs are BaseBank.bits words, qoff / toff BASE offsets (any offset), seqs_bytes a multiple of
+ *                    8 and off + len <= 4 * seqs_bytes, else BSA_E_ARG; BSA_ST_BAD_BASE cannot occur.  QSTRAND: bit 63 of qoff[k]
+ *                    (BSA_QOFF_REVCOMP) marks pair k, which then chains q', q'[i] = 3 - q[qlen - 1 - i], against t; bounds are tested on the masked
+ *                    offset, and without the flag bit 63 is an offset outside the blob (BSA_E_ARG).  maps, maps_off and status are bit-identical to
+ *                    bsa_kmer_chain_batch on a 1 B/base blob in which the caller stored q' (or q) and t -- the query offsets in the anchor words are
+ *                    positions in q'; the k-mer at q'[i, i + ksz) is the reverse complement of stored bases [qlen - ksz - i, qlen - i).  A batch with
+ *                    QSTRAND and no pair marked returns what the plain call returns; a marked pair whose stored 1 B/base query holds a code above 3
+ *                    has no q': BSA_ST_BAD_BASE and no anchors, as for the unmarked pair.  BSA_E_CIGAR_CAP / maps_off[n] as above.
+ *                    Example: a read r of 2 000 bases is stored ONCE at offset 0; target A at offset 2000 overlaps it on the forward strand, target
+ *                    B = the reverse complement of r (B[i] = 3 - r[1999 - i]) at offset 4000.  n = 2, qlen = tlen = {2000, 2000},
+ *                    qoff = {0, 0 | BSA_QOFF_REVCOMP}, toff = {2000, 4000}, flags = BSA_MODE_QSTRAND.  Pair 1 chains q' = B against B: its anchors
+ *                    are i << 32 | i for the positions i whose k-mer occurs once (nearly all of 0 .. 1987 at ksz 13) -- without the mark the pair
+ *                    has no anchors at all, the chainer keeps same-strand k-mers only.  Pair 0 is what it is without the flag.
+ *                    On the device only the first stage (k-mer extraction) sees the flags: a marked query is read mirrored with the roles of the
+ *                    forward and the reverse-complement k-mer swapped; a packed k-mer comes from the one or two words that hold it, and nothing is
+ *                    read in front of the word that holds a read's first base nor behind the one that holds its last.  A packed read goes up as
+ *                    the words that hold it, a quarter of the bytes.  Pairs the device route does not take are chained by the host code on a
+ *                    per-pair decoded copy: the same words.  bsa_ctx_last_kmer_chain_ms keeps its meaning.
+ *                    Out of scope for the k-mer calls: BSA_MODE_CIGAR_EQX and BSA_MODE_SCORE_ONLY, device-pointer or plan forms, the bsalign-hip CLI
+ *                    and the compat layer (both keep 1 B/base forward-strand queries). */
 int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                          const uint64_t *qoff, const uint32_t *qlen,
                          const uint64_t *toff, const uint32_t *tlen, size_t n,
                          uint32_t ksz, uint64_t *maps, size_t maps_cap,
                          uint64_t *maps_off /* n + 1 */, uint32_t *status /* may be NULL */);
+int bsa_kmer_chain_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+                          const uint64_t *qoff, const uint32_t *qlen,
+                          const uint64_t *toff, const uint32_t *tlen, size_t n,
+                          uint32_t ksz, uint64_t *maps, size_t maps_cap,
+                          uint64_t *maps_off /* n + 1 */, uint32_t *status /* may be NULL */, uint32_t flags);
 
 #define BSA_KMER_CHAIN_DEVICE 1u    /* flag of bsa_kmer_edit_batch2: step 1 of the batch (chains, then segment lists) takes its anchors from the device
                                        chainer above instead of the host threads.  Records, CIGAR words, cigar_off and status are bit-identical to
@@ -359,8 +388,16 @@ int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                                        code does, an empty pair has no anchors either way, and a pair above the device route's size limit is chained
                                        by the host inside the call.  bsa_kmer_segments, the two edit batches and bsa_kmer_assemble are the same code.
                                        Example: bsa_kmer_edit_batch2(ctx, ..., &par, out, cigar, cap, cigar_off, status, BSA_KMER_CHAIN_DEVICE).
-                                       flags == 0 IS bsa_kmer_edit_batch (which calls this function with 0); any other bit is BSA_E_ARG.  Does not
-                                       combine with the BSA_MODE_* flags of the align and edit calls: the kmer calls take none of them. */
+                                       flags == 0 IS bsa_kmer_edit_batch (which calls this function with 0).
+                                       flags may also carry BSA_MODE_SEQ2BIT and BSA_MODE_QSTRAND (0x800, 0x2000: no collision with bit 0), with or
+                                       without BSA_KMER_CHAIN_DEVICE, with the meaning and the argument rules given at bsa_kmer_chain_batch2.  Records
+                                       (qb / qe in q' coordinates), CIGAR words, cigar_off and status are then bit-identical to bsa_kmer_edit_batch on a
+                                       1 B/base blob in which the caller stored q' (or q) and t, on either chain route.  The gap segments stay views into
+                                       the caller's blob (gap [qb, qe) of a marked pair is stored bases [qlen - qe, qlen - qb) with BSA_QOFF_REVCOMP set,
+                                       and bsa_edit_batch runs with the same flags); heads and tails are decoded per pair on the host threads.  One
+                                       definition: a marked pair whose stored 1 B/base query holds a code above 3 has no q' -- BSA_ST_BAD_BASE, an
+                                       all-zero record, no CIGAR words; unmarked pairs with such a code behave as without the flags.
+                                       Any other bit is BSA_E_ARG: no BSA_MODE_CIGAR_EQX, BSA_MODE_SCORE_ONLY or other BSA_MODE_* flag is taken. */
 int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                          const uint64_t *qoff, const uint32_t *qlen,
                          const uint64_t *toff, const uint32_t *tlen, size_t n,
