@@ -24,6 +24,8 @@ QOFF_REVCOMP = 1 << 63                                                    # in q
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_EQ, CIGAR_X = 0, 1, 2, 7, 8
 ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 KMER_CHAIN_DEVICE = 1                                                      # bsa_kmer_edit_batch2: the anchors come from the device chainer
+KMER_STRAND_AUTO = 2                                                       # bsa_kmer_chain_batch2 / bsa_kmer_edit_batch2: the call finds each pair's strand ...
+ST_REVCOMP = 16                                                            # ... and sets this status bit where it used the reverse complement of the stored query
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
            -5: "BSA_E_CIGAR_CAP", -6: "BSA_E_UNSUPPORTED"}
@@ -538,30 +540,37 @@ class Context:
         self._chk(lib().bsa_seq_pack2bit(self.h, C.c_void_p(d_codes.data_ptr()), n, C.c_void_p(d_bits.data_ptr()),
                                          C.c_void_p(d_bad.data_ptr() if d_bad is not None else 0)))
 
-    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None, device_chain=False, seq2bit=False, strands=None):
+    def kmer_edit_batch(self, pairs, ksz=13, threads=0, cigar_cap=None, device_chain=False, seq2bit=False, strands=None, auto_strand=False):
         """k-mer anchored edit alignment (the reference's kmer_striped_seqedit_pairwise, bsalign.h:1209) of a batch;
         device_chain: the anchors come from the device chainer (bsa_kmer_edit_batch2 with KMER_CHAIN_DEVICE), same results;
         seq2bit / strands as in edit_batch (bsa_kmer_edit_batch2 with MODE_SEQ2BIT / MODE_QSTRAND in its flags): the queries are stored as
-        given and pair k aligns revcomp(q) where strands[k] is true"""
+        given and pair k aligns revcomp(q) where strands[k] is true.  auto_strand (KMER_STRAND_AUTO, not together with strands): the call finds
+        every pair's strand -- reverse where revcomp(q) chains to more anchors than q -- and status & ST_REVCOMP says which pairs aligned revcomp(q)"""
+        if auto_strand and strands is not None:
+            raise ValueError("kmer_edit_batch: auto_strand finds the strands itself, strands= gives them: pass one of the two")
         p = KmerParams()
         p.ksz, p.threads = ksz, threads
-        flags = (KMER_CHAIN_DEVICE if device_chain else 0) | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        flags = (KMER_CHAIN_DEVICE if device_chain else 0) | (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0) | (KMER_STRAND_AUTO if auto_strand else 0)
         if not flags:
             return self._batch(lib().bsa_kmer_edit_batch, pairs, p, cigar_cap)
         fn = lib().bsa_kmer_edit_batch2
         return self._batch(lambda *a: fn(*a, flags), pairs, p, cigar_cap, seq2bit, strands)
 
-    def kmer_chain_batch(self, pairs, ksz=13, with_status=False, seq2bit=False, strands=None):
+    def kmer_chain_batch(self, pairs, ksz=13, with_status=False, seq2bit=False, strands=None, auto_strand=False):
         """bsa_kmer_chain_batch: the anchors of every pair (query offset << 32 | target offset, in query order) as a list of uint64 arrays,
         chained on the device; with_status: (anchors, status) -- ST_EMPTY / ST_BAD_BASE pairs have none.  seq2bit / strands as in edit_batch
-        (bsa_kmer_chain_batch2): where strands[k] is true the anchors are those of revcomp(q) against t, query offsets in revcomp(q)"""
+        (bsa_kmer_chain_batch2): where strands[k] is true the anchors are those of revcomp(q) against t, query offsets in revcomp(q).
+        auto_strand (KMER_STRAND_AUTO, not together with strands): the call finds every pair's strand and additionally returns them as a bool
+        array (from ST_REVCOMP, which is masked out of the status): (anchors, strands) or (anchors, status, strands)"""
+        if auto_strand and strands is not None:
+            raise ValueError("kmer_chain_batch: auto_strand finds the strands itself, strands= gives them: pass one of the two")
         seqs, qoff, qlen, toff, tlen = pack_pairs(pairs, seq2bit, strands)
         n = len(pairs)
         cap = int(np.minimum(qlen, tlen).sum()) + 1
         maps = np.zeros(cap, dtype=np.uint64)
         off = np.zeros(n + 1, dtype=np.uint64)
         status = np.zeros(max(n, 1), dtype=np.uint32)
-        flags = (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        flags = (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0) | (KMER_STRAND_AUTO if auto_strand else 0)
         if flags:
             self._chk(lib().bsa_kmer_chain_batch2(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
                                                   _p(maps), cap, _p(off), _p(status), flags))
@@ -569,6 +578,10 @@ class Context:
             self._chk(lib().bsa_kmer_chain_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(toff), _p(tlen), n, ksz,
                                                  _p(maps), cap, _p(off), _p(status)))
         res = [maps[int(off[k]):int(off[k + 1])].copy() for k in range(n)]
+        if auto_strand:
+            found = (status[:n] & np.uint32(ST_REVCOMP)) != 0
+            status = status & ~np.uint32(ST_REVCOMP)
+            return (res, status[:n], found) if with_status else (res, found)
         return (res, status[:n]) if with_status else res
 
     def last_kmer_chain_ms(self):

@@ -177,6 +177,19 @@ void chain(uint32_t ksz, const uint8_t *q, uint32_t qlen, const uint8_t *t, uint
 	if(cov < cmin) hits.clear();
 }
 
+/* BSA_KMER_STRAND_AUTO on the host: the anchors of (q, t) and of (q', t), q'[i] = 3 - q[qlen - 1 - i]; reverse exactly when q' has more.  `hits` gets the
+ * winner's; returns whether that is the reverse strand.  The caller keeps pairs with a base code above 3 away (they are chained forward only). */
+bool chain_auto(uint32_t ksz, const uint8_t *q, uint32_t qlen, const uint8_t *t, uint32_t tlen, std::vector<Hit> &hits){
+	chain(ksz, q, qlen, t, tlen, hits);
+	std::vector<uint8_t> rq(qlen);
+	for(uint32_t i = 0; i < qlen; i++) rq[i] = (uint8_t)(3 - q[qlen - 1 - i]);
+	std::vector<Hit> rev;
+	chain(ksz, rq.data(), qlen, t, tlen, rev);
+	if(rev.size() <= hits.size()) return false;
+	hits.swap(rev);
+	return true;
+}
+
 /* the segment list of one pair (bsalign.h:1451-1530): anchor i sits at (qoff + ksz/2, toff + ksz/2); the segment in
  * front of it is aligned, the anchor column itself is emitted as a match in front of the next non-empty segment */
 uint32_t segments(uint32_t ksz, const uint64_t *maps, uint32_t kmap, uint32_t qlen, uint32_t tlen, bsa_kmer_seg_t *segs){
@@ -285,6 +298,11 @@ struct Blob {
 	}
 };
 const uint32_t SEQ_FLAGS = BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND;
+const uint32_t CHAIN_FLAGS = SEQ_FLAGS | BSA_KMER_STRAND_AUTO;        /* what the chainers see */
+/* BSA_KMER_STRAND_AUTO needs the status array and excludes the caller's own marks */
+bool auto_args_ok(uint32_t flags, const uint32_t *status){
+	return !(flags & BSA_KMER_STRAND_AUTO) || (status != nullptr && !(flags & BSA_MODE_QSTRAND));
+}
 
 /* every pair inside the blob; a SEQ2BIT blob is whole words */
 bool blob_args_ok(const Blob &B, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n){
@@ -345,7 +363,7 @@ int device_chains(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, con
 	const size_t m = idx.size();
 	D.off.assign(m + 1, 0); D.st.assign(m, 0);
 	std::vector<uint8_t> fits(m, 0);
-	const int rc = bsa_kmer_chain_dev_internal(ctx, seqs, qoff, qlen, toff, tlen, idx.data(), m, ksz, literal, flags & SEQ_FLAGS, &D.arena, D.off.data(), D.st.data(), fits.data(), &D.ms);
+	const int rc = bsa_kmer_chain_dev_internal(ctx, seqs, qoff, qlen, toff, tlen, idx.data(), m, ksz, literal, flags & CHAIN_FLAGS, &D.arena, D.off.data(), D.st.data(), fits.data(), &D.ms);
 	if(rc != BSA_OK) return rc;
 	for(size_t j = 0; j < m; j++) if(!fits[j]) D.pos[idx[j]] = NONE; else D.on_device ++;
 	D.on_host = (long)n - D.on_device;
@@ -360,6 +378,7 @@ static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
 	const Blob B = { seqs, (flags & BSA_MODE_SEQ2BIT) != 0, (flags & BSA_MODE_QSTRAND) != 0 };
 	if(!blob_args_ok(B, seqs_bytes, qoff, qlen, toff, tlen, n)) return BSA_E_ARG;
 	if(ksz > 15) ksz = 15;
+	const bool autos = (flags & BSA_KMER_STRAND_AUTO) != 0;
 	DevChains D;
 	if(ksz){
 		const int rc = device_chains(ctx, seqs, qoff, qlen, toff, tlen, n, ksz, 0, flags, D);
@@ -384,7 +403,14 @@ static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
 		hst[j] = (any > 3 ? BSA_ST_BAD_BASE : 0u) | ((qlen[k] == 0 || tlen[k] == 0) ? BSA_ST_EMPTY : 0u);
 		if(hst[j] || ksz == 0) return;
 		std::vector<Hit> hits;
-		if(B.packed || B.marked(qoff[k])){                  /* this pair's bases as the call aligns them, one per byte */
+		if(autos && B.packed){
+			std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
+			B.stored(qo, 0, qlen[k], own.data());
+			B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
+			if(chain_auto(ksz, own.data(), qlen[k], own.data() + qlen[k], tlen[k], hits)) hst[j] |= BSA_ST_REVCOMP;
+		} else if(autos){
+			if(chain_auto(ksz, seqs + qo, qlen[k], seqs + toff[k], tlen[k], hits)) hst[j] |= BSA_ST_REVCOMP;
+		} else if(B.packed || B.marked(qoff[k])){                  /* this pair's bases as the call aligns them, one per byte */
 			std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
 			B.query(qoff[k], qlen[k], 0, qlen[k], own.data());
 			B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
@@ -411,7 +437,7 @@ static int kmer_chain_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
 
 extern "C" int bsa_kmer_chain_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		size_t n, uint32_t ksz, uint64_t *maps, size_t maps_cap, uint64_t *maps_off, uint32_t *status, uint32_t flags){
-	if(flags & ~SEQ_FLAGS) return BSA_E_ARG;
+	if((flags & ~CHAIN_FLAGS) || !auto_args_ok(flags, status)) return BSA_E_ARG;
 	try {
 		return kmer_chain_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, ksz, maps, maps_cap, maps_off, status, flags);
 	} catch(...){
@@ -431,7 +457,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 extern "C" int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_kmer_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words, uint64_t *cigar_off, uint32_t *status, uint32_t flags){
-	if(flags & ~(BSA_KMER_CHAIN_DEVICE | SEQ_FLAGS)) return BSA_E_ARG;
+	if((flags & ~(BSA_KMER_CHAIN_DEVICE | CHAIN_FLAGS)) || !auto_args_ok(flags, status)) return BSA_E_ARG;
 	try {
 		return kmer_edit_batch_impl(ctx, seqs, seqs_bytes, qoff, qlen, toff, tlen, n, par, out, cigar, cigar_cap_words, cigar_off, status, flags);
 	} catch(...){                               // host allocations (vectors, worker threads): no exception crosses the C ABI
@@ -451,8 +477,10 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	if(!ctx || !par || !out || (n && (!seqs || !qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;
 	if(par->ksz == 0) return BSA_E_ARG;
 	const uint32_t ksz = par->ksz > 15 ? 15 : par->ksz;
-	const Blob B = { seqs, (flags & BSA_MODE_SEQ2BIT) != 0, (flags & BSA_MODE_QSTRAND) != 0 };
+	Blob B = { seqs, (flags & BSA_MODE_SEQ2BIT) != 0, (flags & BSA_MODE_QSTRAND) != 0 };
 	if(!blob_args_ok(B, seqs_bytes, qoff, qlen, toff, tlen, n)) return BSA_E_ARG;
+	const bool autos = (flags & BSA_KMER_STRAND_AUTO) != 0;
+	std::vector<uint8_t> rev(autos ? n : 0, 0);            /* BSA_KMER_STRAND_AUTO: the pairs step 1 finds on the reverse strand */
 	const bool timing = getenv("BSA_KMER_TIMING") != nullptr;          /* phase times on stderr */
 	auto now = [](){ return std::chrono::steady_clock::now(); };
 	auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b){ return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -476,6 +504,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 		}
 		if(any > 3) flag[k] = BSA_ST_BAD_BASE;
 		if(dev && D.pos[k] != NONE){
+			if(autos) rev[k] = (D.st[D.pos[k]] & BSA_ST_REVCOMP) != 0;
 			const uint64_t *mp = D.arena + D.off[D.pos[k]];
 			const size_t nm = (size_t)(D.off[D.pos[k] + 1] - D.off[D.pos[k]]);
 			segs[k].resize(nm + 1);
@@ -483,7 +512,14 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 			return;
 		}
 		std::vector<Hit> hits;
-		if(B.packed || B.marked(qoff[k])){                  /* this pair's bases as the call aligns them, one per byte */
+		if(autos && any <= 3){                              /* both strands, on the decoded copy where the blob is packed; a bad-base pair is chained forward on its bytes, below */
+			if(B.packed){
+				std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
+				B.stored(qo, 0, qlen[k], own.data());
+				B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
+				rev[k] = chain_auto(ksz, own.data(), qlen[k], own.data() + qlen[k], tlen[k], hits);
+			} else rev[k] = chain_auto(ksz, seqs + qo, qlen[k], seqs + toff[k], tlen[k], hits);
+		} else if(B.packed || B.marked(qoff[k])){           /* this pair's bases as the call aligns them, one per byte */
 			std::vector<uint8_t> own((size_t)qlen[k] + tlen[k]);
 			B.query(qoff[k], qlen[k], 0, qlen[k], own.data());
 			B.stored(toff[k], 0, tlen[k], own.data() + qlen[k]);
@@ -494,6 +530,15 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 		segs[k].resize(hits.size() + 1);
 		segs[k].resize(segments(ksz, maps.data(), (uint32_t)maps.size(), qlen[k], tlen[k], segs[k].data()));
 	});
+	/* BSA_KMER_STRAND_AUTO: from here on the call is the BSA_MODE_QSTRAND route on a private copy of qoff that carries the strands found */
+	std::vector<uint64_t> own_qoff;
+	if(autos){
+		own_qoff.assign(qoff, qoff + n);
+		for(size_t k = 0; k < n; k++) if(rev[k]) own_qoff[k] |= BSA_QOFF_REVCOMP;
+		qoff = own_qoff.data();
+		B.strand = true;
+		flags = (flags & ~BSA_KMER_STRAND_AUTO) | BSA_MODE_QSTRAND;
+	}
 	auto t1 = now();
 	/* 2. two device batches: EXTEND for the reversed heads and the tails (copied into one blob), GLOBAL for the gaps
 	 *    (views into the caller's blob) */
@@ -623,7 +668,7 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 		}
 		const int rc = assemble(segs[k].data(), (uint32_t)ns, rs.data(), ptr.data(), cnt.data(), &out[k], work + need[k], need[k + 1] - need[k], &used[k]);
 		if(rc != BSA_OK) bad = rc;
-		if(status) status[k] = st;
+		if(status) status[k] = st | ((autos && rev[k]) ? BSA_ST_REVCOMP : 0u);
 	});
 	if(bad != BSA_OK) return bad;
 	if(timing) fprintf(stderr, "[bsa_kmer] %zu pairs: chain %.1f ms, pack %.1f ms (%zu heads and tails, %zu gaps), device %.1f ms, stitch %.1f ms\n",

@@ -25,6 +25,16 @@
 //   PK  the sequences are 2-bit words, 32 bases each from the top bit down (bsa_common.h), offsets are base offsets: the forward k-mer comes from the
 //       one or two words that hold it (funnel shift), its reverse complement from a bit reversal with the bits of each pair swapped back -- no
 //       loop over bases, no bad-base scan, no word read that holds no base of the read.
+//
+// BSA_KMER_STRAND_AUTO: k_kmer_chain<PK, false, true> finds the pair's strand itself.  Stages (a) and (b) are those of <PK, false>: the unmarked records,
+// ONE sort.  A run of exactly two records with different flg is a forward hit (qo, to) when the dir bits are equal and a hit (nq - 1 - qo, to) against
+// q' when they differ -- or when the k-mer is its own reverse complement, whose dir is 0 on both strands (even ksz).  Those are the records the QS
+// kernel would have sorted for a marked query: the same canonical k-mers, dir flipped (but for those k-mers), positions
+// mirrored, and the query record still ahead of the target record inside a run (the sort is stable and the query records come first) -- so the run
+// boundaries and the zero-sentinel test `i + 2 == n && kmer == 0` are the same for both strands.  Stages (c) to (e) are one function (kc_chain_hits),
+// called once per strand: the forward pass keeps its hits in the 8 min(qlen, tlen) extra bytes behind the slice's halves so that the sorted records
+// survive it, its anchors then move there, and the reverse pass runs with the layout of the other kernels.  Reverse exactly when it has MORE anchors;
+// a pair with a base code above 3 is chained forward only.
 #include "bsa_common.h"
 #include <algorithm>
 #include <cstdlib>
@@ -88,7 +98,158 @@ __device__ __forceinline__ uint32_t kc_revcomp2bit(uint32_t fwd, uint32_t ksz){
 	return (~r) >> ((16u - ksz) << 1);
 }
 
-template <bool PK, bool QS>
+// Runs of exactly two records with different flg and equal dir (REV: different dir -- a hit against q', at the mirrored query position) in the sorted
+// records `src`: target offset + 1 at index `query offset` of the zeroed `slotq`.  A run of k-mer 0 that reaches the end is never closed (the host's
+// zeroed sentinel).  A k-mer that is its own reverse complement (even ksz only) has dir 0 on either strand of either sequence: its run is a hit
+// forward AND against q'.
+template <bool REV>
+__device__ __forceinline__ void kc_mark_hits(const uint64_t *src, uint32_t nrec, uint32_t *slotq, uint32_t qlen, uint32_t nq, uint32_t ksz){
+	const uint32_t tid = threadIdx.x;
+	for(uint32_t i = tid; i < qlen; i += KC_THREADS) slotq[i] = 0;
+	__syncthreads();
+	for(uint32_t i = tid; i + 1u < nrec; i += KC_THREADS){
+		const uint64_t r = src[i], r1 = src[i + 1];
+		const uint32_t k = (uint32_t)(r >> 34);
+		if((uint32_t)(r1 >> 34) != k) continue;
+		if(i > 0 && (uint32_t)(src[i - 1] >> 34) == k) continue;
+		if(i + 2u < nrec){ if((uint32_t)(src[i + 2] >> 34) == k) continue; }
+		else if(k == 0) continue;
+		if((((uint32_t)r ^ (uint32_t)r1) & 2u) == 0) continue;
+		if constexpr (REV){ if((((uint32_t)r ^ (uint32_t)r1) & 1u) == 0 && kc_revcomp2bit(k, ksz) != k) continue; }
+		else if((((uint32_t)r ^ (uint32_t)r1) & 1u) != 0) continue;
+		const uint64_t kq = ((uint32_t)r & 2u) ? r1 : r, kt = ((uint32_t)r & 2u) ? r : r1;
+		const uint32_t qs = (uint32_t)(kq >> 2), to = (uint32_t)(kt >> 2);
+		const uint32_t qo = REV ? nq - 1u - qs : qs;
+		if(qo < qlen) slotq[qo] = to + 1u;
+	}
+	__syncthreads();
+}
+
+// Stages (c) to (e) and the second coverage test on the hits `slotq` holds (it may be the start of `work`); `hits` (nh <= min(qlen, tlen) words) and `work`
+// (13 nh bytes) are distinct.  Where the chain reaches the end, done(anchors, where they are) is called by every lane; an early return means no anchors.
+template <typename Done>
+__device__ __forceinline__ void kc_chain_hits(const uint32_t *slotq, uint64_t *hits, uint64_t *work, uint32_t qlen, uint32_t tlen, uint32_t ksz, uint32_t cmin,
+		uint32_t *lds, uint32_t *red, uint32_t *s_flag, Done done){
+	const uint32_t tid = threadIdx.x;
+	// (c) the hits in query order: compact slotq into `hits`
+	uint32_t nh;
+	{
+		const uint32_t per = (qlen + KC_THREADS - 1u) / KC_THREADS;
+		const uint32_t b0 = min(tid * per, qlen), e0 = min(b0 + per, qlen);
+		uint32_t c = 0;
+		for(uint32_t i = b0; i < e0; i++) c += slotq[i] != 0;
+		uint32_t w = kc_block_excl_scan(c, red, nh);
+		for(uint32_t i = b0; i < e0; i++){ const uint32_t v = slotq[i]; if(v){ hits[w ++] = (uint64_t)i << 32 | (v - 1u); } }
+	}
+	__syncthreads();
+	if(nh * ksz < cmin) return;
+	// `work` now: [out: nh u64 (the LIS tail beyond its LDS part until then)] [prev: nh u32] [keep: nh bytes] -- 13 nh <= 6.5 (qlen + tlen) bytes
+	uint64_t *outp = work;
+	uint32_t *gtail = (uint32_t*)work;                    // index at [m], target offset at [nh + m]
+	uint32_t *gprev = (uint32_t*)(work + nh);
+	uint8_t  *keep  = (uint8_t*)(gprev + nh);
+	for(uint32_t i = tid; i < nh; i += KC_THREADS) keep[i] = 0;
+	__syncthreads();
+	// (d) + first half of (e): one lane
+	if(tid == 0){
+		uint32_t *tl_i = lds, *tl_v = lds + KC_TAIL_CAP, *pv = lds + 2u * KC_TAIL_CAP;
+		auto set_tail = [&](uint32_t m, uint32_t i, uint32_t v){ if(m < KC_TAIL_CAP){ tl_i[m] = i; tl_v[m] = v; } else { gtail[m] = i; gtail[nh + m] = v; } };
+		auto tail_v = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_v[m] : gtail[nh + m]; };
+		auto tail_i = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_i[m] : gtail[m]; };
+		auto set_prev = [&](uint32_t i, uint32_t v){ if(i < KC_PREV_CAP) pv[i] = v; else gprev[i] = v; };
+		auto get_prev = [&](uint32_t i){ return i < KC_PREV_CAP ? pv[i] : gprev[i]; };
+		uint32_t len = 1, first_v = (uint32_t)hits[0], last_v = first_v, last_i = 0;
+		set_tail(0, 0, first_v); set_prev(0, KC_NONE);
+		uint32_t nxt = nh > 1 ? (uint32_t)hits[1] : 0;
+		for(uint32_t i = 1; i < nh; i++){
+			const uint32_t tv = nxt;
+			if(i + 1u < nh) nxt = (uint32_t)hits[i + 1];
+			if(tv > last_v){
+				set_prev(i, last_i);
+				set_tail(len, i, tv); len ++;
+				last_v = tv; last_i = i;
+			} else if(tv <= first_v){
+				set_prev(i, KC_NONE);
+				set_tail(0, i, tv);
+				first_v = tv;
+				if(len == 1){ last_v = tv; last_i = i; }
+			} else {
+				uint32_t b = 0, e = len;
+				while(b < e){
+					const uint32_t m = b + ((e - b) >> 1), mv = tail_v(m);
+					if(tv > mv) b = m + 1;
+					else if(tv < mv) e = m;
+					else { b = m; break; }
+				}
+				if(b == 0 || b >= len) b = b == 0 ? 1 : len - 1;       // (cannot happen: first_v < tv <= last_v)
+				set_prev(i, get_prev(tail_i(b - 1)));                // as written in the reference: the predecessor of that tail, not the tail
+				set_tail(b, i, tv);
+				if(b == len - 1u){ last_v = tv; last_i = i; }
+			}
+		}
+		uint32_t cov = 0, e = KC_NONE, m = last_i;
+		while(m != KC_NONE && m < nh){
+			const uint32_t tf = (uint32_t)hits[m];
+			keep[m] = 1;
+			cov += (tf + ksz <= e) ? ksz : e - tf;
+			e = tf;
+			m = get_prev(m);
+		}
+		*s_flag = cov >= cmin;
+	}
+	__syncthreads();
+	if(!*s_flag) return;
+	// (e) the diagonal filter across the workgroup (a lane always looks at the same hits)
+	for(;;){
+		uint32_t e = 0, tot = 0;
+		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; tot += (uint32_t)(h >> 32) - (uint32_t)h; e ++; }
+		e = kc_block_sum(e, red);
+		tot = kc_block_sum(tot, red);
+		if(e * ksz < cmin) break;
+		const int mean = (int)tot / (int)e;
+		const uint32_t rank = e / 2u;
+		int lo = -(int)tlen, hi = (int)qlen;                    // the element of rank e / 2: the smallest v with more than `rank` diagonals <= v
+		while(lo < hi){
+			const int mid = lo + ((hi - lo) >> 1);
+			uint32_t c = 0;
+			for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; c += (int)((uint32_t)(h >> 32) - (uint32_t)h) <= mid; }
+			c = kc_block_sum(c, red);
+			if(c > rank) hi = mid; else lo = mid + 1;
+		}
+		const int median = lo;
+		const int var = max(abs(median - mean) * 3, 50);
+		uint32_t dropped = 0;
+		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){
+			const uint64_t h = hits[i];
+			const int d = (int)((uint32_t)(h >> 32) - (uint32_t)h);
+			if(abs(d - mean) > var){ keep[i] = 0; dropped ++; }
+		}
+		dropped = kc_block_sum(dropped, red);
+		if(dropped == 0) break;
+	}
+	__syncthreads();
+	// final compaction (in order) and the second coverage test
+	uint32_t w_tot;
+	{
+		const uint32_t per = (nh + KC_THREADS - 1u) / KC_THREADS;
+		const uint32_t b0 = min(tid * per, nh), e0 = min(b0 + per, nh);
+		uint32_t c = 0;
+		for(uint32_t i = b0; i < e0; i++) c += keep[i] != 0;
+		uint32_t w = kc_block_excl_scan(c, red, w_tot);
+		for(uint32_t i = b0; i < e0; i++) if(keep[i]) outp[w ++] = hits[i];
+	}
+	__syncthreads();
+	uint32_t cov = 0;
+	for(uint32_t i = tid; i < w_tot; i += KC_THREADS){
+		const uint32_t tf = (uint32_t)outp[i], e = i ? (uint32_t)outp[i - 1] + ksz : 0u;
+		cov += (tf >= e + ksz) ? ksz : tf + ksz - e;
+	}
+	cov = kc_block_sum(cov, red);
+	done(cov < cmin ? 0u : w_tot, outp);
+}
+
+
+template <bool PK, bool QS, bool AUTO>
 __global__ __launch_bounds__(KC_THREADS) void k_kmer_chain(const uint8_t *__restrict__ seqs, const KcPair *__restrict__ pairs, uint8_t *ws, uint32_t ksz,
 		uint32_t literal, uint32_t *cnt_out, uint64_t *res_off, uint32_t *status){
 	__shared__ uint32_t lds[KC_LDS_WORDS];
@@ -188,139 +349,34 @@ __global__ __launch_bounds__(KC_THREADS) void k_kmer_chain(const uint8_t *__rest
 		}
 	}
 	// src: the sorted records; dst: free
-	uint32_t *slotq = (uint32_t*)dst;
-	for(uint32_t i = tid; i < qlen; i += KC_THREADS) slotq[i] = 0;
-	__syncthreads();
-	// runs of exactly two records with different flg and equal dir; a run of k-mer 0 that reaches the end is never closed (the host's zeroed sentinel)
-	for(uint32_t i = tid; i + 1u < nrec; i += KC_THREADS){
-		const uint64_t r = src[i], r1 = src[i + 1];
-		const uint32_t k = (uint32_t)(r >> 34);
-		if((uint32_t)(r1 >> 34) != k) continue;
-		if(i > 0 && (uint32_t)(src[i - 1] >> 34) == k) continue;
-		if(i + 2u < nrec){ if((uint32_t)(src[i + 2] >> 34) == k) continue; }
-		else if(k == 0) continue;
-		if((((uint32_t)r ^ (uint32_t)r1) & 2u) == 0 || (((uint32_t)r ^ (uint32_t)r1) & 1u) != 0) continue;
-		const uint64_t kq = ((uint32_t)r & 2u) ? r1 : r, kt = ((uint32_t)r & 2u) ? r : r1;
-		const uint32_t qo = (uint32_t)(kq >> 2), to = (uint32_t)(kt >> 2);
-		if(qo < qlen) slotq[qo] = to + 1u;
-	}
-	__syncthreads();
-	// (c) the hits in query order: compact slotq into `src` (the sorted records are no longer needed)
-	uint64_t *hits = src;
-	uint32_t nh;
-	{
-		const uint32_t per = (qlen + KC_THREADS - 1u) / KC_THREADS;
-		const uint32_t b0 = min(tid * per, qlen), e0 = min(b0 + per, qlen);
-		uint32_t c = 0;
-		for(uint32_t i = b0; i < e0; i++) c += slotq[i] != 0;
-		uint32_t w = kc_block_excl_scan(c, red, nh);
-		for(uint32_t i = b0; i < e0; i++){ const uint32_t v = slotq[i]; if(v){ hits[w ++] = (uint64_t)i << 32 | (v - 1u); } }
-	}
-	__syncthreads();
-	if(nh * ksz < cmin) return;
-	// `dst` now: [out: nh u64 (the LIS tail beyond its LDS part until then)] [prev: nh u32] [keep: nh bytes] -- 13 nh <= 6.5 (qlen + tlen) bytes
-	uint64_t *outp = dst;
-	uint32_t *gtail = (uint32_t*)dst;                     // index at [m], target offset at [nh + m]
-	uint32_t *gprev = (uint32_t*)(dst + nh);
-	uint8_t  *keep  = (uint8_t*)(gprev + nh);
-	for(uint32_t i = tid; i < nh; i += KC_THREADS) keep[i] = 0;
-	__syncthreads();
-	// (d) + first half of (e): one lane
-	if(tid == 0){
-		uint32_t *tl_i = lds, *tl_v = lds + KC_TAIL_CAP, *pv = lds + 2u * KC_TAIL_CAP;
-		auto set_tail = [&](uint32_t m, uint32_t i, uint32_t v){ if(m < KC_TAIL_CAP){ tl_i[m] = i; tl_v[m] = v; } else { gtail[m] = i; gtail[nh + m] = v; } };
-		auto tail_v = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_v[m] : gtail[nh + m]; };
-		auto tail_i = [&](uint32_t m){ return m < KC_TAIL_CAP ? tl_i[m] : gtail[m]; };
-		auto set_prev = [&](uint32_t i, uint32_t v){ if(i < KC_PREV_CAP) pv[i] = v; else gprev[i] = v; };
-		auto get_prev = [&](uint32_t i){ return i < KC_PREV_CAP ? pv[i] : gprev[i]; };
-		uint32_t len = 1, first_v = (uint32_t)hits[0], last_v = first_v, last_i = 0;
-		set_tail(0, 0, first_v); set_prev(0, KC_NONE);
-		uint32_t nxt = nh > 1 ? (uint32_t)hits[1] : 0;
-		for(uint32_t i = 1; i < nh; i++){
-			const uint32_t tv = nxt;
-			if(i + 1u < nh) nxt = (uint32_t)hits[i + 1];
-			if(tv > last_v){
-				set_prev(i, last_i);
-				set_tail(len, i, tv); len ++;
-				last_v = tv; last_i = i;
-			} else if(tv <= first_v){
-				set_prev(i, KC_NONE);
-				set_tail(0, i, tv);
-				first_v = tv;
-				if(len == 1){ last_v = tv; last_i = i; }
-			} else {
-				uint32_t b = 0, e = len;
-				while(b < e){
-					const uint32_t m = b + ((e - b) >> 1), mv = tail_v(m);
-					if(tv > mv) b = m + 1;
-					else if(tv < mv) e = m;
-					else { b = m; break; }
-				}
-				if(b == 0 || b >= len) b = b == 0 ? 1 : len - 1;       // (cannot happen: first_v < tv <= last_v)
-				set_prev(i, get_prev(tail_i(b - 1)));                // as written in the reference: the predecessor of that tail, not the tail
-				set_tail(b, i, tv);
-				if(b == len - 1u){ last_v = tv; last_i = i; }
-			}
+	if constexpr (!AUTO){
+		kc_mark_hits<false>(src, nrec, (uint32_t*)dst, qlen, nq, ksz);
+		// the hits go to `src` (the sorted records are no longer needed)
+		kc_chain_hits((const uint32_t*)dst, src, dst, qlen, tlen, ksz, cmin, lds, red, &s_flag, [&](uint32_t c, const uint64_t *outp){
+			if(tid == 0){ cnt_out[pair] = c; res_off[pair] = P.slot + (size_t)((const uint8_t*)outp - (ws + P.slot)); }
+		});
+	} else {
+		// forward: the hits go behind the two halves, so the sorted records survive; the anchors follow them there
+		uint64_t *fwd = (uint64_t*)(ws + P.slot + 2u * half);
+		uint32_t cf = 0, cr = 0;
+		kc_mark_hits<false>(src, nrec, (uint32_t*)dst, qlen, nq, ksz);
+		kc_chain_hits((const uint32_t*)dst, fwd, dst, qlen, tlen, ksz, cmin, lds, red, &s_flag, [&](uint32_t c, const uint64_t *outp){
+			cf = c;
+			for(uint32_t i = tid; i < c; i += KC_THREADS) fwd[i] = outp[i];
+		});
+		__syncthreads();
+		// reverse: as the other kernels, the hits over the records
+		if(!bad){
+			kc_mark_hits<true>(src, nrec, (uint32_t*)dst, qlen, nq, ksz);
+			kc_chain_hits((const uint32_t*)dst, src, dst, qlen, tlen, ksz, cmin, lds, red, &s_flag, [&](uint32_t c, const uint64_t *){ cr = c; });
 		}
-		uint32_t cov = 0, e = KC_NONE, m = last_i;
-		while(m != KC_NONE && m < nh){
-			const uint32_t tf = (uint32_t)hits[m];
-			keep[m] = 1;
-			cov += (tf + ksz <= e) ? ksz : e - tf;
-			e = tf;
-			m = get_prev(m);
+		if(tid == 0){
+			const bool rv = cr > cf;                            // a tie is forward
+			cnt_out[pair] = rv ? cr : cf;
+			res_off[pair] = P.slot + (rv ? (size_t)((uint8_t*)dst - (ws + P.slot)) : 2u * half);
+			if(rv && status) status[pair] = st | BSA_ST_REVCOMP;
 		}
-		s_flag = cov >= cmin;
 	}
-	__syncthreads();
-	if(!s_flag) return;
-	// (e) the diagonal filter across the workgroup (a lane always looks at the same hits)
-	for(;;){
-		uint32_t e = 0, tot = 0;
-		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; tot += (uint32_t)(h >> 32) - (uint32_t)h; e ++; }
-		e = kc_block_sum(e, red);
-		tot = kc_block_sum(tot, red);
-		if(e * ksz < cmin) break;
-		const int mean = (int)tot / (int)e;
-		const uint32_t rank = e / 2u;
-		int lo = -(int)tlen, hi = (int)qlen;                    // the element of rank e / 2: the smallest v with more than `rank` diagonals <= v
-		while(lo < hi){
-			const int mid = lo + ((hi - lo) >> 1);
-			uint32_t c = 0;
-			for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){ const uint64_t h = hits[i]; c += (int)((uint32_t)(h >> 32) - (uint32_t)h) <= mid; }
-			c = kc_block_sum(c, red);
-			if(c > rank) hi = mid; else lo = mid + 1;
-		}
-		const int median = lo;
-		const int var = max(abs(median - mean) * 3, 50);
-		uint32_t dropped = 0;
-		for(uint32_t i = tid; i < nh; i += KC_THREADS) if(keep[i]){
-			const uint64_t h = hits[i];
-			const int d = (int)((uint32_t)(h >> 32) - (uint32_t)h);
-			if(abs(d - mean) > var){ keep[i] = 0; dropped ++; }
-		}
-		dropped = kc_block_sum(dropped, red);
-		if(dropped == 0) break;
-	}
-	__syncthreads();
-	// final compaction (in order) and the second coverage test
-	uint32_t w_tot;
-	{
-		const uint32_t per = (nh + KC_THREADS - 1u) / KC_THREADS;
-		const uint32_t b0 = min(tid * per, nh), e0 = min(b0 + per, nh);
-		uint32_t c = 0;
-		for(uint32_t i = b0; i < e0; i++) c += keep[i] != 0;
-		uint32_t w = kc_block_excl_scan(c, red, w_tot);
-		for(uint32_t i = b0; i < e0; i++) if(keep[i]) outp[w ++] = hits[i];
-	}
-	__syncthreads();
-	uint32_t cov = 0;
-	for(uint32_t i = tid; i < w_tot; i += KC_THREADS){
-		const uint32_t tf = (uint32_t)outp[i], e = i ? (uint32_t)outp[i - 1] + ksz : 0u;
-		cov += (tf >= e + ksz) ? ksz : tf + ksz - e;
-	}
-	cov = kc_block_sum(cov, red);
-	if(tid == 0){ cnt_out[pair] = cov < cmin ? 0u : w_tot; res_off[pair] = P.slot + (size_t)((uint8_t*)outp - (ws + P.slot)); }
 }
 
 // (f) exclusive scan of the per-pair counts (one workgroup; off has n + 1 entries) ...
@@ -353,20 +409,26 @@ static uint32_t kc_min_cover(uint32_t qlen, uint32_t tlen, uint32_t ksz){       
 	return std::min(c, 2 * ksz);
 }
 // what one pair needs of the scratch: its slice, its packed bytes, its share of the arena and of the tables
-static size_t kc_pair_bytes(uint32_t qlen, uint32_t tlen){
-	return 2u * kc_half_bytes(qlen, tlen) + 256u + ((size_t)qlen + tlen) + 8u * (size_t)std::min(qlen, tlen) + sizeof(KcPair) + 32u;
+// (automatic: a BSA_KMER_STRAND_AUTO launch, whose slice also keeps the forward strand's anchors behind the two halves)
+static inline size_t kc_auto_bytes(uint32_t qlen, uint32_t tlen){ return (8u * (size_t)std::min(qlen, tlen) + 15u) & ~(size_t)15u; }
+static size_t kc_pair_bytes(uint32_t qlen, uint32_t tlen, bool automatic){
+	return 2u * kc_half_bytes(qlen, tlen) + 256u + ((size_t)qlen + tlen) + 8u * (size_t)std::min(qlen, tlen) + sizeof(KcPair) + 32u + (automatic ? kc_auto_bytes(qlen, tlen) : 0u);
 }
 
 // Chains the pairs idx[0 .. m) on the device.  *arena_out (malloc'd, the caller frees it) holds their anchors packed, those of idx[j] at off[j] .. off[j + 1);
 // st (m entries, may be NULL) gets BSA_ST_EMPTY / BSA_ST_BAD_BASE; fits[j] = 0 marks a pair that alone is larger than the workspace (left to the host, no anchors
 // here).  *ms: the kernels' time by HIP events.
 // flags: BSA_MODE_SEQ2BIT -- seqs are 2-bit words and the offsets base offsets: a chunk uploads, for every read, the words that hold it, as they are (a
-// quarter of the bytes); BSA_MODE_QSTRAND -- bit 63 of qoff[k] marks the pair, the stored bytes or words go up unchanged and the kernel reads them mirrored.
+// quarter of the bytes); BSA_MODE_QSTRAND -- bit 63 of qoff[k] marks the pair, the stored bytes or words go up unchanged and the kernel reads them mirrored;
+// BSA_KMER_STRAND_AUTO (not with QSTRAND) -- the <PK, false, true> kernels, 8 min(qlen, tlen) more bytes a slice, and st[j] carries BSA_ST_REVCOMP where the
+// anchors are those of the reverse strand.
 extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint32_t *idx, size_t m, uint32_t ksz, uint32_t literal, uint32_t flags, uint64_t **arena_out, uint64_t *off, uint32_t *st, uint8_t *fits, double *ms){
-	const bool pk = (flags & BSA_MODE_SEQ2BIT) != 0, qs = (flags & BSA_MODE_QSTRAND) != 0;
+	const bool pk = (flags & BSA_MODE_SEQ2BIT) != 0, qs = (flags & BSA_MODE_QSTRAND) != 0, au = (flags & BSA_KMER_STRAND_AUTO) != 0;
+	if(au && qs) return BSA_E_ARG;
 	const uint64_t qmask = qs ? ~BSA_QOFF_REVCOMP : ~0ull;
-	auto kern = pk ? (qs ? k_kmer_chain<true, true> : k_kmer_chain<true, false>) : (qs ? k_kmer_chain<false, true> : k_kmer_chain<false, false>);
+	auto kern = au ? (pk ? k_kmer_chain<true, false, true> : k_kmer_chain<false, false, true>)
+		: pk ? (qs ? k_kmer_chain<true, true, false> : k_kmer_chain<true, false, false>) : (qs ? k_kmer_chain<false, true, false> : k_kmer_chain<false, false, false>);
 	*arena_out = nullptr; *ms = 0.0;
 	off[0] = 0;
 	if(ksz > 15) ksz = 15;
@@ -395,7 +457,7 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 		meta.clear();
 		while(j1 < m){
 			const uint32_t k = idx[j1], ql = qlen[k], tl = tlen[k];
-			const size_t need = kc_pair_bytes(ql, tl);
+			const size_t need = kc_pair_bytes(ql, tl, au);
 			if(need > budget){
 				if(j1 > j0) break;                    // close the chunk in front of it
 				fits[j1] = 0; off[j1 + 1] = off[j1]; if(st) st[j1] = 0;
@@ -411,7 +473,7 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 				P.toff = (uint64_t)seqb * 4u + (to & 31u); if(tl) seqb += (size_t)(((to & 31u) + tl + 31u) >> 5) * 8u;
 			} else { P.qoff = seqb; P.toff = seqb + ql; seqb += (size_t)ql + tl; }
 			meta.push_back(P);
-			slots += 2u * kc_half_bytes(ql, tl); acap += std::min(ql, tl); bytes += need;
+			slots += 2u * kc_half_bytes(ql, tl) + (au ? kc_auto_bytes(ql, tl) : 0u); acap += std::min(ql, tl); bytes += need;
 			j1 ++;
 		}
 		const size_t c = meta.size();

@@ -196,6 +196,9 @@ extern "C" {
                                     state longer than its bound (about two seconds) -- a fault, never an input property.  Result zeroed;
                                     bsa_align_batch returns BSA_E_HIP when any pair carries it.  bsa_align_run (device pointers) is
                                     asynchronous and returns BSA_OK: its caller finds the flag in the status array it passed. */
+#define BSA_ST_REVCOMP    16u   /* this call used the REVERSE COMPLEMENT of the stored query.  Set only by bsa_kmer_chain_batch2 /
+                                    bsa_kmer_edit_batch2 with BSA_KMER_STRAND_AUTO, which find the strand themselves; the bits above and the
+                                    upper half (band margin) keep their meaning. */
 
 /* == seqalign_result_t (bsalign.h:213-218): 10 x int32, [qb,qe) x [tb,te) half-open */
 typedef struct {
@@ -350,8 +353,8 @@ int      bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, const bsa_
  *                    difference but bsa_ctx_last_kmer_chain_ms.  Pairs go in chunks when the workspace does not hold them all.
  *                    Takes 1 B/base blobs and no strand marks: it IS bsa_kmer_chain_batch2 with flags 0, which takes BSA_MODE_SEQ2BIT blobs and
                     BSA_MODE_QSTRAND marks.  Neither takes device pointers.
- * bsa_kmer_chain_batch2: the same call with `flags`, a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND (any other bit: BSA_E_ARG), meaning exactly what they
- *                    mean for bsa_align_batch.  SEQ2BIT: seqs are BaseBank.bits words, qoff / toff BASE offsets (any offset), seqs_bytes a multiple of
+ * bsa_kmer_chain_batch2: the same call with `flags`, a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND | BSA_KMER_STRAND_AUTO (any other bit: BSA_E_ARG); the
+ *                    first two mean exactly what they mean for bsa_align_batch, the third is described at its definition below.  SEQ2BIT: seqs are BaseBank.bits words, qoff / toff BASE offsets (any offset), seqs_bytes a multiple of
  *                    8 and off + len <= 4 * seqs_bytes, else BSA_E_ARG; BSA_ST_BAD_BASE cannot occur.  QSTRAND: bit 63 of qoff[k]
  *                    (BSA_QOFF_REVCOMP) marks pair k, which then chains q', q'[i] = 3 - q[qlen - 1 - i], against t; bounds are tested on the masked
  *                    offset, and without the flag bit 63 is an offset outside the blob (BSA_E_ARG).  maps, maps_off and status are bit-identical to
@@ -397,7 +400,29 @@ int bsa_kmer_chain_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes
                                        and bsa_edit_batch runs with the same flags); heads and tails are decoded per pair on the host threads.  One
                                        definition: a marked pair whose stored 1 B/base query holds a code above 3 has no q' -- BSA_ST_BAD_BASE, an
                                        all-zero record, no CIGAR words; unmarked pairs with such a code behave as without the flags.
+                                       BSA_KMER_STRAND_AUTO (below) is the fourth flag.
                                        Any other bit is BSA_E_ARG: no BSA_MODE_CIGAR_EQX, BSA_MODE_SCORE_ONLY or other BSA_MODE_* flag is taken. */
+#define BSA_KMER_STRAND_AUTO 2u     /* flag of bsa_kmer_chain_batch2 and bsa_kmer_edit_batch2 (no collision with BSA_KMER_CHAIN_DEVICE 1, BSA_MODE_SEQ2BIT
+                                       0x800, BSA_MODE_QSTRAND 0x2000): the call FINDS each pair's strand.  With q the stored query, q' its reverse
+                                       complement (q'[i] = 3 - q[qlen - 1 - i]), F the anchors bsa_kmer_chain returns for (q, t) and R those for (q', t),
+                                       pair k is reverse exactly when |R| > |F|; a tie is forward, 0 against 0 included.  A reverse pair has
+                                       BSA_ST_REVCOMP in status[k], which is why status == NULL is BSA_E_ARG with the flag; together with
+                                       BSA_MODE_QSTRAND it is BSA_E_ARG, and bit 63 of qoff stays part of the offset (outside the blob: BSA_E_ARG).
+                                       Combines with BSA_MODE_SEQ2BIT.  An empty pair, a sequence shorter than ksz and a 1 B/base pair with a code
+                                       above 3 are forward and otherwise return what the call without the flag returns.
+                                       bsa_kmer_chain_batch2: maps, maps_off and status & ~BSA_ST_REVCOMP are bit-identical to the call with
+                                       BSA_MODE_QSTRAND and exactly the reverse pairs marked (query offsets of a reverse pair are positions in q');
+                                       BSA_E_CIGAR_CAP and maps_off[n] count the chosen strand's anchors.  On the device both strands share the one
+                                       sort: a run of two records with equal strand bits is a forward hit, with different bits (or a k-mer that is its
+                                       own reverse complement) a hit against q'.
+                                       bsa_kmer_edit_batch2, with or without BSA_KMER_CHAIN_DEVICE: step 1 chooses the strands, the rest is the
+                                       BSA_MODE_QSTRAND route on a private marked copy of qoff -- records (qb / qe in q' coordinates), CIGAR words and
+                                       cigar_off bit-identical to that call, status with BSA_ST_REVCOMP OR-ed in for the reverse pairs.
+                                       Not taken by bsa_align_* / bsa_edit_*, plans, device pointers, the CLI or the compat layer.  To align the
+                                       pairs on the strand found here, copy the bit into qoff and use BSA_MODE_QSTRAND there:
+                                           bsa_kmer_chain_batch2(ctx, ..., qoff, ..., maps, cap, maps_off, status, BSA_KMER_STRAND_AUTO);
+                                           for(k = 0; k < n; k++) if(status[k] & BSA_ST_REVCOMP) qoff[k] |= BSA_QOFF_REVCOMP;
+                                           par.mode |= BSA_MODE_QSTRAND; bsa_align_batch(ctx, ..., qoff, ..., &par, out, cigar, cap, cigar_off, status); */
 int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                          const uint64_t *qoff, const uint32_t *qlen,
                          const uint64_t *toff, const uint32_t *tlen, size_t n,
