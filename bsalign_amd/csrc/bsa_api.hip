@@ -1372,7 +1372,9 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 			if(rc != BSA_OK) return;
 			const uint64_t t = cigar_off[k0 + m];
 			*tot_out = t;
-			if(base + t > cigar_cap_words){ c->err = "cigar arena too small"; rc = BSA_E_CIGAR_CAP; return; }
+			// (cigar_off[n]: the words needed.  When it is slice B that does not fit, cigar_off[nA + 1 .. n - 1] stay slice B's own offsets, without
+			// slice A's total: on BSA_E_CIGAR_CAP only cigar_off[n] means anything, the array as a whole is not monotone)
+			if(base + t > cigar_cap_words){ cigar_off[k0 + m] = base + t; c->err = "cigar arena too small"; rc = BSA_E_CIGAR_CAP; return; }
 			SL(par_copy(c->device, cigar + base, d_cig, t * 4, hipMemcpyDeviceToHost));
 			if(base) for(size_t k = k0 + 1; k <= k0 + m; k++) cigar_off[k] += base;
 		}
@@ -1382,6 +1384,15 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	collect(doneA, 0, nA, d_offA, d_cigA, 0, &totA);
 	t_colA = since();
 	if(rc == BSA_OK) collect(doneB, nA, nB, d_offB, d_cigB, totA, &totB);
+	else if(rc == BSA_E_CIGAR_CAP){
+		// slice A alone does not fit: the caller still gets the words the whole batch needs in cigar_off[n] -- slice B's total is on the device
+		// (its run is queued whatever the capacity; its offsets do not depend on it)
+		hipError_t e = hipStreamWaitEvent(dns, doneB, 0);
+		if(e == hipSuccess) e = hipMemcpyAsync(&totB, d_offB + nB, sizeof(uint64_t), hipMemcpyDeviceToHost, dns);
+		if(e == hipSuccess) e = hipStreamSynchronize(dns);
+		if(e != hipSuccess){ c->err = std::string("slice B's CIGAR total: ") + hipGetErrorString(e); rc = BSA_E_HIP; }
+		else cigar_off[n] = totA + totB;
+	}
 	t_colB = since();
 	if(tmg) fprintf(stderr, "[bsa_align_batch] %zu pairs in two slices of %zu and %zu (uploads of %zu and %zu intervals): ms since entry -- buffers %.1f, plan of slice A %.1f, slice A launched + slice B planned + uploads issued %.1f, both runs launched %.1f, slice A back %.1f, slice B back %.1f\n",
 		n, nA, nB, ivA.size(), ivB.size(), t_alloc, t_plan, t_join, t_launch, t_colA, t_colB);

@@ -648,10 +648,9 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	const bool want_cig = cigar != nullptr && cigar_off != nullptr;
 	std::vector<uint32_t> scratch;
 	uint32_t *work = cigar;
-	if(!want_cig || need[n] > cigar_cap_words){
-		if(want_cig){ cigar_off[n] = need[n]; return BSA_E_CIGAR_CAP; }      // the words a retry needs (bsalign_hip.h)
-		scratch.resize(need[n] + 1); work = scratch.data();
-	}
+	// (need[] counts every anchor run as a word of its own; assemble merges runs, so the arena is short only if the merged words do not fit:
+	// stitched in scratch space first where the upper bound does not fit)
+	if(!want_cig || need[n] > cigar_cap_words){ scratch.resize(need[n] + 1); work = scratch.data(); }
 	std::vector<uint64_t> used(n, 0);
 	std::atomic<int> bad(BSA_OK);
 	parallel_for(n, par->threads, [&](size_t k){
@@ -674,7 +673,18 @@ static int kmer_edit_batch_impl(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs
 	if(timing) fprintf(stderr, "[bsa_kmer] %zu pairs: chain %.1f ms, pack %.1f ms (%zu heads and tails, %zu gaps), device %.1f ms, stitch %.1f ms\n",
 		n, ms(t0, t1), ms(t1, t2), job[0].ql.size(), job[1].ql.size(), ms(t2, t3), ms(t3, now()));
 	if(timing && dev) fprintf(stderr, "[bsa_kmer]   chained on the device: %ld pairs, kernels %.2f ms; on the host: %ld pairs\n", D.on_device, D.ms, D.on_host);
-	if(want_cig){
+	if(want_cig && work != cigar){
+		uint64_t w = 0;
+		for(size_t k = 0; k < n; k++) w += used[k];
+		if(w > cigar_cap_words){ cigar_off[n] = w; return BSA_E_CIGAR_CAP; }      // the words a retry needs (bsalign_hip.h)
+		w = 0;
+		for(size_t k = 0; k < n; k++){
+			cigar_off[k] = w;
+			if(used[k]) memcpy(cigar + w, work + need[k], used[k] * sizeof(uint32_t));
+			w += used[k];
+		}
+		cigar_off[n] = w;
+	} else if(want_cig){
 		/* close the gaps left by merged match runs so that pair k owns cigar[cigar_off[k] .. cigar_off[k+1]) */
 		uint64_t w = 0;
 		for(size_t k = 0; k < n; k++){

@@ -282,6 +282,22 @@ int  bsa_align_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t 
 void bsa_align_plan_destroy(bsa_align_plan_t *plan);
 /* total band cells of the plan: sum over pairs of tlen * bw_eff (the GCUPS numerator) */
 double bsa_align_plan_cells(const bsa_align_plan_t *plan);
+/* bsa_align_run is asynchronous and returns BSA_OK before a kernel has run, so it cannot report a CIGAR arena that is too small: the caller
+ * compares d_cigar_off[n] with its capacity after the run.  With device pointers and ANY cigar_cap_words, short or not (0 with a non-NULL
+ * d_cigar included):
+ *   - d_out, d_status and all n + 1 entries of d_cigar_off are exactly those of a run with a large arena; every element of the three is
+ *     written by every run (zero records and BSA_ST_* flags for the pairs without a result), whatever the buffers held;
+ *   - d_cigar_off[n] is the number of words needed;
+ *   - no word at an index at or above cigar_cap_words is touched, and none at or above d_cigar_off[n];
+ *   - every pair's range [d_cigar_off[k], d_cigar_off[k + 1]) inside the arena holds either exactly that pair's words or is untouched;
+ *   - with cigar_cap_words >= d_cigar_off[n] every pair is there;
+ *   - a plan of one workspace chunk on one stream (the words go straight from the walkers' slots to the arena) writes every pair whose
+ *     words end inside the arena;
+ *   - on the other routes (several chunks, the two-stream pipeline, BSA_CIGAR_VIA_ARENA) the words pass through a staging arena of
+ *     cigar_cap_words in processing order, so a pair can fit by pair order and not by processing order: WHICH of the fitting pairs are
+ *     present after an overflow is unspecified.  Do not use a short run's words; run again with d_cigar_off[n] words.
+ * A run leaves nothing behind that a later run reads: a plan may be run again on other sequences of the same lengths, after a short run,
+ * and in turn with other plans of the same context.  bsa_edit_run has the same contract. */
 int  bsa_align_run(bsa_align_plan_t *plan, const uint8_t *d_seqs,
                    bsa_result_t *d_out, uint32_t *d_cigar, size_t cigar_cap_words,
                    uint64_t *d_cigar_off, uint32_t *d_status);
@@ -300,6 +316,7 @@ int  bsa_edit_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t *
                           const bsa_edit_params_t *par, bsa_edit_plan_t **out);
 void bsa_edit_plan_destroy(bsa_edit_plan_t *plan);
 double bsa_edit_plan_cells(const bsa_edit_plan_t *plan);
+/* the arena and re-run contract stated at bsa_align_run holds here word for word */
 int  bsa_edit_run(bsa_edit_plan_t *plan, const uint8_t *d_seqs,
                   bsa_result_t *d_out, uint32_t *d_cigar, size_t cigar_cap_words,
                   uint64_t *d_cigar_off, uint32_t *d_status);
@@ -309,7 +326,10 @@ int  bsa_edit_run(bsa_edit_plan_t *plan, const uint8_t *d_seqs,
  * between consecutive anchors are aligned, every one of them by the device edit path (two bsa_edit_batch calls for
  * the whole batch: reversed heads and tails in EXTEND mode, gaps in GLOBAL mode), and the CIGAR of each pair is stitched together exactly as the
  * reference does it (including where it puts the anchor matches).  A pair without a usable chain is aligned globally.
- * All pointers are HOST memory; cigar/cigar_off/status follow bsa_edit_batch. */
+ * All pointers are HOST memory; cigar/cigar_off/status follow bsa_edit_batch.
+ * BSA_E_CIGAR_CAP (bsa_kmer_edit_batch and bsa_kmer_edit_batch2): the capacity is compared with the words of the STITCHED CIGARs, in which neighbouring
+ * match runs are merged, and cigar_off[n] is that number -- a call with that capacity succeeds.  The error comes after the stitching: out[] and
+ * status[] are already written then; cigar and cigar_off[0 .. n - 1] are not. */
 typedef struct {
 	uint32_t ksz;        /* k-mer size, values above 15 mean 15 (bsalign.h:1217); the CLI default is 13 (main.c:141) */
 	uint32_t threads;    /* host threads for chaining and stitching; 0 = all hardware threads (or $BSA_KMER_THREADS) */
