@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import poa_support as P
+import rows_sat_cases as RS
 import support as S
 
 pytestmark = pytest.mark.gpu
@@ -140,3 +141,42 @@ def test_synthetic_programs_match_oracle(ctx, bw, mode):
         b = orows[b0 * blk:(b0 + nb) * blk].reshape(nb, blk)[1:, :used]
         bad = np.nonzero((a != b).any(axis=1))[0]
         assert len(bad) == 0, (bw, mode, i, "first differing block", int(bad[0]) + 1)
+
+
+@pytest.mark.parametrize("mode", RS.MODES)
+@pytest.mark.parametrize("name,bw", [(n, bw) for n in RS.SETS for bw in ((256,) if n in RS.WIDE_SETS else RS.SWEEP_BANDWIDTHS)])
+def test_synthetic_programs_match_oracle_outside_the_guard(ctx, name, bw, mode):
+    """test_synthetic_programs_match_oracle's scheme under the scorings of rows_sat_cases.SETS (each refused by the graph kernels' guard), in
+    the register forms (16, 64, 256 columns) and the run-time-width form (176, 512): 24 programs of 50 - 300 nodes, slen in [bw + 50, bw + 400],
+    some ending with rpos + bw == slen (the byte-wise tail of rows_fetch_codes and the cells beyond the read's end under clamped scores).  Rows block
+    for block, and bsa_sweep_result_t (SCORE_TAIL / SCORE_END, strictly greater wins) exactly.  The share of rows that clamp is asserted per set
+    as rows_sat_cases.check_share states it.  wide_ext_e4 / wide_ext_e9 rest on the refusal of bsa_poa_graph_supported alone."""
+    import bsalign_amd as B
+    sb = RS.sweep_batch(name, bw, mode)
+    RS.assert_outside_guard(name, bw, B.lib(), int(sb["qlen"].max()))       # (above 256 columns k_poa_wf declines by the width; k_poa_gen by the scores)
+    assert sb["ends"] >= 8
+    RS.check_share(name, bw, mode, sb["share"])
+    rows, res = ctx.sweep_host(sb["tasks"], sb["progs"], sb["queries"], sb["qoff"], sb["qlen"], _sweep_params(sb["sc"], bw), sb["nblocks"])
+    assert np.array_equal(res, sb["ores"]), [(i, res[i], sb["ores"][i]) for i in range(len(res)) if res[i] != sb["ores"][i]][:3]
+    blk, used = sb["blk"], RS.used_bytes(bw, sb["pw"])
+    a = rows.reshape(sb["nblocks"], blk)[:, :used]
+    b = sb["orows"].reshape(sb["nblocks"], blk)[:, :used]
+    scratch = np.zeros(sb["nblocks"], bool)
+    scratch[sb["progs"]["first_block"]] = True                  # block 0 of every program: the moved row of the run-time-width form
+    bad = np.nonzero((a != b).any(axis=1) & ~scratch)[0]
+    assert len(bad) == 0, (name, bw, mode, "first differing block", int(bad[0]))
+
+
+def test_merge_program_at_8192_columns(ctx):
+    """W = 512: the re-basing of row_merge every 256 vectors (bsalign.h:2496) in rows_task_gen, on the program whose blocks the reference
+    recorded (tests/golden/rows_sat.npz) -- the device against the reference directly, and against the oracle's result"""
+    _, mp, merge = RS.load_fixture()
+    bw, pw = RS.MERGE_BW, RS.piecewise(mp["sc"], RS.MERGE_BW)
+    progs = np.array([(0, len(mp["tasks"]), 0, 0)], dtype=P.PROG_DTYPE)
+    qoff, qlen = np.zeros(1, np.uint64), np.array([mp["slen"]], np.uint32)
+    rows, res = ctx.sweep_host(mp["tasks"], progs, mp["query"], qoff, qlen, _sweep_params(mp["sc"], bw), mp["nblocks"])
+    blk, used = P.block_bytes(bw, pw), RS.used_bytes(bw, pw)
+    for k, want in merge.items():
+        assert np.array_equal(rows[k * blk:k * blk + used], want), ("block", k)
+    orows, ores = P.oracle_sweep(mp["tasks"], progs, mp["query"], qoff, qlen, mp["sc"], bw, mp["nblocks"], pw)
+    assert np.array_equal(res, ores)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import poa_support as P
+import rows_sat_cases as RS
 import support as S
 
 pytestmark = pytest.mark.gpu
@@ -155,3 +157,123 @@ def test_row_tasks_match_oracle(ctx, gaps, bw):
         dst = (c + 1) * (depth + 2) + depth
         used = (pw + 1) * bw + 68
         assert np.array_equal(got[dst * blk:dst * blk + used], rows[dst * blk:dst * blk + used]), ("merge", gaps, bw, c)
+
+
+# ---- outside the exactness guard of the POA graph kernels (tests/rows_sat_cases.py) ---------------------------------------------------
+def _run_rows(ctx, d_rows, tasks, d_q, d_qoff, d_qlen, par):
+    import bsalign_amd as B
+    t = np.array(tasks, dtype=B.ROW_TASK_DTYPE)
+    d_t = torch.from_numpy(t.view(np.uint8)).cuda()
+    rc = B.lib().bsa_rows_run(ctx.h, C.c_void_p(d_rows.data_ptr()), C.c_void_p(d_t.data_ptr()), len(t), C.c_void_p(d_q.data_ptr()),
+                              C.c_void_p(d_qoff.data_ptr()), C.c_void_p(d_qlen.data_ptr()), C.byref(par))
+    assert rc == 0
+    ctx.sync()
+    torch.cuda.synchronize()
+
+
+def _chains_on_the_device(ctx, name, bw, mode):
+    """rows_sat_cases.chains (24 chains x 20 levels, then merges of chain pairs; left-boundary rh with both gap pieces for piecewise 2, as
+    bspoa.h:2243-2255) level by level through bsa_rows_run: every used byte of every destination block after each level"""
+    import bsalign_amd as B
+    ch = RS.chains(name, bw, mode)
+    sc, blk, used = ch["sc"], ch["blk"], RS.used_bytes(bw, ch["pw"])
+    assert B.lib().bsa_rows_block_bytes(bw, *RS.gaps(sc)) == blk
+    d_rows = torch.zeros(ch["nrows"] * blk, dtype=torch.uint8, device="cuda:0")
+    d_q = torch.from_numpy(ch["qblob"]).cuda()
+    d_qoff = torch.from_numpy(ch["qoff"].view(np.int64)).cuda()
+    d_qlen = torch.from_numpy(ch["qlen"].view(np.int32)).cuda()
+    par = B.RowsParams(mode, bw, sc["M"], sc["X"], sc["refbonus"], *RS.gaps(sc))
+    for lev, (tasks, exp) in enumerate(ch["levels"]):
+        _run_rows(ctx, d_rows, tasks, d_q, d_qoff, d_qlen, par)
+        got = d_rows.cpu().numpy()
+        for tk, (dst, want) in zip(tasks, exp):
+            assert np.array_equal(got[dst * blk:dst * blk + used], want), (name, bw, mode, "level", lev, tk)
+    return ch
+
+
+@pytest.mark.parametrize("mode", RS.MODES)
+@pytest.mark.parametrize("name,bw", [(n, bw) for n in RS.SETS for bw in RS.bandwidths(n)])
+def test_row_tasks_match_oracle_outside_the_guard(ctx, name, bw, mode):
+    """the saturating, lane-exact arithmetic of rows_update / rows_merge / rows_task_gen where it does clamp and wrap: the sets of
+    rows_sat_cases.SETS, each refused by bsa_poa_graph_supported (and, but for the two wide_ext sets, by bsa_poa_graph_gen_supported)"""
+    import bsalign_amd as B
+    RS.assert_outside_guard(name, bw, B.lib(), bw + 700)
+    ch = _chains_on_the_device(ctx, name, bw, mode)
+    RS.check_share(name, bw, mode, ch["share"])
+
+
+@pytest.mark.parametrize("mode", RS.MODES)
+@pytest.mark.parametrize("bw", RS.BANDWIDTHS)
+def test_row_tasks_match_oracle_default_scoring_every_mode(ctx, bw, mode):
+    """test_row_tasks_match_oracle's scoring family (the POA's defaults) at bandwidth 32 as well, and in global and extend mode"""
+    _chains_on_the_device(ctx, "default", bw, mode)
+
+
+def test_recorded_reference_rows_replayed(ctx):
+    """tests/golden/rows_sat.npz through bsa_rows_run: every recorded step as one UPDATE task on the reference's own previous row (its result
+    against the reference's row after row_cal) and one MERGE task on the reference's moved and new row -- the device against the reference
+    directly, without the oracle in between"""
+    import bsalign_amd as B
+    recs = RS.load_fixture()[0]
+    groups = {}
+    for c, rows in recs:
+        groups.setdefault((c["name"], c["bw"], c["mode"]), []).append((c, rows))
+    for (name, bw, mode), chains in groups.items():
+        sc = chains[0][0]["sc"]
+        pw = RS.piecewise(sc, bw)
+        blk, used = P.block_bytes(bw, pw), RS.used_bytes(bw, pw)
+        host, upd, mrg, want = [], [], [], {}
+        qlen = np.array([len(c["query"]) for c, _ in chains], np.uint32)
+        qoff = np.zeros(len(chains), np.uint64)
+        qoff[1:] = np.cumsum(qlen + 8)[:-1]
+        qblob = np.zeros(int(qoff[-1]) + int(qlen[-1]) + 8, np.uint8)
+
+        def put(b):
+            host.append(np.concatenate([b, np.zeros(blk - used, np.uint8)]))
+            return len(host) - 1
+
+        for qi, (c, rows) in enumerate(chains):
+            qblob[int(qoff[qi]):int(qoff[qi]) + len(c["query"])] = c["query"]
+            rbeg = 0
+            for st, (movx, base, prof, _) in enumerate(c["steps"]):
+                src = put(rows[0] if st == 0 else rows[2 + 4 * (st - 1)])
+                dst = put(np.zeros(used, np.uint8))
+                upd.append((0, src, dst, rbeg, rbeg + movx, st, qi, base, prof, 0))
+                want[dst] = rows[2 + 4 * st]
+                rbeg += movx
+                a, b = put(rows[1 + 4 * st]), put(rows[2 + 4 * st])
+                mrg.append((1, a, b, 0, 0, 0, 0, 0, 0, 0))
+                want[b] = rows[3 + 4 * st]
+        d_rows = torch.from_numpy(np.concatenate(host)).cuda()
+        d_q = torch.from_numpy(qblob).cuda()
+        d_qoff = torch.from_numpy(qoff.view(np.int64)).cuda()
+        d_qlen = torch.from_numpy(qlen.view(np.int32)).cuda()
+        par = B.RowsParams(mode, bw, sc["M"], sc["X"], sc["refbonus"], *RS.gaps(sc))
+        _run_rows(ctx, d_rows, upd + mrg, d_q, d_qoff, d_qlen, par)
+        got = d_rows.cpu().numpy()
+        for dst, w in want.items():
+            assert np.array_equal(got[dst * blk:dst * blk + used], w), (name, bw, mode, "block", dst, (upd + mrg)[[t[2] for t in upd + mrg].index(dst)])
+
+
+def test_merge_where_int16_saturates(ctx):
+    """rows_sat_cases.draw_merge_s16_cases as recorded in tests/golden/rows_sat.npz: one MERGE task per pair at 4096 columns (W = 256, the
+    run-time-width form), where the int16 sums of row_merge reach -32768 -- the device against the reference's merged row directly"""
+    import bsalign_amd as B
+    cases = RS.load_s16_cases()
+    bw, sc = RS.S16_BW, RS.MERGE_SC
+    assert RS.piecewise(sc, bw) == 1
+    blk, used = P.block_bytes(bw, 1), RS.used_bytes(bw, 1)
+    assert B.lib().bsa_rows_block_bytes(bw, *RS.gaps(sc)) == blk and cases[0][0].shape == (used,)
+    host = np.zeros((2 * len(cases), blk), np.uint8)
+    for k, (a, b, _) in enumerate(cases):
+        host[2 * k, :used], host[2 * k + 1, :used] = a, b
+    d_rows = torch.from_numpy(host.reshape(-1)).cuda()
+    d_q = torch.zeros(64, dtype=torch.uint8, device="cuda:0")
+    d_qoff = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    d_qlen = torch.full((1,), 64, dtype=torch.int32, device="cuda:0")
+    par = B.RowsParams(sc["alnmode"], bw, sc["M"], sc["X"], sc["refbonus"], *RS.gaps(sc))
+    _run_rows(ctx, d_rows, [(1, 2 * k, 2 * k + 1, 0, 0, 0, 0, 0, 0, 0) for k in range(len(cases))], d_q, d_qoff, d_qlen, par)
+    got = d_rows.cpu().numpy().reshape(-1, blk)
+    for k, (a, _, want) in enumerate(cases):
+        assert np.array_equal(got[2 * k, :used], a), ("source block", k)
+        assert np.array_equal(got[2 * k + 1, :used], want), ("merged block", k, int(np.nonzero(got[2 * k + 1, :used] != want)[0][0]))
