@@ -165,6 +165,14 @@ def lib():
         L.bsa_kmer_chain_batch2.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.c_uint32,
                                             u64p, C.c_size_t, u64p, u32p, C.c_uint32]
         L.bsa_ctx_last_kmer_chain_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        L.bsa_kmer_chain_plan_create.argtypes = [vp, u64p, u32p, u64p, u32p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        L.bsa_kmer_chain_plan_destroy.argtypes = [vp]
+        L.bsa_kmer_chain_plan_destroy.restype = None
+        L.bsa_kmer_chain_plan_chunks.argtypes = [vp]
+        L.bsa_kmer_chain_plan_chunks.restype = C.c_uint32
+        L.bsa_kmer_chain_words_bound.argtypes = [u32p, u32p, C.c_size_t]
+        L.bsa_kmer_chain_words_bound.restype = C.c_uint64
+        L.bsa_kmer_chain_run.argtypes = [vp, u8p, u64p, C.c_size_t, u64p, u32p]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -585,7 +593,8 @@ class Context:
         return (res, status[:n]) if with_status else res
 
     def last_kmer_chain_ms(self):
-        """(kernel ms, pairs chained on the device, pairs chained on the host) of the last kmer_chain_batch / kmer_edit_batch(device_chain=True)"""
+        """(kernel ms, pairs chained on the device, pairs chained on the host) of the last kmer_chain_batch / kmer_edit_batch(device_chain=True),
+        or of the last KmerChainPlan.run (waits for that run's last chunk)"""
         ms, a, b = C.c_double(), C.c_long(), C.c_long()
         self._chk(lib().bsa_ctx_last_kmer_chain_ms(self.h, C.byref(ms), C.byref(a), C.byref(b)))
         return ms.value, a.value, b.value
@@ -679,6 +688,55 @@ class EditPlan:
     def close(self):
         if self.h:
             lib().bsa_edit_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kmer_chain_words_bound(qlen, tlen):
+    """bsa_kmer_chain_words_bound: sum of min(qlen, tlen), an anchor arena (64-bit words) that always suffices; host only"""
+    qlen, tlen = _np(qlen, np.uint32), _np(tlen, np.uint32)
+    if len(qlen) != len(tlen):
+        raise ValueError("kmer_chain_words_bound: one tlen per qlen")
+    return int(lib().bsa_kmer_chain_words_bound(_p(qlen), _p(tlen), len(qlen)))
+
+
+class KmerChainPlan:
+    """bsa_kmer_chain_plan_create / bsa_kmer_chain_run: kmer_chain_batch for a blob that is already on the device -- host metadata once, device
+    pointers per run (torch tensors, plumbing only), asynchronous on the context's stream.  flags: MODE_SEQ2BIT (d_seqs 2-bit packed words,
+    8-byte aligned, base offsets), MODE_QSTRAND (QOFF_REVCOMP in qoff[k]) or KMER_STRAND_AUTO (d_status required; ST_REVCOMP marks the reverse pairs).
+    qoff / toff are offsets into d_seqs as the caller holds it; that they lie inside it is the caller's business.  Raises BsaError(-6) for a pair
+    the device route does not take (qlen + tlen above 262144, or a slice larger than the workspace limit): there is no host route behind a run."""
+
+    def __init__(self, ctx, qoff, qlen, toff, tlen, ksz=13, flags=0):
+        self.ctx = ctx
+        self.n = len(qlen)
+        self.qoff, self.qlen = _np(qoff, np.uint64), _np(qlen, np.uint32)
+        self.toff, self.tlen = _np(toff, np.uint64), _np(tlen, np.uint32)
+        self.ksz, self.flags = ksz, flags
+        h = C.c_void_p()
+        ctx._chk(lib().bsa_kmer_chain_plan_create(ctx.h, _p(self.qoff), _p(self.qlen), _p(self.toff), _p(self.tlen), self.n, ksz, flags, C.byref(h)))
+        self.h = h
+
+    def chunks(self):
+        """workspace chunks one run goes through"""
+        return int(lib().bsa_kmer_chain_plan_chunks(self.h))
+
+    def run(self, d_seqs, d_maps, d_maps_off, d_status=None):
+        """d_maps: the anchor arena (its numel() 64-bit words are the capacity) or None for a count-only run; d_maps_off: n + 1 64-bit words;
+        d_status: n 32-bit words or None.  Pair k's anchors are d_maps[d_maps_off[k] : d_maps_off[k + 1]] where d_maps_off[k + 1] <= capacity;
+        d_maps_off[n] is the number of words a complete run needs."""
+        cap = d_maps.numel() if d_maps is not None else 0
+        self.ctx._chk(lib().bsa_kmer_chain_run(self.h, C.c_void_p(d_seqs.data_ptr()), C.c_void_p(d_maps.data_ptr() if d_maps is not None else 0), cap,
+                                               C.c_void_p(d_maps_off.data_ptr()), C.c_void_p(d_status.data_ptr() if d_status is not None else 0)))
+
+    def close(self):
+        if self.h:
+            lib().bsa_kmer_chain_plan_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -42,6 +42,8 @@ struct bsa_ctx {
 	long last_handover = 0;              // pairs the last bsa_align_batch re-ran through the literal kernels
 	double diagdp_ms = 0;
 	double kmer_chain_ms = 0; long kmer_on_device = 0, kmer_on_host = 0;      // last bsa_kmer_chain_batch / bsa_kmer_edit_batch2 (bsa_ctx_last_kmer_chain_ms)
+	std::vector<hipEvent_t> kev;     // ... or, after bsa_kmer_chain_run (asynchronous), a (start, stop) pair a workspace chunk, read when the time is asked for
+	size_t kev_used = 0;
 	// small device buffers kept between calls (slot 0: a plan's metadata pool, slot 1: the host-pointer wrapper's buffers): a batch
 	// of one pair otherwise spends more time in hipMalloc / hipFree than in its kernels
 	size_t budget_last = 0;          // last answer of ctx_ws_budget
@@ -145,6 +147,7 @@ extern "C" void bsa_ctx_destroy(bsa_ctx_t *c){
 	for(hipEvent_t e : c->sev) (void)hipEventDestroy(e);
 	for(hipEvent_t e : c->tev) (void)hipEventDestroy(e);
 	for(hipEvent_t e : c->mev) (void)hipEventDestroy(e);
+	for(hipEvent_t e : c->kev) (void)hipEventDestroy(e);
 	if(c->ws) (void)hipFree(c->ws);
 	for(int k = 0; k < 2; k++) if(c->keep[k]) (void)hipFree(c->keep[k]);
 	for(int k = 0; k < 3; k++) if(c->scratch[k]) (void)hipFree(c->scratch[k]);
@@ -1650,10 +1653,37 @@ extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *c, hipStream_t *st){
 extern "C" size_t bsa_ctx_workspace_limit_internal(bsa_ctx_t *c){ return c ? c->ws_limit : 0; }
 extern "C" void bsa_ctx_set_kmer_chain_stats_internal(bsa_ctx_t *c, double ms, long on_device, long on_host){
 	if(!c) return;
-	c->kmer_chain_ms = ms; c->kmer_on_device = on_device; c->kmer_on_host = on_host;
+	c->kmer_chain_ms = ms; c->kmer_on_device = on_device; c->kmer_on_host = on_host; c->kev_used = 0;
 }
+// bsa_kmer_chain_run (bsa_kmer_dev.hip) cannot wait for its kernels: it records a (start, stop) pair of the context's events around every chunk, *ev gets
+// 2 * chunks of them, and bsa_ctx_last_kmer_chain_ms adds them up when it is asked
+extern "C" int bsa_ctx_kmer_chain_events_internal(bsa_ctx_t *c, size_t chunks, long on_device, hipEvent_t **ev){
+	if(!c || !ev) return BSA_E_ARG;
+	(void)hipSetDevice(c->device);
+	while(c->kev.size() < 2 * chunks){
+		hipEvent_t e;
+		HIPCHK(c, hipEventCreate(&e));
+		c->kev.push_back(e);
+	}
+	c->kev_used = 2 * chunks;
+	c->kmer_chain_ms = 0; c->kmer_on_device = on_device; c->kmer_on_host = 0;
+	*ev = c->kev.data();
+	return BSA_OK;
+}
+extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *c, const char *msg){ if(c) c->err = msg ? msg : ""; }
 extern "C" int bsa_ctx_last_kmer_chain_ms(bsa_ctx_t *c, double *ms, long *pairs_on_device, long *pairs_on_host){
 	if(!c) return BSA_E_ARG;
+	if(c->kev_used){
+		(void)hipSetDevice(c->device);
+		HIPCHK(c, hipEventSynchronize(c->kev[c->kev_used - 1]));
+		double tot = 0;
+		for(size_t i = 0; i + 1 < c->kev_used; i += 2){
+			float t = 0;
+			HIPCHK(c, hipEventElapsedTime(&t, c->kev[i], c->kev[i + 1]));
+			tot += t;
+		}
+		c->kmer_chain_ms = tot; c->kev_used = 0;
+	}
 	if(ms) *ms = c->kmer_chain_ms;
 	if(pairs_on_device) *pairs_on_device = c->kmer_on_device;
 	if(pairs_on_host) *pairs_on_host = c->kmer_on_host;

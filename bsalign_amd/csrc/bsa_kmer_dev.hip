@@ -37,8 +37,10 @@
 // a pair with a base code above 3 is chained forward only.
 #include "bsa_common.h"
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -545,5 +547,182 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 	if(!a) return BSA_E_NOMEM;
 	if(!arena.empty()) memcpy(a, arena.data(), arena.size() * sizeof(uint64_t));
 	*arena_out = a;
+	return BSA_OK;
+}
+
+// ---- the resident form: bsa_kmer_chain_plan_create / bsa_kmer_chain_run -------------------------------------------------------------------------
+// The same k_kmer_chain kernels read the CALLER's device blob in place (KcPair.qoff / toff are the caller's offsets), the pair tables go up once when the
+// plan is made, and a run is launches on the context stream and nothing else: per workspace chunk the chain kernel, k_kmer_scan_carry and
+// k_kmer_gather_whole, which writes straight into the caller's arena.  Stream order is all that keeps chunk c + 1 from the slices chunk c still gathers from.
+extern "C" int bsa_ctx_kmer_chain_events_internal(bsa_ctx_t *ctx, size_t chunks, long on_device, hipEvent_t **ev);
+extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *ctx, const char *msg);
+
+// (f) for a chunk of a plan: the exclusive scan of its counts in 64 bits, carried from chunk to chunk through the caller's array.  `off` points at the chunk's
+// first entry: off[0] is what the chunk before wrote there as its total (the first chunk writes the 0 itself), off[i + 1] = off[0] + cnt[0] + .. + cnt[i].
+// One workgroup; the counts of a chunk add up to less than 2^31 (the plan cuts its chunks that way), the totals across chunks do not have to.
+__global__ __launch_bounds__(KC_THREADS) void k_kmer_scan_carry(const uint32_t *__restrict__ cnt, uint64_t *off, uint32_t n, uint32_t first){
+	__shared__ uint32_t red[KC_THREADS / 64];
+	const uint32_t tid = threadIdx.x, per = (n + KC_THREADS - 1u) / KC_THREADS;
+	const uint32_t b0 = min(tid * per, n), e0 = min(b0 + per, n);
+	const uint64_t base = first ? 0ull : off[0];              // (off[0] is read by every lane and written by none unless `first`, and then read by none)
+	uint32_t c = 0, total;
+	for(uint32_t i = b0; i < e0; i++) c += cnt[i];
+	uint32_t w = kc_block_excl_scan(c, red, total);
+	for(uint32_t i = b0; i < e0; i++){ w += cnt[i]; off[i + 1] = base + w; }
+	if(first && tid == 0) off[0] = 0;
+}
+// ... and the gather into the CALLER's arena (off: the chunk's first entry, as above).  A pair is written whole or not at all: all of its words when its range
+// ends inside the arena (off[pair + 1] <= arena_cap), none otherwise -- so nothing at or above arena_cap is touched, nor anything at or above the last
+// offset, and with arena_cap == 0 `arena` is never dereferenced (it may be NULL: a count-only run).
+__global__ __launch_bounds__(KC_THREADS) void k_kmer_gather_whole(const uint8_t *__restrict__ ws, const uint64_t *__restrict__ res_off, const uint32_t *__restrict__ cnt,
+		const uint64_t *__restrict__ off, uint64_t *arena, uint64_t arena_cap){
+	const uint32_t pair = blockIdx.x, c = cnt[pair];
+	const uint64_t o = off[pair];
+	if(c == 0 || o + c > arena_cap) return;
+	const uint64_t *s = (const uint64_t*)(ws + res_off[pair]);
+	for(uint32_t i = threadIdx.x; i < c; i += KC_THREADS) arena[o + i] = s[i];
+}
+
+// what one pair of a plan needs of the scratch: kc_pair_bytes without the packed sequence bytes and the staged arena (the kernels read the caller's blob and
+// write the caller's arena)
+static size_t kc_plan_pair_bytes(uint32_t qlen, uint32_t tlen, bool automatic){
+	return 2u * kc_half_bytes(qlen, tlen) + 256u + sizeof(KcPair) + 32u + (automatic ? kc_auto_bytes(qlen, tlen) : 0u);
+}
+
+struct KcChunk { size_t j0, j1, slots; };                    // pairs [j0, j1) and the bytes of their slices
+struct bsa_kmer_chain_plan {
+	bsa_ctx_t *ctx = nullptr;
+	size_t n = 0;
+	uint32_t ksz = 0, flags = 0;
+	KcPair *d_meta = nullptr;                                 // n entries, slot = the pair's offset inside its chunk's workspace
+	std::vector<KcChunk> chunks;
+	size_t scratch = 0;                                       // bytes of the context's scratch the largest chunk asks for
+};
+// a chunk's carve of the scratch: counts, result offsets, slices
+static inline size_t kc_plan_o_res(size_t c){ return kc_up(c * 4); }
+static inline size_t kc_plan_o_ws(size_t c){ return kc_plan_o_res(c) + kc_up(c * 8); }
+
+extern "C" uint64_t bsa_kmer_chain_words_bound(const uint32_t *qlen, const uint32_t *tlen, size_t n){
+	uint64_t w = 0;
+	if(qlen && tlen) for(size_t k = 0; k < n; k++) w += std::min(qlen[k], tlen[k]);
+	return w;
+}
+extern "C" void bsa_kmer_chain_plan_destroy(bsa_kmer_chain_plan_t *p){
+	if(!p) return;
+	if(p->d_meta) (void)hipFree(p->d_meta);
+	delete p;
+}
+extern "C" uint32_t bsa_kmer_chain_plan_chunks(const bsa_kmer_chain_plan_t *p){ return p ? (uint32_t)p->chunks.size() : 0u; }
+
+static int kc_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n, uint32_t ksz, uint32_t flags,
+		bsa_kmer_chain_plan_t **out){
+	const bool qs = (flags & BSA_MODE_QSTRAND) != 0, au = (flags & BSA_KMER_STRAND_AUTO) != 0;
+	hipStream_t stream;
+	int rc = bsa_ctx_get_stream_internal(ctx, &stream);        // (also selects the context's device)
+	if(rc != BSA_OK) return rc;
+	size_t budget = bsa_ctx_workspace_limit_internal(ctx);
+	if(budget == 0){
+		size_t fr = 0, tot = 0;
+		budget = (size_t)2 << 30;
+		if(hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::min(budget, fr / 2);
+	}
+	budget = budget > 4096 ? budget - 4096 : 0;
+	// no host route behind a run: every pair has to be one the kernels take
+	const uint64_t lim = bsa_kmer_dev_max_internal();
+	char msg[200];
+	for(size_t k = 0; k < n; k++){
+		const uint64_t sum = (uint64_t)qlen[k] + tlen[k];
+		if(sum > lim){
+			snprintf(msg, sizeof msg, "bsa_kmer_chain_plan_create: pair %zu has qlen + tlen = %llu, above %llu: chain it with bsa_kmer_chain_batch2", k, (unsigned long long)sum, (unsigned long long)lim);
+			bsa_ctx_set_error_internal(ctx, msg);
+			return BSA_E_UNSUPPORTED;
+		}
+		const size_t need = kc_plan_pair_bytes(qlen[k], tlen[k], au);
+		if(need > budget){
+			snprintf(msg, sizeof msg, "bsa_kmer_chain_plan_create: pair %zu alone needs %zu bytes of workspace, the limit leaves %zu: chain it with bsa_kmer_chain_batch2", k, need, budget);
+			bsa_ctx_set_error_internal(ctx, msg);
+			return BSA_E_UNSUPPORTED;
+		}
+	}
+	std::unique_ptr<bsa_kmer_chain_plan, void(*)(bsa_kmer_chain_plan*)> p(new bsa_kmer_chain_plan(), bsa_kmer_chain_plan_destroy);
+	p->ctx = ctx; p->n = n; p->ksz = ksz; p->flags = flags;
+	std::vector<KcPair> meta(n);
+	const uint64_t qmask = qs ? ~BSA_QOFF_REVCOMP : ~0ull;
+	for(size_t j0 = 0; j0 < n; ){
+		// the chunk [j0, j1): as many pairs as the budget holds
+		size_t j1 = j0, bytes = 0, slots = 0, acap = 0;
+		while(j1 < n){
+			const uint32_t ql = qlen[j1], tl = tlen[j1];
+			const size_t need = kc_plan_pair_bytes(ql, tl, au);
+			if(j1 > j0 && (bytes + need > budget || acap + std::min(ql, tl) > 0x7FFFFFF0ull || j1 - j0 >= 0x7FFFFFF0ull)) break;
+			KcPair &P = meta[j1];
+			P.qoff = qoff[j1] & qmask; P.toff = toff[j1]; P.slot = slots; P.qlen = ql; P.tlen = tl;
+			P.cmin = kc_min_cover(ql, tl, ksz); P.rc = (qs && (qoff[j1] & BSA_QOFF_REVCOMP)) ? 1u : 0u;
+			slots += 2u * kc_half_bytes(ql, tl) + (au ? kc_auto_bytes(ql, tl) : 0u); acap += std::min(ql, tl); bytes += need;
+			j1 ++;
+		}
+		p->chunks.push_back(KcChunk{ j0, j1, slots });
+		p->scratch = std::max(p->scratch, kc_plan_o_ws(j1 - j0) + kc_up(slots + 16));
+		j0 = j1;
+	}
+	if(n){
+		if(hipMalloc((void**)&p->d_meta, n * sizeof(KcPair)) != hipSuccess){ p->d_meta = nullptr; (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_plan_create: no device memory for the pair table"); return BSA_E_NOMEM; }
+		if(hipMemcpy(p->d_meta, meta.data(), n * sizeof(KcPair), hipMemcpyHostToDevice) != hipSuccess){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_plan_create: upload of the pair table failed"); return BSA_E_HIP; }
+	}
+	*out = p.release();
+	return BSA_OK;
+}
+
+extern "C" int bsa_kmer_chain_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
+		uint32_t ksz, uint32_t flags, bsa_kmer_chain_plan_t **out){
+	if(!ctx || !out) return BSA_E_ARG;
+	*out = nullptr;
+	if(n && (!qoff || !qlen || !toff || !tlen)) return BSA_E_ARG;
+	if(flags & ~(uint32_t)(BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND | BSA_KMER_STRAND_AUTO)){ bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_plan_create: unknown flag"); return BSA_E_ARG; }
+	if((flags & BSA_MODE_QSTRAND) && (flags & BSA_KMER_STRAND_AUTO)){ bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_plan_create: BSA_KMER_STRAND_AUTO finds the strands, BSA_MODE_QSTRAND gives them"); return BSA_E_ARG; }
+	if(n > 0xFFFFFFF0ull){ bsa_ctx_set_error_internal(ctx, "too many pairs"); return BSA_E_ARG; }
+	try {
+		return kc_plan_create(ctx, qoff, qlen, toff, tlen, n, ksz > 15 ? 15u : ksz, flags, out);
+	} catch(...){
+		return BSA_E_NOMEM;
+	}
+}
+
+extern "C" int bsa_kmer_chain_run(bsa_kmer_chain_plan_t *p, const uint8_t *d_seqs, uint64_t *d_maps, size_t maps_cap, uint64_t *d_maps_off, uint32_t *d_status){
+	if(!p || !d_maps_off || (p->n && !d_seqs) || (maps_cap && !d_maps)) return BSA_E_ARG;
+	bsa_ctx_t *ctx = p->ctx;
+	const bool pk = (p->flags & BSA_MODE_SEQ2BIT) != 0, qs = (p->flags & BSA_MODE_QSTRAND) != 0, au = (p->flags & BSA_KMER_STRAND_AUTO) != 0;
+	if(au && !d_status){ bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_run: BSA_KMER_STRAND_AUTO reports the strands in d_status"); return BSA_E_ARG; }
+	if(pk && ((uintptr_t)d_seqs & 7u)){ bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_run: a BSA_MODE_SEQ2BIT blob is 64-bit words, d_seqs has to be 8-byte aligned"); return BSA_E_ARG; }
+	auto kern = au ? (pk ? k_kmer_chain<true, false, true> : k_kmer_chain<false, false, true>)
+		: pk ? (qs ? k_kmer_chain<true, true, false> : k_kmer_chain<true, false, false>) : (qs ? k_kmer_chain<false, true, false> : k_kmer_chain<false, false, false>);
+	// k-mer size 0: no anchors anywhere, the status as ever -- the kernel sees a k-mer no sequence is long enough for and leaves after its status word
+	const uint32_t ksz = p->ksz ? p->ksz : 0xFFFFFFFFu;
+	hipStream_t stream;
+	int rc = bsa_ctx_get_stream_internal(ctx, &stream);
+	if(rc != BSA_OK) return rc;
+	hipEvent_t *ev = nullptr;
+	if((rc = bsa_ctx_kmer_chain_events_internal(ctx, p->chunks.size(), (long)p->n, &ev)) != BSA_OK) return rc;
+	if(p->chunks.empty()){                                    // n == 0: d_maps_off[0] = 0 is all there is to write
+		hipLaunchKernelGGL(k_kmer_scan_carry, dim3(1), dim3(KC_THREADS), 0, stream, (const uint32_t*)nullptr, d_maps_off, 0u, 1u);
+		if(hipGetLastError() != hipSuccess){ bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_run: launch failed"); return BSA_E_HIP; }
+		return BSA_OK;
+	}
+	void *bufv = nullptr;
+	if((rc = bsa_ctx_scratch_internal(ctx, 1, p->scratch, &bufv)) != BSA_OK) return rc;        // (waits for the stream only when it has to grow)
+	uint8_t *buf = (uint8_t*)bufv;
+	for(size_t ci = 0; ci < p->chunks.size(); ci++){
+		const KcChunk &ch = p->chunks[ci];
+		const uint32_t c = (uint32_t)(ch.j1 - ch.j0);
+		uint32_t *cnt = (uint32_t*)buf;
+		uint64_t *res = (uint64_t*)(buf + kc_plan_o_res(c));
+		uint8_t *ws = buf + kc_plan_o_ws(c);
+		if(hipEventRecord(ev[2 * ci], stream) != hipSuccess){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_run: hipEventRecord failed"); return BSA_E_HIP; }
+		hipLaunchKernelGGL(kern, dim3(c), dim3(KC_THREADS), 0, stream, d_seqs, (const KcPair*)(p->d_meta + ch.j0), ws, ksz, 0u, cnt, res, d_status ? d_status + ch.j0 : (uint32_t*)nullptr);
+		hipLaunchKernelGGL(k_kmer_scan_carry, dim3(1), dim3(KC_THREADS), 0, stream, (const uint32_t*)cnt, d_maps_off + ch.j0, c, ci == 0 ? 1u : 0u);
+		hipLaunchKernelGGL(k_kmer_gather_whole, dim3(c), dim3(KC_THREADS), 0, stream, (const uint8_t*)ws, (const uint64_t*)res, (const uint32_t*)cnt,
+			(const uint64_t*)(d_maps_off + ch.j0), d_maps, (uint64_t)maps_cap);
+		if(hipGetLastError() != hipSuccess || hipEventRecord(ev[2 * ci + 1], stream) != hipSuccess){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_kmer_chain_run: launch failed"); return BSA_E_HIP; }
+	}
 	return BSA_OK;
 }

@@ -246,7 +246,8 @@ int         bsa_ctx_last_margin_ms(bsa_ctx_t *ctx, double *ms, long *launches);
  * kernel flagged) */
 long        bsa_ctx_last_handover(bsa_ctx_t *ctx);
 /* the device k-mer chainer in the last bsa_kmer_chain_batch / bsa_kmer_edit_batch2(BSA_KMER_CHAIN_DEVICE) call: time of its kernels (HIP events on the
- * context stream, summed over the workspace chunks), pairs it chained and pairs the host chained in the same call (any pointer may be NULL) */
+ * context stream, summed over the workspace chunks), pairs it chained and pairs the host chained in the same call (any pointer may be NULL).
+ * After bsa_kmer_chain_run (asynchronous): the same sum for that run, read once its last chunk has finished (the call waits for it), n and 0 */
 int         bsa_ctx_last_kmer_chain_ms(bsa_ctx_t *ctx, double *ms, long *pairs_on_device, long *pairs_on_host);
 void        bsa_set_score_matrix(int8_t matrix[16], int8_t mat, int8_t mis);   /* bsalign.h:323 */
 
@@ -372,7 +373,7 @@ int      bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, const bsa_
  *                    exceeds bsa_ctx_set_workspace_limit, is chained by the host code inside the same call -- same words, the caller sees no
  *                    difference but bsa_ctx_last_kmer_chain_ms.  Pairs go in chunks when the workspace does not hold them all.
  *                    Takes 1 B/base blobs and no strand marks: it IS bsa_kmer_chain_batch2 with flags 0, which takes BSA_MODE_SEQ2BIT blobs and
-                    BSA_MODE_QSTRAND marks.  Neither takes device pointers.
+                    BSA_MODE_QSTRAND marks.  Neither takes device pointers: the form for a resident blob is bsa_kmer_chain_plan_create / bsa_kmer_chain_run below.
  * bsa_kmer_chain_batch2: the same call with `flags`, a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND | BSA_KMER_STRAND_AUTO (any other bit: BSA_E_ARG); the
  *                    first two mean exactly what they mean for bsa_align_batch, the third is described at its definition below.  SEQ2BIT: seqs are BaseBank.bits words, qoff / toff BASE offsets (any offset), seqs_bytes a multiple of
  *                    8 and off + len <= 4 * seqs_bytes, else BSA_E_ARG; BSA_ST_BAD_BASE cannot occur.  QSTRAND: bit 63 of qoff[k]
@@ -392,8 +393,9 @@ int      bsa_kmer_assemble(const bsa_kmer_seg_t *segs, uint32_t nseg, const bsa_
  *                    read in front of the word that holds a read's first base nor behind the one that holds its last.  A packed read goes up as
  *                    the words that hold it, a quarter of the bytes.  Pairs the device route does not take are chained by the host code on a
  *                    per-pair decoded copy: the same words.  bsa_ctx_last_kmer_chain_ms keeps its meaning.
- *                    Out of scope for the k-mer calls: BSA_MODE_CIGAR_EQX and BSA_MODE_SCORE_ONLY, device-pointer or plan forms, the bsalign-hip CLI
- *                    and the compat layer (both keep 1 B/base forward-strand queries). */
+ *                    Out of scope for the k-mer calls: BSA_MODE_CIGAR_EQX and BSA_MODE_SCORE_ONLY, a device-pointer or plan form of bsa_kmer_edit_batch2 (the
+ *                    chain call has one: bsa_kmer_chain_plan_create / bsa_kmer_chain_run), the bsalign-hip CLI and the compat layer (both keep 1 B/base
+ *                    forward-strand queries). */
 int bsa_kmer_chain_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                          const uint64_t *qoff, const uint32_t *qlen,
                          const uint64_t *toff, const uint32_t *tlen, size_t n,
@@ -438,7 +440,8 @@ int bsa_kmer_chain_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes
                                        bsa_kmer_edit_batch2, with or without BSA_KMER_CHAIN_DEVICE: step 1 chooses the strands, the rest is the
                                        BSA_MODE_QSTRAND route on a private marked copy of qoff -- records (qb / qe in q' coordinates), CIGAR words and
                                        cigar_off bit-identical to that call, status with BSA_ST_REVCOMP OR-ed in for the reverse pairs.
-                                       Not taken by bsa_align_* / bsa_edit_*, plans, device pointers, the CLI or the compat layer.  To align the
+                                       Taken by bsa_kmer_chain_plan_create (device pointers, below); not by bsa_align_* / bsa_edit_* or their plans, the
+                                       CLI or the compat layer.  To align the
                                        pairs on the strand found here, copy the bit into qoff and use BSA_MODE_QSTRAND there:
                                            bsa_kmer_chain_batch2(ctx, ..., qoff, ..., maps, cap, maps_off, status, BSA_KMER_STRAND_AUTO);
                                            for(k = 0; k < n; k++) if(status[k] & BSA_ST_REVCOMP) qoff[k] |= BSA_QOFF_REVCOMP;
@@ -449,6 +452,55 @@ int bsa_kmer_edit_batch2(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
                          const bsa_kmer_params_t *par,
                          bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
                          uint64_t *cigar_off, uint32_t *status, uint32_t flags);
+
+/* bsa_kmer_chain_plan_* : bsa_kmer_chain_batch2 in the two-phase form for resident data, as bsa_align_plan_* is to bsa_align_batch: the plan takes the HOST
+ *                    metadata once, bsa_kmer_chain_run takes DEVICE pointers for the sequence blob and all outputs.
+ * flags, ksz       : flags is a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND | BSA_KMER_STRAND_AUTO, each meaning exactly what it means for
+ *                    bsa_kmer_chain_batch2; any other bit is BSA_E_ARG, and so is QSTRAND together with STRAND_AUTO.  ksz above 15 means 15, ksz == 0 gives no
+ *                    anchors anywhere (the status words are written all the same).  n == 0 is fine: the run writes d_maps_off[0] = 0.  With STRAND_AUTO
+ *                    d_status == NULL is BSA_E_ARG from the run; with SEQ2BIT a d_seqs that is not 8-byte aligned is BSA_E_ARG from the run.
+ * the blob         : the kernels read the caller's blob IN PLACE.  qoff / toff are the caller's own offsets into d_seqs, bytes, or base offsets with SEQ2BIT;
+ *                    with QSTRAND bit 63 of qoff[k] is the strand bit.  Like bsa_align_plan_create the plan takes no blob size and cannot check bounds:
+ *                    that every read lies inside the blob is a PRECONDITION.  With SEQ2BIT nothing is read in front of the word that holds a read's first
+ *                    base nor behind the one that holds its last.
+ * results          : d_maps[d_maps_off[k] .. d_maps_off[k + 1]), all of d_maps_off and d_status (BSA_ST_REVCOMP under STRAND_AUTO included) are bit-identical
+ *                    to what bsa_kmer_chain_batch2 returns for the same pairs and flags on a host copy of the blob -- hence to per-pair bsa_kmer_chain on
+ *                    q or q'.  A pair with a base code above 3 gets BSA_ST_BAD_BASE and no anchors, an empty pair BSA_ST_EMPTY and none.
+ * no host route    : a run cannot read device memory on the host and stay asynchronous, so bsa_kmer_chain_plan_create returns BSA_E_UNSUPPORTED when a pair has
+ *                    qlen + tlen > 262144, or when a pair's slice alone (about 16 bytes a base) exceeds the workspace limit in force at creation
+ *                    (bsa_ctx_set_workspace_limit); bsa_last_error names the first such pair.  Send those pairs through bsa_kmer_chain_batch2.
+ * asynchronous     : bsa_kmer_chain_run is asynchronous on the context stream and returns BSA_OK before a kernel has run.  It copies nothing between host
+ *                    and device and does not synchronise: the pair tables went up when the plan was made, into memory the plan owns, and so were the
+ *                    workspace chunks decided (bsa_kmer_chain_plan_chunks; one chunk unless the workspace limit forces more).  The workspace is the
+ *                    context's scratch: a run that has to grow it may synchronise once.
+ * arena            : the run cannot report an arena that is too small; the caller compares d_maps_off[n] with maps_cap afterwards
+ *                    (bsa_kmer_chain_words_bound gives a maps_cap that always suffices).  For ANY maps_cap, 0 with a non-NULL d_maps and a NULL d_maps with
+ *                    maps_cap 0 (a count-only run) included:
+ *                      - all n + 1 entries of d_maps_off and all n of d_status are those of a run with a large arena, and every run writes every one of
+ *                        them, whatever the buffers held;
+ *                      - d_maps_off[n] is the number of words needed;
+ *                      - pair k's words are written if and only if d_maps_off[k + 1] <= maps_cap, otherwise no word of its range is touched (the gather
+ *                        writes straight into the caller's arena, in pair order: unlike bsa_align_run's, WHICH pairs are present is specified);
+ *                      - no word at or above maps_cap, nor at or above d_maps_off[n], is touched.
+ * re-run           : a run leaves nothing behind that a later run reads.  A plan may be run again on other sequences of the same lengths, after a short run,
+ *                    and in turn with other chain, align and edit plans of the same context.  Destroy a plan before its context.
+ * timing           : bsa_ctx_last_kmer_chain_ms after bsa_ctx_sync: the summed event time of the last run's chunks, pairs_on_device = n, pairs_on_host = 0.
+ * Example          : a shard from bsa_shard_scatter, or bsa_synth_pairs_dev's blob, stays where it is --
+ *                      bsa_kmer_chain_plan_create(ctx, qoff, qlen, toff, tlen, n, 13, BSA_KMER_STRAND_AUTO, &plan);
+ *                      cap = bsa_kmer_chain_words_bound(qlen, tlen, n);             (hipMalloc d_maps: cap words, d_maps_off: n + 1, d_status: n)
+ *                      bsa_kmer_chain_run(plan, d_seqs, d_maps, cap, d_maps_off, d_status); bsa_ctx_sync(ctx);
+ *                    then 4 bytes a pair come down (d_status), BSA_ST_REVCOMP goes into qoff[k] as BSA_QOFF_REVCOMP, and bsa_align_plan_create with
+ *                    BSA_MODE_QSTRAND aligns the same resident blob on the strands found.
+ * Out of scope     : a resident form of bsa_kmer_edit_batch2 (its edit plans need the segments' lengths on the host), a host fallback inside the run. */
+typedef struct bsa_kmer_chain_plan bsa_kmer_chain_plan_t;
+int      bsa_kmer_chain_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t *qlen,
+                                    const uint64_t *toff, const uint32_t *tlen, size_t n,
+                                    uint32_t ksz, uint32_t flags, bsa_kmer_chain_plan_t **out);
+void     bsa_kmer_chain_plan_destroy(bsa_kmer_chain_plan_t *plan);
+uint32_t bsa_kmer_chain_plan_chunks(const bsa_kmer_chain_plan_t *plan);      /* workspace chunks one run goes through */
+uint64_t bsa_kmer_chain_words_bound(const uint32_t *qlen, const uint32_t *tlen, size_t n);  /* sum of min(qlen, tlen): a maps_cap that always suffices; host only, no GPU */
+int      bsa_kmer_chain_run(bsa_kmer_chain_plan_t *plan, const uint8_t *d_seqs,
+                            uint64_t *d_maps, size_t maps_cap, uint64_t *d_maps_off /* n + 1 */, uint32_t *d_status /* n, may be NULL */);
 
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
