@@ -28,6 +28,7 @@
 #include "bsa_common.h"
 #include "bsa_dpp.h"
 #include <algorithm>
+#include <cstdio>
 #ifndef XQ_BEGS16
 #define XQ_BEGS16 0              // 1: band offsets leave sixteen rows (one 64-byte line) at a time instead of four (16 bytes at an odd dword).  Measured at C2 with
                                  // slots at multiples of 256 bytes: WRITE_SIZE 80.0 -> 69.7 GB (= the 69.6 GB the kernel has to store), forward 59.6 -> 60.2 ms (two-piece
@@ -923,6 +924,508 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	}
 }
 
+// ABSOLUTE-SCORE form of the row body (one-piece gaps, sixteen cells a half, four lanes per pair, moving band, two-bit D / Od fields: the
+// headline shape).  Same code rows, band offsets, scores and end records as x_forward, bit for bit.
+// The row is kept as scores, not as differences: H^(x, y) = H(x, y) - gape (x + y) - base, x the query column, y the target row, base an int32
+// of the pair.  In this frame extending a gap costs nothing in either direction, a cell's value does not depend on where the band stands, and the
+// recurrence needs no re-basing from cell to cell:
+//     pass 1:  d = Hp + S~     m = max(E, d)     mg = m + gapo     f = max(f, mg)
+//     pass 2:  h = max(m, f)   fm = max(f, mg)   f = fm            En = max(E, h + gapo)
+// with Hp[k] = H^ of the new cell k's diagonal predecessor and E[k] = its E^ (the upper neighbour's H^ + e - gape); both are plain int16 in the
+// two halves.  Every comparison is x_forward's with the diagonal predecessor's score added on both sides, so the four facts of a cell are the same
+// bits: M: h == d, D / Od field: h - En = min(h - E, -gapo), R: fm == mg.
+// The row is held slid by one cell as in x_forward: cell k writes h into Hp[k] (its own slot: the new cell k's diagonal predecessor is the old
+// cell k) and En into E[k - 1]; cell 0's En travels to the previous block's E[W - 1].  Nothing of Hp crosses a lane on a row that moves by one.
+//   * the cell entering at the band end has H^ = (last cell) + cfirst - gape, E^ = that - gape (e = 0); the cells behind it (moves of two and
+//     more) repeat both values (u = gape1);
+//   * the virtual column left of the band's first cell (ubegs[0], re-based on cell 0 with u = 0 by the reference's tail) is (cell 0) + gape;
+//   * the -63 sentinels (f entering every block in pass 1 and block 0 in pass 2, e of row -1, the first-cell rule) keep their exact values,
+//     added to the score they were relative to; a band that jumps past all it held starts again from a row of SCORE_MIN;
+//   * real scores are read where they are needed: H at band position p of row i = base + H^ + gape (rbeg + p + i).
+// F values are absolute, so the F-penetration is the bare prefix maximum over the pair's lanes.
+// S~ comes sign-extended out of ONE byte permute: the row's table entry is two dwords {PADS, S~(q0), 0, S~(q1)}, {0, S~(q2), 0, S~(q3)} and the
+// window's selector of a column is {byte of its code, sign of that byte} per half (selectors 8 .. 11 replicate the top bit of bytes 1, 3, 5, 7);
+// code 4 (beyond the query end) selects the PADS byte and the constant 0xFF: a fifth entry at no cost, queries shorter than the band included.
+// REBASE: every (rmask + 1) rows the H^ of lane 0's first slot is subtracted from Hp and E and added to base (bsa_align8_abs_rows has the bound).
+// Flags are bit 0 of a half, M and R accumulated as they are stored (not inverted); accumulators and two-bit fields fill the low byte.
+// PW: 1 one-piece gaps, 0 linear gaps (gapo = 0: E^ of a cell is its upper neighbour's H^, R and Od are always set).  DO2: the two-bit D / Od fields (four lanes, one piece);
+// otherwise the four planes, with D (h == E) and Od (field == -gapo) accumulated as they are stored too.  L = 8: bandwidth 256, a half is one reference block of sixteen cells.
+// EXT: the staging area and the window come from the caller (k_align8_fwd_x_mix).
+template<int L, int NWV, int PW = 1, bool DO2 = true, bool EXT = false>
+static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const uint32_t first_pos, const uint32_t count, const uint32_t tid_base, const uint32_t rmask,
+		const uint32_t row0 = 0u, const uint32_t row1 = 0xFFFFFFF8u, uint32_t *st = nullptr, uint32_t *ext_stage = nullptr, uint32_t *ext_qwin = nullptr){
+	constexpr int W = 16, BW = 2 * L * W, WR = BW / 16, CR = 8 / L;
+	static_assert((L == 4 || L == 8) && (PW == 0 || PW == 1) && (!DO2 || (PW == 1 && L == 4)), "bandwidth 128 (four lanes per pair) or 256 (eight), one-piece or linear gaps");
+	constexpr int NACC = 2, NDO = DO2 ? 4 : 1, ND = 4, CWD = WR / 8;
+	const int lt = threadIdx.x;
+	const int jl = lt & (L - 1);
+	const bool first = jl == 0, last = jl == L - 1;
+	const uint32_t g = (tid_base + (uint32_t)lt) / (uint32_t)L;
+	const bool live = g < count;
+	const uint32_t ppos = first_pos + (live ? g : 0u);
+	const uint32_t pair = a.order[ppos];
+	const uint32_t qlen = a.qlen[pair];
+	uint32_t tlen = a.tlen[pair];
+	const uint8_t *qp = a.qst + a.qpoff[pair], *tp = a.tst + a.tpoff[pair];
+	int *begs = (int*)(a.rows + a.slot_off[ppos]);
+	uint8_t *rowp = (uint8_t*)begs + bsa_begs_bytes(tlen);
+	if(!live || a.status[pair] != 0u) tlen = 0;
+
+	const int mode = a.mode & 3;
+	const int gapo1 = a.gapo1, gape1 = a.gape1;
+	const int GE = gape1, GO = gapo1;
+	const uint32_t GO16 = x_i16(GO), GE16 = x_i16(GE);
+	const uint32_t ONE1 = 0x00010001u;
+	uint32_t TWO = 0x00020002u;
+	asm volatile("" : "+s"(TWO));
+	uint32_t KDO0 = 0x00400040u, KDO1 = 0x00100010u, KDO2 = 0x00040004u;
+	asm volatile("" : "+s"(KDO0), "+s"(KDO1), "+s"(KDO2));
+	const uint32_t DOSP = (GO == -1) ? 2u : 1u;
+	const uint32_t MINF16 = x_i16(BSA_EPI8_MIN - 2 * GE);
+	const int gopen = gapo1 + gape1;
+	const int cfirst = min(a.smin, gopen) - 1 - a.smax + gopen;
+	const uint32_t ENT16 = x_i16(cfirst - GE);             // the entering cell's H^ above the last cell's
+	const int NEWNE = (PW == 0) ? 0 : GE;                  // gape - e of an entering cell (e = 0; linear gaps: e is the constant gape)
+	const int NE0 = (PW == 0) ? 0 : GE - BSA_EPI8_MIN;     // ... of row -1 (e = -63)
+	const uint32_t NGO1 = x_i16(-GO - 1);
+	__shared__ __attribute__((aligned(8))) uint32_t xa_mtab[8];
+	if((lt & 63) < 4){
+		const int t = lt & 3;
+		auto sb = [&](int q) -> uint32_t { return (uint32_t)(((int)a.matrix[q * 4 + t] - 2 * GE) & 0xff); };
+		xa_mtab[2 * t] = (uint32_t)((BSA_EPI8_MIN - 2 * GE) & 0xff) | (sb(0) << 8) | (sb(1) << 24);
+		xa_mtab[2 * t + 1] = (sb(2) << 8) | (sb(3) << 24);
+	}
+	__builtin_amdgcn_wave_barrier();
+
+	uint32_t Hp[W], E[W];
+	int base = 0;
+	uint32_t svH = 0, svE = 0;        // lane 0, low half: H^ of the virtual column left of the row's first cell and E^ of that cell, for a row that does not move
+	uint32_t rbeg = 0, mov = 0, i = row0;
+	int cand_sc = BSA_SCORE_MIN, cand_te = 0;
+	// this lane's band positions times -gape, per half
+	const uint32_t NGP = ((uint32_t)(-GE * jl * W) & 0xffffu) | ((uint32_t)(-GE * (jl + L) * W) << 16);
+	if(row0 == 0u){
+		// row -1 (bsalign.h:2094-2140), slid by one cell: Hp[k] = H^ at band position p, E[k] = E^ at p + 1 (e = -63)
+		const int first_u = (int)(int8_t)(gapo1 + gape1 + a.smin - a.smax);
+		const bool ov = mode == BSA_MODE_OVERLAP;
+		base = ov ? 0 : gapo1 + 2 * gape1;
+#pragma unroll
+		for(int k = 0; k < W; k++){
+			// global / extend: H(p, -1) = gapo + (p + 1) gape: H^ = 0; overlap: H = 0: H^ = -gape (p - 1)
+			Hp[k] = ov ? x_add(NGP, x_i16(GE - GE * k)) : 0u;
+			E[k] = ov ? x_add(NGP, x_i16(-GE * k - NE0)) : x_i16(-NE0);
+		}
+		// the entering cell behind the row's last one
+		if(last){
+			const uint32_t hl = (Hp[W - 1] >> 16) + (uint32_t)(cfirst - GE - NEWNE);
+			E[W - 1] = (E[W - 1] & 0xffffu) | (hl << 16);
+		}
+		svH = ov ? x_i16(2 * GE) : x_i16(GE - first_u);
+		svE = ov ? x_i16(GE - NE0) : x_i16(-NE0);
+	}
+	if(row0 != 0u){
+		const uint32_t *sp = st + (lt & 63);
+		int r = 0;
+#pragma unroll
+		for(int k = 0; k < W; k++) Hp[k] = sp[64 * r++];
+#pragma unroll
+		for(int k = 0; k < W; k++) E[k] = sp[64 * r++];
+		base = (int)sp[64 * r++]; svH = sp[64 * r++]; svE = sp[64 * r++];
+		rbeg = sp[64 * r++]; mov = sp[64 * r++]; cand_sc = (int)sp[64 * r++]; cand_te = (int)sp[64 * r++];
+	}
+	__shared__ uint32_t xa_stage[EXT ? 1 : NWV][EXT ? 1 : 4 * ND][64];
+	uint32_t *const stg = EXT ? ext_stage + (size_t)(lt >> 6) * (4 * ND * 64) + (lt & 63) : &xa_stage[(!EXT && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
+	constexpr int KD = 4 + 12, NSEL = 2 * KD;
+	constexpr uint32_t QOFFMAX = (uint32_t)(NSEL - W);
+	static_assert(NSEL % 4 == 0 && NSEL - W <= BSA_QPAD_TAIL, "a refill reads NSEL - W bytes behind the band's last block");
+	__shared__ uint32_t xa_qwin[EXT ? 1 : NWV][EXT ? 1 : 2 * KD][64];
+	uint32_t *const qwp = EXT ? ext_qwin + (size_t)(lt >> 6) * (2 * KD * 64) + (lt & 63) : &xa_qwin[(!EXT && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
+	uint32_t wbase = 0x40000000u;
+	int begq = 0;
+	if(tlen != 0u && first && row0 == 0u) begs[0] = 0;
+	uint64_t twin = 0;          // eight target bases times eight: the byte offsets of their table entries
+	if(row0 < tlen){ __builtin_memcpy(&twin, tp + row0, 8); twin <<= 3; }
+	const int rbz = 2 * max((int)(tlen / max(qlen, 1u)), 1);
+	const bool rush32 = (unsigned long long)(uint32_t)rbz * tlen + qlen + (uint32_t)BW + (uint32_t)rbz < 0xFFFFFFFFull;
+	uint32_t rzl = rush32 ? (uint32_t)rbz * (tlen - min(row0, tlen) - 1u) : 0u;
+	int rby_tab = 0;
+	const int rby_lane = (lt & (64 - L)) << 2;
+
+	uint64_t actm = 0;
+	while(i < row1 && (actm = __builtin_amdgcn_ballot_w64(i < tlen)) != 0ull){
+		const bool act = i < tlen;
+		if(mode == BSA_MODE_GLOBAL && (i & (uint32_t)(L - 1)) == 0u)
+			rby_tab = (int)((1.0 * (double)(i + (uint32_t)jl) / (double)tlen) * (double)qlen);
+		// ---- rebase (i is uniform)
+		if((i & rmask) == 0u){
+			const uint32_t bc = x_bcast_first<L>(Hp[0]);
+			const uint32_t dl = __builtin_amdgcn_perm(bc, bc, 0x01000100u);
+#pragma unroll
+			for(int k = 0; k < W; k++){ Hp[k] = x_sub(Hp[k], dl); E[k] = x_sub(E[k], dl); }
+			svH = x_sub(svH, dl); svE = x_sub(svE, dl);
+			base += x_lo16(bc);
+		}
+		mov = min(mov, __builtin_elementwise_sub_sat(qlen, rbeg + (uint32_t)BW));
+		rbeg += mov;
+		int rhj = 0;
+		// ---- row_movx: correct what did not move by one
+		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov != 1u) & actm) != 0ull, 0)){
+			if(__any(act && mov >= (uint32_t)BW)){
+				const bool z = act && mov >= (uint32_t)BW;
+				const uint32_t bc = x_bcast_last<L>(Hp[W - 1]);
+				// H at the last cell of the previous row (band offset rbeg - mov, row i - 1)
+				const int rhz = base + x_hi16(bc) + GE * ((int)(rbeg - mov) + BW - 1 + (int)i - 1);
+				if(z){
+					rhj = rhz;
+					// a row of SCORE_MIN with e = 0: base such that the diagonal predecessor of band position 0 has H^ = 0
+					base = BSA_SCORE_MIN - GE * ((int)rbeg + (int)i - 2);
+#pragma unroll
+					for(int k = 0; k < W; k++){ Hp[k] = x_add(NGP, x_i16(-GE * k)); E[k] = x_add(NGP, x_i16(-GE * (k + 1) - NEWNE)); }
+				}
+			}
+			if(__any(act && mov == 0u)){
+				const bool d = act && mov == 0u;
+				const uint64_t dm = __ballot(d);
+				const uint32_t pu = x_shift_down<L>(Hp[W - 1], svH, first), pe = x_shift_down<L>(E[W - 1], svE, first);
+#pragma unroll
+				for(int k = W - 1; k >= 1; k--){ x_sel(Hp[k], Hp[k - 1], dm); x_sel(E[k], E[k - 1], dm); }
+				x_sel(Hp[0], pu, dm); x_sel(E[0], pe, dm);
+			}
+			for(uint32_t s = 1; __any(act && mov < (uint32_t)BW && s < mov); s++){
+				const bool d = act && mov < (uint32_t)BW && s < mov;
+				const uint64_t dm = __ballot(d);
+				// the cells behind the band end: the first has H^ = last + cfirst - gape, the others repeat it; E^ of all of them is what the slide put in
+				uint32_t hfill = __builtin_amdgcn_perm(Hp[W - 1], Hp[W - 1], 0x03020302u);
+				if(s == 1u) hfill = x_add(hfill, ENT16);
+				const uint32_t efill = __builtin_amdgcn_perm(E[W - 1], E[W - 1], 0x03020302u);
+				const uint32_t inh = x_shift_up<L>(Hp[0], hfill, last), ine = x_shift_up<L>(E[0], efill, last);
+#pragma unroll
+				for(int k = 0; k + 1 < W; k++){ x_sel(Hp[k], Hp[k + 1], dm); x_sel(E[k], E[k + 1], dm); }
+				x_sel(Hp[W - 1], inh, dm); x_sel(E[W - 1], ine, dm);
+			}
+		}
+		// ---- S~(x, y), sign-extended
+		uint32_t S[W];
+		{
+			const uint32_t tw32 = (i & 4u) ? (uint32_t)(twin >> 32) : (uint32_t)twin;
+			const uint32_t tb8 = __builtin_amdgcn_ubfe(tw32, 8u * (i & 3u), 5u);
+			uint32_t off = rbeg - wbase;
+			if(__builtin_expect((__builtin_amdgcn_ballot_w64(off > QOFFMAX) & actm) != 0ull, 0)){
+				// refill for every live pair of the wave (x_forward, "refill"); a column's selector is {value byte, sign selector} of its two codes:
+				// code c < 4: bytes 2c + 1 and 8 + c, code 4: byte 0 (PADS) and 0x0D (0xFF)
+				if(act){
+					const uint8_t *pl = qp + rbeg + jl * W, *ph = qp + rbeg + (jl + L) * W;
+					uint32_t bl[NSEL / 4], bh[NSEL / 4];
+					__builtin_memcpy(bl, pl, NSEL); __builtin_memcpy(bh, ph, NSEL);
+					uint32_t TV = 0x07050301u, TS = 0x0B0A0908u;
+					asm volatile("" : "+v"(TV), "+v"(TS));
+#pragma unroll
+					for(int n = 0; n < NSEL / 4; n++){
+						const uint32_t lv = __builtin_amdgcn_perm(0x00000000u, TV, bl[n]), ls = __builtin_amdgcn_perm(0x0000000Du, TS, bl[n]);
+						const uint32_t hv = __builtin_amdgcn_perm(0x00000000u, TV, bh[n]), hs = __builtin_amdgcn_perm(0x0000000Du, TS, bh[n]);
+						const uint32_t l01 = __builtin_amdgcn_perm(ls, lv, 0x05010400u), l23 = __builtin_amdgcn_perm(ls, lv, 0x07030602u);
+						const uint32_t h01 = __builtin_amdgcn_perm(hs, hv, 0x05010400u), h23 = __builtin_amdgcn_perm(hs, hv, 0x07030602u);
+						qwp[64 * (4 * n)] = __builtin_amdgcn_perm(h01, l01, 0x05040100u);
+						qwp[64 * (4 * n + 1)] = __builtin_amdgcn_perm(h01, l01, 0x07060302u);
+						qwp[64 * (4 * n + 2)] = __builtin_amdgcn_perm(h23, l23, 0x05040100u);
+						qwp[64 * (4 * n + 3)] = __builtin_amdgcn_perm(h23, l23, 0x07060302u);
+					}
+					wbase = rbeg; off = 0u;
+				}
+			}
+			const uint32_t *wl = qwp + 64u * (act ? off : 0u);
+			const uint2 mr = *(const uint2*)((const uint8_t*)xa_mtab + tb8);
+#pragma unroll
+			for(int k = 0; k < W; k++) S[k] = __builtin_amdgcn_perm(mr.y, mr.x, wl[64 * k]);
+		}
+		// ---- first cell of the band (bsalign.h:2899-2907), x_forward's rule with the scores made real: ubegs[0] = base + Hp[0] + gape (rbeg + i - 2)
+		const uint32_t d0s = x_add(Hp[0], S[0]);
+		uint32_t d0h = d0s;
+		uint32_t q0m = 0x10000u, q0d = 0x10000u;          // (never equal to a half)
+		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u) & actm) != 0ull, 0)){
+			int rh;
+			if(mov >= (uint32_t)BW) rh = rhj;
+			else if(rbeg) rh = BSA_SCORE_MIN;
+			else if(mode == BSA_MODE_OVERLAP || i == 0) rh = 0;
+			else rh = gapo1 + gape1 * (int)i;
+			const int hp0 = x_lo16(Hp[0]);
+			const int HBr = base + hp0 + GE * ((int)rbeg + (int)i - 2);
+			const int s0 = x_lo16(S[0]) + 2 * GE;
+			const int t0 = x_lo16(E[0]) - hp0 + 2 * GE;          // u + e
+			int hh = (rh - HBr) + s0;
+			hh = (hh >= t0) ? min(hh, BSA_EPI8_MAX) : BSA_EPI8_MIN;
+			if(first && (mov == 0u || mov >= (uint32_t)BW)) d0h = (d0s & 0xffff0000u) | ((uint32_t)(hp0 + hh - 2 * GE) & 0xffffu);
+			const int cm = rh - HBr + s0 - 2 * GE, cd = t0 + rh - HBr - 2 * GE;
+			q0m = (cm >= -128 && cm <= 127) ? ((uint32_t)(hp0 + cm) & 0xffffu) : 0x10000u;
+			q0d = (cd >= -128 && cd <= 127) ? ((uint32_t)(hp0 + cd) & 0xffffu) : 0x10000u;
+		}
+		// ---- pass 1: F leaving every block when nothing but the sentinel enters it
+		uint32_t d[W], m[W], mg[W];
+		const uint32_t fini = x_add(Hp[0], MINF16);
+		uint32_t f = fini;
+#pragma unroll
+		for(int k = 0; k < W; k++){
+			d[k] = (k == 0) ? d0s : x_add(Hp[k], S[k]);
+			m[k] = x_max(E[k], (k == 0) ? d0h : d[k]);
+			mg[k] = (PW == 0) ? m[k] : x_add(m[k], GO16);
+			f = x_max(f, mg[k]);
+		}
+		// ---- F-penetration: prefix maximum over the blocks
+		{
+			const uint32_t P = x_scan_max<L>(f);
+			const uint32_t bc = x_bcast_last<L>(P);
+			const uint32_t Gm = x_max(P, (bc << 16) | 0x8000u);
+			f = x_shift_down<L>(Gm, fini, first);
+		}
+		// ---- pass 2, flags
+		uint32_t accM[NACC], accR[NACC], accD[NACC], accO[NACC], accDO[NDO];
+#pragma unroll
+		for(int n = 0; n < NDO; n++) accDO[n] = 0;
+#pragma unroll
+		for(int n = 0; n < NACC; n++){ accM[n] = 0; accR[n] = 0; accD[n] = 0; accO[n] = 0; }
+		uint32_t tmpE0 = 0, hfirst = 0;
+#pragma unroll
+		for(int k = 0; k < W; k++){
+			const uint32_t h = x_max(m[k], f);
+			const uint32_t fm = x_max(f, mg[k]);
+			f = fm;
+			if constexpr (PW != 0) accR[k >> 3] = x_acc(accR[k >> 3], x_satsubu(ONE1, x_sub(fm, mg[k])), TWO);
+			const uint32_t en = (PW == 0) ? h : x_max(E[k], x_add(h, GO16));          // (gapo = 0: h >= E)
+			if constexpr (DO2){
+				const uint32_t fld = x_sub(h, en);
+				const uint32_t kk = ((k & 3) == 0) ? KDO0 : ((k & 3) == 1) ? KDO1 : KDO2;
+				if((k & 3) == 3) accDO[k >> 2] = x_add(accDO[k >> 2], fld);
+				else accDO[k >> 2] = x_acc(fld, accDO[k >> 2], kk);
+			} else {
+				accD[k >> 3] = x_acc(accD[k >> 3], x_satsubu(ONE1, x_sub(h, E[k])), TWO);
+				if constexpr (PW != 0) accO[k >> 3] = x_acc(accO[k >> 3], x_satsubu(x_sub(h, en), NGO1), TWO);          // field == -gapo
+			}
+			accM[k >> 3] = x_acc(accM[k >> 3], x_satsubu(ONE1, x_sub(h, d[k])), TWO);
+			Hp[k] = h;
+			if(k == 0){ tmpE0 = en; hfirst = h; }
+			else E[k - 1] = en;
+		}
+		// ---- flags of special cells (x_forward's, on accumulators that are not inverted and sit in the low byte)
+		if(__builtin_expect((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull, 0)){
+			if(first && rbeg == 0u){
+				const uint32_t hl = hfirst & 0xffffu;
+				accM[0] = (accM[0] & ~0x80u) | ((hl == q0m) ? 0x80u : 0u);
+				if constexpr (DO2){
+					const uint32_t fld = (accDO[0] >> 6) & 3u;
+					accDO[0] = (accDO[0] & ~0xC0u) | ((hl == q0d) ? 0x40u : 0u) | ((fld == (uint32_t)(-GO)) ? 0x80u : 0u);
+				} else accD[0] = (accD[0] & ~0x80u) | ((hl == q0d) ? 0x80u : 0u);
+			}
+		}
+		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov > 1u) & actm) != 0ull, 0)){
+#pragma unroll
+			for(int hf = 0; hf < 2; hf++){
+				const int lim = BW - (int)mov - (jl + L * hf) * W;
+				const int nd = min(max(lim, 0), W), nm = min(max(lim + 1, 0), W);
+#pragma unroll
+				for(int n = 0; n < NACC; n++){
+					const int cd = min(max(nd - 8 * n, 0), 8), cm = min(max(nm - 8 * n, 0), 8);
+					const uint32_t md = ((1u << (8 - cd)) - 1u) << (16 * hf), mm = ((1u << (8 - cm)) - 1u) << (16 * hf);
+					if(mov != 0u){ if constexpr (!DO2) accD[n] &= ~md; accM[n] &= ~mm; }
+				}
+				if constexpr (DO2){
+#pragma unroll
+				for(int n = 0; n < NDO; n++){
+					const int c0 = min(max(nd - 4 * n, 0), 4);
+					const uint32_t cm = (0x55u & ((1u << (8 - 2 * c0)) - 1u)) << (16 * hf);
+					const uint32_t z = ~(accDO[n] | (accDO[n] >> 1)) & cm;
+					if(mov != 0u) accDO[n] |= z * DOSP;
+				}
+				}
+			}
+		} else if constexpr (DO2){
+			const uint32_t t = accDO[NDO - 1];
+			if(mov == 1u && last && (t & 0x00030000u) == 0u) accDO[NDO - 1] = t | (DOSP << 16);
+		} else accD[NACC - 1] &= ~((mov == 1u && last) ? 0x00010000u : 0u);          // band cell bw - 1 after a slide by one: no deletion there
+		if constexpr (PW == 0){
+#pragma unroll
+			for(int n = 0; n < NACC; n++){ accR[n] = 0x00FF00FFu; accO[n] = 0x00FF00FFu; }          // linear gaps: every gap is opened at length 1
+		}
+		// ---- the code row (bsa_common.h "COMPACT slot"), the layouts of x_forward
+		{
+			uint32_t cur[ND];
+			if constexpr (DO2){
+				// M | R << 8 | two-bit fields << 16 per reference block
+#pragma unroll
+				for(int n = 0; n < NACC; n++){
+					const uint32_t t1 = __builtin_amdgcn_perm(accR[n], accM[n], 0x06020400u);
+					const uint32_t t2 = __builtin_amdgcn_perm(accDO[2 * n], accDO[2 * n + 1], 0x06020400u);
+					cur[n] = __builtin_amdgcn_perm(t2, t1, 0x05040100u);
+					cur[NACC + n] = __builtin_amdgcn_perm(t2, t1, 0x07060302u);
+				}
+			} else if constexpr (WR == 8){
+				// M | D << 8 | R << 16 | Od << 24 per reference block
+#pragma unroll
+				for(int n = 0; n < NACC; n++){
+					const uint32_t t1 = __builtin_amdgcn_perm(accD[n], accM[n], 0x06020400u);
+					const uint32_t t2 = __builtin_amdgcn_perm(accO[n], accR[n], 0x06020400u);
+					cur[n] = __builtin_amdgcn_perm(t2, t1, 0x05040100u);
+					cur[NACC + n] = __builtin_amdgcn_perm(t2, t1, 0x07060302u);
+				}
+			} else {
+				// sixteen cells a block: dword 0 = M | D << 16, dword 1 = R | Od << 16
+				const uint32_t xm = __builtin_amdgcn_perm(accM[0], accM[1], 0x06020400u), xd = __builtin_amdgcn_perm(accD[0], accD[1], 0x06020400u);
+				const uint32_t xr = __builtin_amdgcn_perm(accR[0], accR[1], 0x06020400u), xo = __builtin_amdgcn_perm(accO[0], accO[1], 0x06020400u);
+				cur[0] = __builtin_amdgcn_perm(xd, xm, 0x05040100u); cur[1] = __builtin_amdgcn_perm(xo, xr, 0x05040100u);
+				cur[2] = __builtin_amdgcn_perm(xd, xm, 0x07060302u); cur[3] = __builtin_amdgcn_perm(xo, xr, 0x07060302u);
+			}
+			const uint32_t ri = i & 3u;
+			if constexpr (CWD == 1){
+				uint32_t *const sr = stg + 64u * ri;
+#pragma unroll
+				for(int q = 0; q < ND; q++) sr[256 * q] = cur[q];
+			} else {
+				uint32_t *const sr = stg + (64u * ND) * ri;
+#pragma unroll
+				for(int q = 0; q < ND; q++) sr[64 * q] = cur[q];
+			}
+			if(act && (ri == 3u || i + 1u == tlen)){
+				uint32_t *gp = (uint32_t*)rowp + bsa_code_off(i & ~3u, 0u, CWD);
+				if constexpr (CWD == 1){
+#pragma unroll
+					for(int q = 0; q < ND; q++){
+						const uint32_t blk = (uint32_t)(NACC * (jl + L * (q / NACC)) + q % NACC);
+						uint4 t; t.x = stg[256 * q]; t.y = stg[256 * q + 64]; t.z = stg[256 * q + 128]; t.w = stg[256 * q + 192];
+						*(uint4*)(gp + 4u * blk) = t;
+					}
+				} else {
+					// a block's four rows of two dwords are contiguous: two 16-byte pieces of two rows each
+#pragma unroll
+					for(int hb = 0; hb < 2; hb++){
+						uint32_t *bp = gp + (4u * CWD) * (uint32_t)(jl + L * hb);
+#pragma unroll
+						for(int pc = 0; pc < CWD; pc++){
+							uint4 t;
+							uint32_t *tw = (uint32_t*)&t;
+#pragma unroll
+							for(int e = 0; e < 4; e++){
+								const int lin = 4 * pc + e, row = lin / CWD, d = lin % CWD;
+								tw[e] = stg[64 * (ND * row + CWD * hb + d)];
+							}
+							*(uint4*)(bp + 4 * pc) = t;
+						}
+					}
+				}
+			}
+		}
+		// ---- tail: H^ left of every block (block 0: the virtual column, cell 0 + gape) and at the two ends of the row
+		const uint32_t hv = x_add(Hp[0], GE16);
+		const uint32_t Hsh = x_shift_down<L>(Hp[W - 1], hv, first);
+		const uint32_t bcl = x_bcast_last<L>(Hp[W - 1]);
+		if(act){
+			constexpr uint32_t LM = (uint32_t)(L - 1);
+			const bool lastrow = i + 1u == tlen;
+			if((i & LM) == (uint32_t)jl) begq = (int)rbeg;
+			if(((i & LM) == LM || lastrow) && (uint32_t)jl <= (i & LM)) begs[(i & ~LM) + 1u + (uint32_t)jl] = begq;
+			const int rbase = base + GE * ((int)rbeg + (int)i);          // H at band position p = rbase + H^ + gape p
+			auto score_at = [&](uint32_t pos) -> int {
+				const uint32_t b = pos / W, kk = pos % W;
+				const bool hi = b >= (uint32_t)L;
+				uint32_t hh = Hp[0];
+#pragma unroll
+				for(int k = 1; k < W; k++) x_sel(hh, Hp[k], __ballot((uint32_t)k == kk));          // (a plain select chain is turned into an indexed load of the row from scratch)
+				return rbase + (hi ? x_hi16(hh) : x_lo16(hh)) + GE * (int)pos;
+			};
+			if(mode != BSA_MODE_GLOBAL && rbeg + BW >= qlen){
+				const uint32_t pos = qlen - 1u - rbeg;
+				if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl){
+					const int sc = score_at(pos);
+					if(sc > cand_sc){ cand_sc = sc; cand_te = (int)i; }
+				}
+			}
+			if(lastrow && mode == BSA_MODE_GLOBAL){
+				const uint32_t pos = qlen - 1u - rbeg;
+				int *const gs = begs + tlen + 1u;
+				if(pos >= (uint32_t)BW){ if(first) *gs = (int)0x80000000u; }
+				else if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl) *gs = score_at(pos);
+			} else if(lastrow){
+				bsa_code_end_t *er = (bsa_code_end_t*)(rowp + (size_t)bsa_code_rows(tlen) * (64u * CWD));
+#pragma unroll
+				for(int q = 0; q < 16 / L; q++){ er->cand_sc[jl + L * q] = q ? BSA_SCORE_MIN : cand_sc; er->cand_te[jl + L * q] = q ? 0 : cand_te; }
+				int8_t *ub = (int8_t*)(er + 1);
+#pragma unroll
+				for(int hf = 0; hf < 2; hf++){
+					const int b = jl + L * hf;
+					auto half = [&](uint32_t x) -> int { return hf ? x_hi16(x) : x_lo16(x); };
+					er->ubegs[b * CR] = rbase + half(Hsh) + GE * (b * W - 1);
+					if constexpr (CR == 2) er->ubegs[b * CR + 1] = rbase + half(Hp[W / 2 - 1]) + GE * (b * W + W / 2 - 1);
+#pragma unroll
+					for(int k = 0; k < W; k++) ub[b * W + k] = (int8_t)(half(Hp[k]) - half((k == 0) ? Hsh : Hp[k - 1]) + GE);
+				}
+				if(last){ er->ubegs[16] = rbase + x_hi16(Hp[W - 1]) + GE * (BW - 1); er->rbeg_last = (int)rbeg; }
+			}
+		}
+		// ---- adaptive band + global steering (x_forward's, the block differences read from H^)
+		{
+			uint32_t x;
+			if constexpr (CR == 1){
+				const uint32_t dl = x_add(x_sub(Hp[W - 1], Hsh), x_i16(W * GE));          // ubegs[b + 1] - ubegs[b]
+				x = x_max(dl, x_sub(0u, dl));
+			} else {
+				const uint32_t HGE16 = x_i16((W / 2) * GE);
+				const uint32_t da = x_add(x_sub(Hp[W / 2 - 1], Hsh), HGE16), db = x_add(x_sub(Hp[W - 1], Hp[W / 2 - 1]), HGE16);
+				x = x_add(x_max(da, x_sub(0u, da)), x_max(db, x_sub(0u, db)));
+			}
+			x = x_sum<L>(x);
+			const int nzsum = (int)((x & 0xffffu) + (x >> 16));
+			const uint32_t bcf = x_bcast_first<L>(Hp[0]);
+			const int d16 = x_hi16(bcl) - x_lo16(bcf) + (BW - 1) * GE;          // ubegs[16] - ubegs[0]
+			uint32_t nz = (uint32_t)(nzsum / 16);
+			nz = nz / (uint32_t)WR * 16u / 2u;
+			const int noisy = (int)((16u > nz) ? 16u : nz);
+			int rbx;
+			if(i <= (uint32_t)BW / 4u) rbx = 0;
+			else if(rbeg + BW >= qlen) rbx = 0;
+			else if(noisy < d16) rbx = 2;
+			else if(d16 < -noisy) rbx = 0;
+			else rbx = 1;
+			if(mode == BSA_MODE_GLOBAL){
+				const int rby = __builtin_amdgcn_ds_bpermute(rby_lane + (int)((i & (uint32_t)(L - 1)) << 2), rby_tab);
+				const uint32_t left = tlen - i - 1u;
+				bool rush;
+				if(rush32) rush = act && rbeg + rzl + (uint32_t)BW <= qlen + (uint32_t)rbz - 1u;
+				else {
+					const unsigned long long lhs = (unsigned long long)rbeg + (unsigned long long)(uint32_t)rbz * left + (unsigned long long)BW;
+					rush = act && lhs <= (unsigned long long)(uint32_t)(qlen + (uint32_t)rbz - 1u);
+				}
+				if((int)rbeg < rby - BW) mov = (uint32_t)(rbx + 1);
+				else if((int)rbeg > rby) mov = (uint32_t)max(0, rbx - 1);
+				else mov = (uint32_t)rbx;
+				if(rush) mov = 1u + (uint32_t)(qlen - (rbeg + BW)) / max(left, 1u);
+			} else mov = (uint32_t)rbx;
+		}
+		// ---- speculative slide by one cell: E of every block's first cell goes to the block before it, the entering cell's behind the last
+		{
+			const uint32_t efill = x_add(__builtin_amdgcn_perm(Hp[W - 1], Hp[W - 1], 0x03020302u), x_i16(cfirst - GE - NEWNE));
+			E[W - 1] = x_shift_up<L>(tmpE0, efill, last);
+			svH = hv; svE = tmpE0;
+		}
+		i++;
+		rzl -= (uint32_t)rbz;
+		if((i & 7u) == 0u && i < tlen){ __builtin_memcpy(&twin, tp + i, 8); twin <<= 3; }
+	}
+	if(st != nullptr && row1 < tlen){
+		uint32_t *sp = st + (lt & 63);
+		int r = 0;
+		auto put = [&](uint32_t v){ __hip_atomic_store(sp + 64 * r, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); r++; };
+#pragma unroll
+		for(int k = 0; k < W; k++) put(Hp[k]);
+#pragma unroll
+		for(int k = 0; k < W; k++) put(E[k]);
+		put((uint32_t)base); put(svH); put(svE);
+		put(rbeg); put(mov); put((uint32_t)cand_sc); put((uint32_t)cand_te);
+	}
+}
+// whole pairs in the absolute-score form
+template<int L, int PW, bool DO2>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_align8_fwd_x_abs(const Align8Args a, const uint32_t rmask){
+	x_forward_abs<L, 4, PW, DO2>(a, a.first, a.count, blockIdx.x * 256u, rmask);
+}
+
 template<int W, int L, bool DO2 = false, bool SCORE = false>
 __global__ void __launch_bounds__(256) k_align8_fwd_x(const Align8Args a){
 	x_forward<W, L, 1, false, 4, DO2, false, SCORE>(a, a.first, a.count, blockIdx.x * 256u);
@@ -951,10 +1454,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
 // eight lanes per pair, the others the first a.count - n8 pairs four lanes per pair.  One launch: the short blocks start
 // first and the dispatcher hands the long ones to whichever CU has room, so pairs of one length no longer finish in
 // lock-step rounds with a nearly empty last one.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_align8_fwd_x_mix(const Align8Args a, const uint32_t nb8, const uint32_t n8){
+// ABS: the four-lane blocks run the absolute-score form (rmask = its rebase period - 1)
+template<bool ABS = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_align8_fwd_x_mix(const Align8Args a, const uint32_t nb8, const uint32_t n8, const uint32_t rmask = 0u){
 	// one staging area and one query window for both shapes (four waves; <16, 4> is the larger: 16 code dwords and 2 x 16 window dwords a lane)
 	__shared__ uint32_t mix_stage[4 * 16 * 64], mix_qwin[4 * 32 * 64];
 	if(blockIdx.x < nb8) x_forward<8, 8, 1, false, 4, false, true>(a, a.first + (a.count - n8), n8, blockIdx.x * 256u, 0u, 0xFFFFFFF8u, nullptr, mix_stage, mix_qwin);
+	else if constexpr (ABS) x_forward_abs<4, 4, 1, false, true>(a, a.first, a.count - n8, (blockIdx.x - nb8) * 256u, rmask, 0u, 0xFFFFFFF8u, nullptr, mix_stage, mix_qwin);
 	else x_forward<16, 4, 1, false, 4, false, true>(a, a.first, a.count - n8, (blockIdx.x - nb8) * 256u, 0u, 0xFFFFFFF8u, nullptr, mix_stage, mix_qwin);
 }
 
@@ -966,8 +1472,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
 // the band position and its pending move), runs the rows and hands the state on.  The launch then ends within one segment of the
 // ideal.  ctl[0] = next item, ctl[16 + g] = segments of group g that are done (release / acquire at agent scope: the next segment
 // usually runs on another CU).  An item only ever waits for an item that was handed out before it, i.e. one that is running.
-struct XQArgs { uint32_t *ctl; uint32_t *state; uint32_t ngroups, nseg, seg_rows, spin_cap; };          // ctl[0]: next ticket, ctl[1]: some wave gave up waiting, ctl[16 + g]: segments of group g done
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false>
+struct XQArgs { uint32_t *ctl; uint32_t *state; uint32_t ngroups, nseg, seg_rows, spin_cap, rmask; };          // ctl[0]: next ticket, ctl[1]: some wave gave up waiting, ctl[16 + g]: segments of group g done
+// ABS: the absolute-score form of the row body (x_forward_abs; q.rmask = its rebase period - 1)
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) k_align8_fwd_xq(const Align8Args a, const XQArgs q){
 	// one item per wave (a block is a wave: the dispatcher refills a wave slot the moment it is free); the ticket, not the block
 	// index, names the item, so that an item's predecessor is always one that has started
@@ -1004,6 +1511,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) 
 		}
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 	}
+	if constexpr (ABS){
+		static_assert(W == 16 && PW <= 1 && !SCORE, "absolute-score form");
+		x_forward_abs<L, 1, PW, DO2>(a, a.first, a.count, g * 64u, q.rmask, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
+	} else
 	x_forward<W, L, PW, false, 1, DO2, false, SCORE>(a, a.first, a.count, g * 64u, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
 	if(s + 1u < q.nseg){
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the state's write-through stores have arrived
@@ -1026,9 +1537,15 @@ size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count){
 	const size_t groups = ((size_t)count * L + 63u) / 64u;
 	return (16u + groups) * 4u + 256u + groups * (size_t)(XS_WORDS(Wl, pw) * 64u * 4u);
 }
+// name of a launch in the absolute-score form: the family's description and the rebase period that bsa_align8_abs_rows chose (tests read it)
+static const char *x_abs_name(const char *what, uint32_t rebase_rows){
+	static thread_local char buf[256];
+	snprintf(buf, sizeof buf, "%s [rebase every %u rows]", what, rebase_rows);
+	return buf;
+}
 // true when the launch was made
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false>
-static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err){
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false>
+static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err, uint32_t rebase_rows = 0u){
 	const char *qe = bsa_env("BSA_ALIGN8_XQ");
 	if(!a.xq || (qe && qe[0] == '0')) return false;
 	const uint32_t groups = (uint32_t)(((size_t)a.count * L + 63u) / 64u);
@@ -1045,12 +1562,14 @@ static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err){
 	XQArgs q;
 	q.ctl = a.xq; q.state = (uint32_t*)((uint8_t*)a.xq + ctl_bytes); q.ngroups = groups; q.nseg = nseg; q.seg_rows = seg_rows;
 	q.spin_cap = 1u << 22;
+	q.rmask = ABS ? rebase_rows - 1u : 0u;
 	if(const char *sc = bsa_env("BSA_ALIGN8_XQ_SPIN_CAP")){ const long v = atol(sc); if(v >= 1) q.spin_cap = (uint32_t)v; }          // (test hook: a cap of a few turns makes hand-over waits give up)
 	err = hipMemsetAsync(a.xq, 0, ctl_bytes, st);
 	if(err != hipSuccess) return true;
-	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE>), dim3(groups * nseg), dim3(64), 0, st, a, q);
+	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE, ABS>), dim3(groups * nseg), dim3(64), 0, st, a, q);
 	err = hipGetLastError();
 	bsa_last_fwd_kernel = SCORE ? "k_align8_fwd_xq score-only (exact-arithmetic forward DP in row segments, no traceback codes)"
+		: ABS ? x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, 4-bit traceback codes)", rebase_rows)
 		: "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
 	return true;
 }
@@ -1079,6 +1598,38 @@ bool bsa_align8_x_supported(const Align8Args &a, int pw){
 	return m + 3 * g + 2 * ge <= 100 && n + m + g + 2 * ge <= 110 && 63 + 2 * ge + n + m + 2 * g <= 125;
 }
 
+// Rebase period of the absolute-score form (x_forward_abs) in rows, a power of two; 0 = this launch keeps the difference form.
+// The form exists for one-piece and linear gaps at bandwidth 128 and 256 (sixteen cells a half).  Bound, with m = smax, go = -gapo, ge = -gape, g = go + ge, in the frame
+// H^ = H - gape (x + y) - base:
+//   * step along a computed row, u^ = H^(x, y) - H^(x - 1, y): at least -go, because F^(x) >= H^(x - 1) + gapo; at most m + go + 2 ge, by induction over the rows: if h comes from F,
+//     u^ <= 0; from the diagonal, H^(x - 1, y) >= E^ >= H^(x - 1, y - 1) + gapo gives u^ <= S~ - gapo <= m + 2 ge + go; from E, both columns took the same gap from a row y' and
+//     u^(y) <= u^(y').  Cells behind the band end enter flat (u^ = 0) behind one step of cfirst - gape < 0, which only ever lowers the upper bound's induction.  So a row of bw cells
+//     spans at most s bw with s = max(go, m + go + 2 ge).
+//   * drift from row to row: every cell is at least its upper neighbour's H^ + gapo and at most the previous row's maximum + max(S~) = m + 2 ge: at most s a row, either way.
+//   * what is not a computed cell lies within K = 512 of one: E^ and F^ (within go), mg = m + gapo, the -63 - 2 ge sentinels of F and of the first-cell rule, the virtual column
+//     (+ gape), the entering cells (cfirst - gape - gape >= -100 - 2 ge inside the guard), the pads beyond the query end.  A band that jumps past all it held starts from a row that
+//     is -gape p by construction: the SCORE_MIN of its real scores is carried by the int32 base, not by the int16 row.
+// A rebase makes the row's first slot 0; R rows later every value lies within s (bw + R) + K of it: R is the largest power of two up to 64 with s (bw + R) + K <= 32767, and a scoring
+// that leaves no R >= 8 keeps the difference form.  (The benchmark's scoring: s = 9, 9 (128 + 64) + 512 = 2240.)
+// BSA_ALIGN8_ABS=0 keeps the difference form.  BSA_ALIGN8_ABS_R=<rows> (test hook) shortens the period: the largest power of two that is at most <rows>, at least 8 and at most
+// the derived R; anything that is not a number of at least 8 gives 8.
+uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw){
+	const char *e = bsa_env("BSA_ALIGN8_ABS");
+	if((e && e[0] == '0') || pw > 1 || !(a.bw == 128u || a.bw == 256u) || !bsa_align8_x_supported(a, pw)) return 0u;
+	const int go = -(int)(int8_t)a.gapo1, ge = -(int)(int8_t)a.gape1, m = a.smax;
+	const int s = std::max(go, m + go + 2 * ge);
+	uint32_t r = 64u;
+	while(r >= 8u && s * (int)(a.bw + r) + 512 > 32767) r >>= 1;
+	if(r < 8u) return 0u;
+	if(const char *re = bsa_env("BSA_ALIGN8_ABS_R")){
+		const long want = std::max(atol(re), 8L);
+		uint32_t f = 8u;
+		while(f * 2u <= r && (long)(f * 2u) <= want) f *= 2u;
+		r = f;
+	}
+	return r;
+}
+
 // the code rows with two-bit D / Od fields (Align8Args::code_fmt 1): what the forward kernels need; the traceback side is asked in bsa_api.hip
 bool bsa_align8_do2_supported(const Align8Args &a, int pw){
 	const int go = -(int)(int8_t)a.gapo1;
@@ -1094,9 +1645,16 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		// two-bit D / Od fields (bsa_align8_do2_supported): bandwidth 128, one-piece gaps, four lanes per pair
 		if(pw != 1 || a.bw != 128u) return hipErrorInvalidValue;
 		hipError_t qe = hipSuccess;
+		const uint32_t rr = bsa_align8_abs_rows(a, pw);          // rebase period of the absolute-score form, 0: the difference form
 		if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
 			hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, true>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
 			bsa_last_fwd_kernel = "k_align8_fwd_x_static (exact-arithmetic forward DP, band in place, traceback codes with two-bit D/Od fields)";
+		} else if(rr && x_launch_xq<16, 4, 1, true, 3, false, true>(a, st, qe, rr)){
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", rr);
+			return qe;
+		} else if(rr){
+			hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, true>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a, rr - 1u);
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", rr);
 		} else if(x_launch_xq<16, 4, 1, true>(a, st, qe)){
 			bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, traceback codes with two-bit D/Od fields)";
 			return qe;
@@ -1142,6 +1700,15 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 	hipError_t qerr = hipSuccess;
 	if(pw == 0){
 		if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 0>(a, st, qerr)) return qerr;
+		if(const uint32_t rr = bsa_align8_abs_rows(a, pw)){
+			// absolute-score form (bandwidth 128, 256): row segments, else whole pairs
+			if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
+			if(a.bw == 256u && x_launch_xq<16, 8, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
+			if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 0, false>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a, rr - 1u);
+			else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr);
+			return hipGetLastError();
+		}
 		if(a.bw == 128u && x_launch_xq<16, 4, 0>(a, st, qerr)) return qerr;
 		if(a.bw == 256u && x_launch_xq<16, 8, 0>(a, st, qerr)) return qerr;
 		switch(a.bw / 16){
@@ -1156,6 +1723,14 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		return hipGetLastError();
 	}
 	if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 1>(a, st, qerr)) return qerr;
+	const uint32_t rr1 = bsa_align8_abs_rows(a, pw);          // rebase period of the absolute-score form, 0: the difference form
+	if(rr1 && a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1, false, 3, false, true>(a, st, qerr, rr1)) return qerr;
+	if(rr1 && a.bw == 256u){
+		if(x_launch_xq<16, 8, 1, false, 3, false, true>(a, st, qerr, rr1)) return qerr;
+		hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
+		bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1);
+		return hipGetLastError();
+	}
 	if(a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1>(a, st, qerr)) return qerr;
 	if(a.bw == 256u && x_launch_xq<16, 8, 1>(a, st, qerr)) return qerr;
 	switch(a.bw / 16){
@@ -1180,11 +1755,18 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 			if(le && le[0] == '8') n4 = 0;
 			if(le && le[0] == '4') n4 = a.count;
 			if(const char *ne = bsa_env("BSA_ALIGN8_X_N8")){ const long v = atol(ne); if(v >= 0 && (uint32_t)v <= a.count) n4 = a.count - (uint32_t)v; }      // tuning: pairs that go eight lanes per pair
-			if(n4 == a.count) hipLaunchKernelGGL((k_align8_fwd_x<16, 4>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a);
+			// (the four-lane shape runs the absolute-score form where it applies; the eight-lane one, eight cells a half, has none)
+			if(n4 == a.count && rr1){
+				hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, false>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a, rr1 - 1u);
+				bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1);
+			} else if(n4 == a.count) hipLaunchKernelGGL((k_align8_fwd_x<16, 4>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a);
 			else if(n4 == 0) hipLaunchKernelGGL((k_align8_fwd_x<8, 8>), dim3(b8), dim3(256), 0, st, a);
 			else {
 				const uint32_t n8 = a.count - n4, nb8 = (n8 + 31u) / 32u;
-				hipLaunchKernelGGL(k_align8_fwd_x_mix, dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8);
+				if(rr1){
+					hipLaunchKernelGGL((k_align8_fwd_x_mix<true>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, rr1 - 1u);
+					bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x_mix (exact-arithmetic forward DP, absolute scores in the four-lane blocks, 4-bit traceback codes)", rr1);
+				} else hipLaunchKernelGGL((k_align8_fwd_x_mix<false>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, 0u);
 			}
 			break;
 		}
