@@ -25,16 +25,14 @@
 //     Rows that do not move (or move by more) are corrected afterwards, under a wave-level branch.
 //   * ubegs are kept as PN[b] = ubegs[b+1] - ubegs[0] - (b+1) W gape in packed int16 plus ubegs[0] in an int32.
 // Values are value << 8 in each int16 half (as in the packed kernel), so S~ comes out of v_perm_b32 byte lookups.
+// Two row bodies: x_forward holds the row as int8 differences (above; every shape), x_forward_abs as int16 scores (its own comment; one-piece and linear gaps with
+// sixteen cells a half, where it is 11 % faster).  The pair preamble, the LDS carving, the target-base window, the band steering, the code-row store, the band
+// offsets / end record and the hand-over between row segments are written in both, statement for statement: a fix to one of them goes into both.  (Moving any of
+// them into a force-inlined helper changes this compiler's output for the file's kernels, measurably so for some: HISTORY.md 11b.)
 #include "bsa_common.h"
 #include "bsa_dpp.h"
 #include <algorithm>
 #include <cstdio>
-#ifndef XQ_BEGS16
-#define XQ_BEGS16 0              // 1: band offsets leave sixteen rows (one 64-byte line) at a time instead of four (16 bytes at an odd dword).  Measured at C2 with
-                                 // slots at multiples of 256 bytes: WRITE_SIZE 80.0 -> 69.7 GB (= the 69.6 GB the kernel has to store), forward 59.6 -> 60.2 ms (two-piece
-                                 // gaps 123.9 -> 125.5): the partial lines cost traffic, not time, and the kernel is bound by its instructions -- off
-#endif
-
 typedef short xv2s __attribute__((ext_vector_type(2)));
 typedef unsigned short xv2u __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ uint32_t x_add(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) + __builtin_bit_cast(xv2u, b))); }
@@ -130,6 +128,7 @@ static __device__ __forceinline__ void x_load_qcodes(const uint8_t *p, uint32_t 
 	else if constexpr (W == 2){ uint16_t v; __builtin_memcpy(&v, p, 2); w[0] = v | 0x04040000u; }
 	else w[0] = p[0] | 0x04040400u;
 }
+
 
 // W cells per lane and half, L lanes per pair: 2 L blocks of W cells; the reference's 16 running blocks have WR = 2 L W / 16
 // cells, so a block here holds CR = 8 / L of them
@@ -294,17 +293,8 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 	// the dword its offset has reached -- no shifting into place, no lookup of packed codes, no spreading of the looked-up bytes.  The selectors depend on
 	// the query alone; they are built when the window is loaded, every 2 KD - W columns of band movement (about 15 rows), for all the live pairs of the wave at
 	// once (below).  The staged query is padded far enough behind its end (plan: bandwidth + BSA_QPAD_TAIL bytes).
-#ifdef XQ_NO_QWIN
-	constexpr bool QWIN = false;
-#else
 	constexpr bool QWIN = !STATIC && PW != 2 && W == 16;      // (measured: two-piece gaps at 251 registers lose 3 % with it, eight cells a half gain nothing)
-#endif
-	// band offsets leave sixteen rows at a time through four LDS dwords a lane (below, "band offsets"); the window gives them up -- 12 instead of 16 columns of
-	// band movement between refills -- so that the block's LDS stays what three waves per SIMD allow (one KB more a wave cost 5 % of the launch)
-	constexpr bool BQ16 = XQ_BEGS16 && L == 4 && !EXT;
-	__shared__ uint32_t x_bq[BQ16 ? NWV : 1][BQ16 ? 4 : 1][64];
-	uint32_t *const bqp = &x_bq[(BQ16 && NWV > 1) ? (lt >> 6) : 0][0][lt & 63];
-	constexpr int KD = NQ + ((BQ16 && QWIN) ? 10 : 12);   // the window is 2 KD dwords a lane
+	constexpr int KD = NQ + 12;   // the window is 2 KD dwords a lane
 	constexpr int NSEL = 2 * KD;                          // selectors (band columns) in the window
 	constexpr uint32_t QOFFMAX = (uint32_t)(NSEL - W);    // the last offset at which selectors off .. off + W - 1 are all inside
 	static_assert(!QWIN || (NSEL % 4 == 0 && NSEL - W <= BSA_QPAD_TAIL), "a refill reads NSEL - W bytes behind the band's last block: the staged query's padding (bsa_api.hip: qpad = bandwidth + BSA_QPAD_TAIL) must cover it");
@@ -774,23 +764,9 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 			// band offsets: lane (i mod L) keeps the offset of row i, the group stores them together
 			constexpr uint32_t LM = (uint32_t)(L - 1);
 			const bool lastrow = i + 1u == tlen;
-			if constexpr (SCORE){}
-			else if constexpr (BQ16){
-				// Four rows of offsets are 16 bytes at an odd dword: stored as they come, every piece is a partial sector that the L2 has written back long
-				// before its neighbours arrive (48 us later).  The lane keeps its last four offsets in LDS slots of its own (slot (row >> 2) & 3) and the
-				// pair stores begs[16 k .. 16 k + 15] -- rows 16 k - 1 .. 16 k + 14, one whole line -- when row 16 k + 14 is done; what is pending at the end of
-				// the pair or of the segment leaves row by row.
-				if((i & 3u) == (uint32_t)jl) bqp[64u * ((i >> 2) & 3u)] = rbeg;
-				if((i & 15u) == 14u || lastrow || i + 1u == row1){
-					const uint32_t pf = (i >= 15u) ? (((i - 15u) & ~15u) + 15u) : 0u;          // first row no earlier flush has taken
-					const int lo = (int)max(row0, pf);
-#pragma unroll
-					for(int sl = 0; sl < 4; sl++){
-						const int row = (int)i - (int)((i - (uint32_t)(4 * sl + jl)) & 15u);
-						if(row >= lo) begs[row + 1] = (int)bqp[64 * sl];
-					}
-				}
-			} else {
+			// (four rows of offsets are 16 bytes at an odd dword, partial lines in memory; sixteen rows -- one 64-byte line -- leaving at a time through LDS were measured
+			// at C2: WRITE_SIZE 80.0 -> 69.7 GB, forward 59.6 -> 60.2 ms: the partial lines cost traffic, not time)
+			if constexpr (!SCORE){
 			if((i & LM) == (uint32_t)jl) begq = (int)rbeg;
 			if(((i & LM) == LM || lastrow) && (uint32_t)jl <= (i & LM)) begs[(i & ~LM) + 1u + (uint32_t)jl] = begq;
 			}
@@ -1640,32 +1616,31 @@ bool bsa_align8_do2_supported(const Align8Args &a, int pw){
 static bool x8_at_64(){ const char *e = bsa_env("BSA_ALIGN8_X_LANES"); return e && e[0] == '8'; }
 hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 	if(a.count == 0) return hipSuccess;
-	const uint32_t b8 = (a.count + 31u) / 32u;
+	const uint32_t b4 = (a.count + 63u) / 64u, b8 = (a.count + 31u) / 32u;          // blocks of 256 lanes at four / eight lanes per pair
 	if(a.code_fmt == 1u){
 		// two-bit D / Od fields (bsa_align8_do2_supported): bandwidth 128, one-piece gaps, four lanes per pair
 		if(pw != 1 || a.bw != 128u) return hipErrorInvalidValue;
 		hipError_t qe = hipSuccess;
 		const uint32_t rr = bsa_align8_abs_rows(a, pw);          // rebase period of the absolute-score form, 0: the difference form
 		if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
-			hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, true>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
+			hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, true>), dim3(b4), dim3(256), 0, st, a);
 			bsa_last_fwd_kernel = "k_align8_fwd_x_static (exact-arithmetic forward DP, band in place, traceback codes with two-bit D/Od fields)";
 		} else if(rr && x_launch_xq<16, 4, 1, true, 3, false, true>(a, st, qe, rr)){
 			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", rr);
 			return qe;
 		} else if(rr){
-			hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, true>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a, rr - 1u);
+			hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, true>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
 			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", rr);
 		} else if(x_launch_xq<16, 4, 1, true>(a, st, qe)){
 			bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, traceback codes with two-bit D/Od fields)";
 			return qe;
 		} else {
-			hipLaunchKernelGGL((k_align8_fwd_x<16, 4, true>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
+			hipLaunchKernelGGL((k_align8_fwd_x<16, 4, true>), dim3(b4), dim3(256), 0, st, a);
 			bsa_last_fwd_kernel = "k_align8_fwd_x (exact-arithmetic forward DP, traceback codes with two-bit D/Od fields)";
 		}
 		return hipGetLastError();
 	}
 	if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
-		const uint32_t b4 = (a.count + 63u) / 64u;
 		if(pw == 2 && a.bw == 128u){ hipLaunchKernelGGL((k_align8_fwd_x_static<8, 8, 2>), dim3(b8), dim3(256), 0, st, a); return hipGetLastError(); }
 		if(pw == 1 && a.bw == 64u){ hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 1>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
 		if(pw == 1 && a.bw == 128u){ hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
@@ -1678,7 +1653,7 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		hipError_t qe2 = hipSuccess;
 		bsa_last_fwd_kernel = "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)";
 		if(x_launch_xq<8, 4, 2>(a, st, qe2)) return qe2;
-		hipLaunchKernelGGL((k_align8_fwd_x2w<8, 4>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
+		hipLaunchKernelGGL((k_align8_fwd_x2w<8, 4>), dim3(b4), dim3(256), 0, st, a);
 		return hipGetLastError();
 	}
 	if(pw == 2 && a.bw == 256u){
@@ -1704,7 +1679,7 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 			// absolute-score form (bandwidth 128, 256): row segments, else whole pairs
 			if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
 			if(a.bw == 256u && x_launch_xq<16, 8, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
-			if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 0, false>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a, rr - 1u);
+			if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 0, false>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
 			else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
 			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr);
 			return hipGetLastError();
@@ -1714,9 +1689,9 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		switch(a.bw / 16){
 			case 4:
 				if(x8_at_64()) hipLaunchKernelGGL((k_align8_fwd_x0<4, 8>), dim3(b8), dim3(256), 0, st, a);
-				else hipLaunchKernelGGL((k_align8_fwd_x0<8, 4>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
+				else hipLaunchKernelGGL((k_align8_fwd_x0<8, 4>), dim3(b4), dim3(256), 0, st, a);
 				break;
-			case 8:  hipLaunchKernelGGL((k_align8_fwd_x0<16, 4>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a); break;
+			case 8:  hipLaunchKernelGGL((k_align8_fwd_x0<16, 4>), dim3(b4), dim3(256), 0, st, a); break;
 			case 16: hipLaunchKernelGGL((k_align8_fwd_x0<16, 8>), dim3(b8), dim3(256), 0, st, a); break;
 			default: return hipErrorInvalidValue;
 		}
@@ -1736,20 +1711,15 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 	switch(a.bw / 16){
 		case 4:      // bandwidth 64: four lanes per pair (16 pairs per wave, eight cells per half); BSA_ALIGN8_X_LANES=8: eight lanes
 			if(x8_at_64()) hipLaunchKernelGGL((k_align8_fwd_x<4, 8>), dim3(b8), dim3(256), 0, st, a);
-			else hipLaunchKernelGGL((k_align8_fwd_x<8, 4>), dim3((a.count + 63u) / 64u), dim3(256), 0, st, a);
+			else hipLaunchKernelGGL((k_align8_fwd_x<8, 4>), dim3(b4), dim3(256), 0, st, a);
 			break;
 		case 8: {
 			// Four lanes per pair (16 pairs per wave) cost 620 instructions per row of a wave, eight lanes per pair 387.
 			// Pairs of one length finish together, so what counts is the largest number of waves any SIMD gets: whole
 			// rounds of one four-lane wave per SIMD, and a remainder of at most half a round as eight-lane waves (0.62 of
 			// a round instead of a whole one).  BSA_ALIGN8_X_LANES=4 / 8 forces one shape.
-			static const int cus = [](){
-				int dev = 0, v = 0;
-				if(hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-				return v;
-			}();
 			const char *le = bsa_env("BSA_ALIGN8_X_LANES");
-			const uint32_t round4 = (uint32_t)cus * 4u * 16u;
+			const uint32_t round4 = (uint32_t)x_cus() * 4u * 16u;
 			uint32_t n4 = a.count / round4 * round4;
 			if(a.count - n4 > round4 / 2u) n4 = a.count;
 			if(le && le[0] == '8') n4 = 0;
