@@ -137,6 +137,8 @@ def lib():
         L.bsa_align_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(AlignParams),
                                       vp, u32p, C.c_size_t, u64p, u32p]
         L.bsa_align_plan_create.argtypes = [vp, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(AlignParams), C.POINTER(vp)]
+        if hasattr(L, "bsa_align8_abs_form_internal"):          # (a BSA_LIB_PATH build from before it: everything else still runs)
+            L.bsa_align8_abs_form_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
         L.bsa_align_plan_destroy.argtypes = [vp]
         L.bsa_align_plan_destroy.restype = None
         L.bsa_align_plan_cells.argtypes = [vp]
@@ -222,6 +224,15 @@ def make_params(mode=MODE_GLOBAL, bandwidth=128, M=2, X=-6, O=-3, E=-2, Q=0, P=0
             p.matrix[i] = int(matrix[i])
     p.gapo1, p.gape1, p.gapo2, p.gape2 = O, E, Q, P
     return p
+
+
+def align8_abs_form(par):
+    """what the 8-bit forward launcher decides for a scoring at par.bandwidth 128 or 256 (bsa_align8_abs_rows; host only): (form, rows) with form -1 = not
+    taken by the exact-arithmetic kernel, 0 = difference form, 1 = absolute scores with integer maxima, 2 = with three-operand maxima in the biased frame,
+    and rows the rebase period"""
+    rows = C.c_uint32(0)
+    form = lib().bsa_align8_abs_form_internal(C.byref(par), C.byref(rows))
+    return int(form), int(rows.value)
 
 
 def pack2bit(codes):

@@ -38,6 +38,13 @@ typedef unsigned short xv2u __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ uint32_t x_add(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) + __builtin_bit_cast(xv2u, b))); }
 static __device__ __forceinline__ uint32_t x_sub(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) - __builtin_bit_cast(xv2u, b))); }
 static __device__ __forceinline__ uint32_t x_max(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(xv2s, a), __builtin_bit_cast(xv2s, b))); }
+// max(a, b, c) per half in ONE instruction (v_pk_maximum3_f16; there is no three-operand packed integer maximum): the halves are read as f16, whose order is that
+// of int16 for the patterns 0x0400 .. 0x7BFF (positive, finite, normal: no sign, no NaN, nothing a denormal mode could flush), and the result is one of the
+// operands, bit for bit.  The caller keeps every operand in that range (x_forward_abs, "biased frame").
+typedef _Float16 xv2h __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ uint32_t x_max3(uint32_t a, uint32_t b, uint32_t c){
+	return __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(xv2h, a), __builtin_bit_cast(xv2h, b)), __builtin_bit_cast(xv2h, c)));
+}
 static __device__ __forceinline__ uint32_t x_minu(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(xv2u, a), __builtin_bit_cast(xv2u, b))); }
 static __device__ __forceinline__ uint32_t x_satsubu(uint32_t a, uint32_t b){ return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(xv2u, a), __builtin_bit_cast(xv2u, b))); }
 // acc * 2 + flag per half: one v_pk_mad_u16 as long as the compiler cannot see that `two` is the constant 0x00020002 (it
@@ -927,7 +934,20 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 // PW: 1 one-piece gaps, 0 linear gaps (gapo = 0: E^ of a cell is its upper neighbour's H^, R and Od are always set).  DO2: the two-bit D / Od fields (four lanes, one piece);
 // otherwise the four planes, with D (h == E) and Od (field == -gapo) accumulated as they are stored too.  L = 8: bandwidth 256, a half is one reference block of sixteen cells.
 // EXT: the staging area and the window come from the caller (k_align8_fwd_x_mix).
-template<int L, int NWV, int PW = 1, bool DO2 = true, bool EXT = false>
+// M3: THREE-OPERAND MAXIMA in a BIASED FRAME.  m and mg are never formed:
+//     pass 1:  d = Hp + S~     t = max3(t, E, d)                      (t enters as fini - gapo, F leaving the block is t + gapo:
+//                                                                      max(fini, max_k (max(E_k, d_k) + gapo)) with the addition taken out of the maximum)
+//     pass 2:  h = max3(E, d, f)   hg = h + gapo   fm = max(f, hg)   En = max(E, hg)
+// fm is what it was: max(f, hg) = max(f, m + gapo, f + gapo) = max(f, mg) because gapo <= 0.  R is fm == hg: where f <= m that is the same comparison (h = m), and where
+// f > m both are false for gapo < 0 (hg = f + gapo < f = fm, and mg < f = fm), which one-piece gaps always have (bsa_align8_x_supported).  Linear gaps: fm = En = h.
+// max3 is the f16 instruction (x_max3), so every operand of it -- Hp / d, E, f, the sentinels -- must be an int16 in 0x0400 .. 0x7BFF.  The frame therefore sits at B = 0x4000
+// instead of 0: a rebase makes lane 0's first slot B, not 0, and whatever writes absolute H^ / E^ values (row -1, the row a jumping band starts from) adds B, with -B folded
+// into base, so that H = base + H^ + gape (x + y) holds wherever it is read.  Everything else is relative to a value of the row and needs nothing.  bsa_align8_abs_rows
+// has the bound that keeps the values inside B +- 15359.  Only the maxima are f16: every addition and subtraction stays packed integer, and so do the F scan (its
+// 0x8000 filler is no score; what leaves the scan is one) and the maxima of fm and En.  Lanes of dead pairs (tlen = 0) and of rows past a short target carry arbitrary
+// patterns, NaNs included, through the maxima: nothing they compute is stored, and nothing crosses from one pair's lanes into another's.
+// M3 = false keeps the integer recurrence above in the frame at 0, for the scorings whose bound does not fit the biased frame (bandwidth 256 only: bsa_align8_abs_rows).
+template<int L, int NWV, int PW = 1, bool DO2 = true, bool EXT = false, bool M3 = true>
 static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const uint32_t first_pos, const uint32_t count, const uint32_t tid_base, const uint32_t rmask,
 		const uint32_t row0 = 0u, const uint32_t row1 = 0xFFFFFFF8u, uint32_t *st = nullptr, uint32_t *ext_stage = nullptr, uint32_t *ext_qwin = nullptr){
 	constexpr int W = 16, BW = 2 * L * W, WR = BW / 16, CR = 8 / L;
@@ -954,8 +974,8 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 	const uint32_t ONE1 = 0x00010001u;
 	uint32_t TWO = 0x00020002u;
 	asm volatile("" : "+s"(TWO));
-	uint32_t KDO0 = 0x00400040u, KDO1 = 0x00100010u, KDO2 = 0x00040004u;
-	asm volatile("" : "+s"(KDO0), "+s"(KDO1), "+s"(KDO2));
+	uint32_t FOUR = 0x00040004u;
+	asm volatile("" : "+s"(FOUR));
 	const uint32_t DOSP = (GO == -1) ? 2u : 1u;
 	const uint32_t MINF16 = x_i16(BSA_EPI8_MIN - 2 * GE);
 	const int gopen = gapo1 + gape1;
@@ -964,6 +984,8 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 	const int NEWNE = (PW == 0) ? 0 : GE;                  // gape - e of an entering cell (e = 0; linear gaps: e is the constant gape)
 	const int NE0 = (PW == 0) ? 0 : GE - BSA_EPI8_MIN;     // ... of row -1 (e = -63)
 	const uint32_t NGO1 = x_i16(-GO - 1);
+	static_assert(M3 || L == 8, "no scoring inside bsa_align8_x_supported leaves the biased frame at bandwidth 128 (bsa_align8_abs_rows)");
+	constexpr int FB = M3 ? 0x4000 : 0;                    // where the frame sits: H^ of lane 0's first slot after a rebase
 	__shared__ __attribute__((aligned(8))) uint32_t xa_mtab[8];
 	if((lt & 63) < 4){
 		const int t = lt & 3;
@@ -984,20 +1006,20 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		// row -1 (bsalign.h:2094-2140), slid by one cell: Hp[k] = H^ at band position p, E[k] = E^ at p + 1 (e = -63)
 		const int first_u = (int)(int8_t)(gapo1 + gape1 + a.smin - a.smax);
 		const bool ov = mode == BSA_MODE_OVERLAP;
-		base = ov ? 0 : gapo1 + 2 * gape1;
+		base = (ov ? 0 : gapo1 + 2 * gape1) - FB;
 #pragma unroll
 		for(int k = 0; k < W; k++){
-			// global / extend: H(p, -1) = gapo + (p + 1) gape: H^ = 0; overlap: H = 0: H^ = -gape (p - 1)
-			Hp[k] = ov ? x_add(NGP, x_i16(GE - GE * k)) : 0u;
-			E[k] = ov ? x_add(NGP, x_i16(-GE * k - NE0)) : x_i16(-NE0);
+			// global / extend: H(p, -1) = gapo + (p + 1) gape: H^ = 0; overlap: H = 0: H^ = -gape (p - 1); both above FB
+			Hp[k] = ov ? x_add(NGP, x_i16(FB + GE - GE * k)) : x_i16(FB);
+			E[k] = ov ? x_add(NGP, x_i16(FB - GE * k - NE0)) : x_i16(FB - NE0);
 		}
 		// the entering cell behind the row's last one
 		if(last){
 			const uint32_t hl = (Hp[W - 1] >> 16) + (uint32_t)(cfirst - GE - NEWNE);
 			E[W - 1] = (E[W - 1] & 0xffffu) | (hl << 16);
 		}
-		svH = ov ? x_i16(2 * GE) : x_i16(GE - first_u);
-		svE = ov ? x_i16(GE - NE0) : x_i16(-NE0);
+		svH = ov ? x_i16(FB + 2 * GE) : x_i16(FB + GE - first_u);
+		svE = ov ? x_i16(FB + GE - NE0) : x_i16(FB - NE0);
 	}
 	if(row0 != 0u){
 		const uint32_t *sp = st + (lt & 63);
@@ -1035,11 +1057,11 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		// ---- rebase (i is uniform)
 		if((i & rmask) == 0u){
 			const uint32_t bc = x_bcast_first<L>(Hp[0]);
-			const uint32_t dl = __builtin_amdgcn_perm(bc, bc, 0x01000100u);
+			const uint32_t dl = x_sub(__builtin_amdgcn_perm(bc, bc, 0x01000100u), x_i16(FB));          // the slot becomes FB
 #pragma unroll
 			for(int k = 0; k < W; k++){ Hp[k] = x_sub(Hp[k], dl); E[k] = x_sub(E[k], dl); }
 			svH = x_sub(svH, dl); svE = x_sub(svE, dl);
-			base += x_lo16(bc);
+			base += x_lo16(bc) - FB;
 		}
 		mov = min(mov, __builtin_elementwise_sub_sat(qlen, rbeg + (uint32_t)BW));
 		rbeg += mov;
@@ -1053,10 +1075,10 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 				const int rhz = base + x_hi16(bc) + GE * ((int)(rbeg - mov) + BW - 1 + (int)i - 1);
 				if(z){
 					rhj = rhz;
-					// a row of SCORE_MIN with e = 0: base such that the diagonal predecessor of band position 0 has H^ = 0
-					base = BSA_SCORE_MIN - GE * ((int)rbeg + (int)i - 2);
+					// a row of SCORE_MIN with e = 0: base such that the diagonal predecessor of band position 0 has H^ = FB
+					base = BSA_SCORE_MIN - GE * ((int)rbeg + (int)i - 2) - FB;
 #pragma unroll
-					for(int k = 0; k < W; k++){ Hp[k] = x_add(NGP, x_i16(-GE * k)); E[k] = x_add(NGP, x_i16(-GE * (k + 1) - NEWNE)); }
+					for(int k = 0; k < W; k++){ Hp[k] = x_add(NGP, x_i16(FB - GE * k)); E[k] = x_add(NGP, x_i16(FB - GE * (k + 1) - NEWNE)); }
 				}
 			}
 			if(__any(act && mov == 0u)){
@@ -1136,15 +1158,26 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 			q0d = (cd >= -128 && cd <= 127) ? ((uint32_t)(hp0 + cd) & 0xffffu) : 0x10000u;
 		}
 		// ---- pass 1: F leaving every block when nothing but the sentinel enters it
-		uint32_t d[W], m[W], mg[W];
+		uint32_t d[W], m[M3 ? 1 : W], mg[M3 ? 1 : W];
 		const uint32_t fini = x_add(Hp[0], MINF16);
 		uint32_t f = fini;
+		if constexpr (M3){
+			// (the opening is added once, behind the sixteen maxima)
+			if constexpr (PW != 0) f = x_sub(f, GO16);
+#pragma unroll
+			for(int k = 0; k < W; k++){
+				d[k] = (k == 0) ? d0s : x_add(Hp[k], S[k]);
+				f = x_max3(f, E[k], (k == 0) ? d0h : d[k]);
+			}
+			if constexpr (PW != 0) f = x_add(f, GO16);
+		} else {
 #pragma unroll
 		for(int k = 0; k < W; k++){
 			d[k] = (k == 0) ? d0s : x_add(Hp[k], S[k]);
 			m[k] = x_max(E[k], (k == 0) ? d0h : d[k]);
 			mg[k] = (PW == 0) ? m[k] : x_add(m[k], GO16);
 			f = x_max(f, mg[k]);
+		}
 		}
 		// ---- F-penetration: prefix maximum over the blocks
 		{
@@ -1162,16 +1195,28 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		uint32_t tmpE0 = 0, hfirst = 0;
 #pragma unroll
 		for(int k = 0; k < W; k++){
-			const uint32_t h = x_max(m[k], f);
+			uint32_t h, en;
+			if constexpr (M3){
+				h = x_max3(E[k], (k == 0) ? d0h : d[k], f);
+				if constexpr (PW != 0){
+					const uint32_t hg = x_add(h, GO16);
+					const uint32_t fm = x_max(f, hg);
+					accR[k >> 3] = x_acc(accR[k >> 3], x_satsubu(ONE1, x_sub(fm, hg)), TWO);
+					f = fm;
+					en = x_max(E[k], hg);
+				} else { f = h; en = h; }
+			} else {
+			h = x_max(m[k], f);
 			const uint32_t fm = x_max(f, mg[k]);
 			f = fm;
 			if constexpr (PW != 0) accR[k >> 3] = x_acc(accR[k >> 3], x_satsubu(ONE1, x_sub(fm, mg[k])), TWO);
-			const uint32_t en = (PW == 0) ? h : x_max(E[k], x_add(h, GO16));          // (gapo = 0: h >= E)
+			en = (PW == 0) ? h : x_max(E[k], x_add(h, GO16));          // (gapo = 0: h >= E)
+			}
 			if constexpr (DO2){
 				const uint32_t fld = x_sub(h, en);
-				const uint32_t kk = ((k & 3) == 0) ? KDO0 : ((k & 3) == 1) ? KDO1 : KDO2;
-				if((k & 3) == 3) accDO[k >> 2] = x_add(accDO[k >> 2], fld);
-				else accDO[k >> 2] = x_acc(fld, accDO[k >> 2], kk);
+				// four fields a byte, the first on top: fld0 * 64 + fld1 * 16 + fld2 * 4 + fld3 by Horner, three multiply-adds by construction
+				if((k & 3) == 0) accDO[k >> 2] = fld;
+				else accDO[k >> 2] = x_acc(accDO[k >> 2], fld, FOUR);
 			} else {
 				accD[k >> 3] = x_acc(accD[k >> 3], x_satsubu(ONE1, x_sub(h, E[k])), TWO);
 				if constexpr (PW != 0) accO[k >> 3] = x_acc(accO[k >> 3], x_satsubu(x_sub(h, en), NGO1), TWO);          // field == -gapo
@@ -1396,10 +1441,10 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		put(rbeg); put(mov); put((uint32_t)cand_sc); put((uint32_t)cand_te);
 	}
 }
-// whole pairs in the absolute-score form
-template<int L, int PW, bool DO2>
+// whole pairs in the absolute-score form (M3: x_forward_abs's three-operand maxima in the biased frame)
+template<int L, int PW, bool DO2, bool M3 = true>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_align8_fwd_x_abs(const Align8Args a, const uint32_t rmask){
-	x_forward_abs<L, 4, PW, DO2>(a, a.first, a.count, blockIdx.x * 256u, rmask);
+	x_forward_abs<L, 4, PW, DO2, false, M3>(a, a.first, a.count, blockIdx.x * 256u, rmask);
 }
 
 template<int W, int L, bool DO2 = false, bool SCORE = false>
@@ -1449,8 +1494,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
 // ideal.  ctl[0] = next item, ctl[16 + g] = segments of group g that are done (release / acquire at agent scope: the next segment
 // usually runs on another CU).  An item only ever waits for an item that was handed out before it, i.e. one that is running.
 struct XQArgs { uint32_t *ctl; uint32_t *state; uint32_t ngroups, nseg, seg_rows, spin_cap, rmask; };          // ctl[0]: next ticket, ctl[1]: some wave gave up waiting, ctl[16 + g]: segments of group g done
-// ABS: the absolute-score form of the row body (x_forward_abs; q.rmask = its rebase period - 1)
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false>
+// ABS: the absolute-score form of the row body (x_forward_abs; q.rmask = its rebase period - 1), M3: with its three-operand maxima in the biased frame
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false, bool M3 = ABS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) k_align8_fwd_xq(const Align8Args a, const XQArgs q){
 	// one item per wave (a block is a wave: the dispatcher refills a wave slot the moment it is free); the ticket, not the block
 	// index, names the item, so that an item's predecessor is always one that has started
@@ -1489,7 +1534,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) 
 	}
 	if constexpr (ABS){
 		static_assert(W == 16 && PW <= 1 && !SCORE, "absolute-score form");
-		x_forward_abs<L, 1, PW, DO2>(a, a.first, a.count, g * 64u, q.rmask, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
+		x_forward_abs<L, 1, PW, DO2, false, M3>(a, a.first, a.count, g * 64u, q.rmask, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
 	} else
 	x_forward<W, L, PW, false, 1, DO2, false, SCORE>(a, a.first, a.count, g * 64u, s * q.seg_rows, (s + 1u) * q.seg_rows, q.state + (size_t)g * (XS_WORDS(W, PW) * 64u));
 	if(s + 1u < q.nseg){
@@ -1513,14 +1558,14 @@ size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count){
 	const size_t groups = ((size_t)count * L + 63u) / 64u;
 	return (16u + groups) * 4u + 256u + groups * (size_t)(XS_WORDS(Wl, pw) * 64u * 4u);
 }
-// name of a launch in the absolute-score form: the family's description and the rebase period that bsa_align8_abs_rows chose (tests read it)
-static const char *x_abs_name(const char *what, uint32_t rebase_rows){
-	static thread_local char buf[256];
-	snprintf(buf, sizeof buf, "%s [rebase every %u rows]", what, rebase_rows);
+// name of a launch in the absolute-score form: the family's description, the rebase period and the form of the maxima that bsa_align8_abs_rows chose (tests read it)
+static const char *x_abs_name(const char *what, uint32_t rebase_rows, bool m3){
+	static thread_local char buf[320];
+	snprintf(buf, sizeof buf, "%s [rebase every %u rows] [%s]", what, rebase_rows, m3 ? "three-operand maxima, biased frame" : "integer maxima");
 	return buf;
 }
 // true when the launch was made
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false>
+template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false, bool M3 = ABS>
 static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err, uint32_t rebase_rows = 0u){
 	const char *qe = bsa_env("BSA_ALIGN8_XQ");
 	if(!a.xq || (qe && qe[0] == '0')) return false;
@@ -1542,10 +1587,10 @@ static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err, ui
 	if(const char *sc = bsa_env("BSA_ALIGN8_XQ_SPIN_CAP")){ const long v = atol(sc); if(v >= 1) q.spin_cap = (uint32_t)v; }          // (test hook: a cap of a few turns makes hand-over waits give up)
 	err = hipMemsetAsync(a.xq, 0, ctl_bytes, st);
 	if(err != hipSuccess) return true;
-	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE, ABS>), dim3(groups * nseg), dim3(64), 0, st, a, q);
+	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE, ABS, M3>), dim3(groups * nseg), dim3(64), 0, st, a, q);
 	err = hipGetLastError();
 	bsa_last_fwd_kernel = SCORE ? "k_align8_fwd_xq score-only (exact-arithmetic forward DP in row segments, no traceback codes)"
-		: ABS ? x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, 4-bit traceback codes)", rebase_rows)
+		: ABS ? x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, 4-bit traceback codes)", rebase_rows, M3)
 		: "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
 	return true;
 }
@@ -1585,18 +1630,31 @@ bool bsa_align8_x_supported(const Align8Args &a, int pw){
 //   * what is not a computed cell lies within K = 512 of one: E^ and F^ (within go), mg = m + gapo, the -63 - 2 ge sentinels of F and of the first-cell rule, the virtual column
 //     (+ gape), the entering cells (cfirst - gape - gape >= -100 - 2 ge inside the guard), the pads beyond the query end.  A band that jumps past all it held starts from a row that
 //     is -gape p by construction: the SCORE_MIN of its real scores is carried by the int32 base, not by the int16 row.
-// A rebase makes the row's first slot 0; R rows later every value lies within s (bw + R) + K of it: R is the largest power of two up to 64 with s (bw + R) + K <= 32767, and a scoring
-// that leaves no R >= 8 keeps the difference form.  (The benchmark's scoring: s = 9, 9 (128 + 64) + 512 = 2240.)
+// A rebase puts the row's first slot at the frame's origin; R rows later every value lies within D(R) = s (bw + R) + K of it.
+//   * Three-operand maxima (x_forward_abs, M3; *m3 = true): the origin is B = 0x4000 and every operand of a maximum must be an int16 whose pattern an f16 maximum orders as an
+//     integer one does, 0x0400 .. 0x7BFF.  That is [B - 15360, B + 15359]: D(R) <= 15359, the smaller side.  K = 512 already covers what enters those maxima beside cells:
+//     E^, F^, the sentinels and fini - gapo (within 63 + 2 ge + go of a cell), the entering cells, the pads.
+//   * Integer maxima (*m3 = false): the origin is 0 and an int16 holds D(R) <= 32767.
+// R is the largest power of two up to 64 that meets the first bound; a scoring that leaves no R >= 8 there takes the largest that meets the second, and one that leaves none
+// there either keeps the difference form.  (The benchmark's scoring: s = 9, 9 (128 + 64) + 512 = 2240.)  The guard gives s <= m + 3 g + 2 ge <= 100, and at bandwidth 128
+// s (128 + 8) + 512 <= 15359 holds up to s = 109: the integer maxima are only ever chosen at bandwidth 256 (s >= 57), and the launchers build them for that width alone.
+// A shorter period with three-operand maxima is still the cheaper row: a rebase is 37 instructions every R rows, the maxima save 30 a row.
 // BSA_ALIGN8_ABS=0 keeps the difference form.  BSA_ALIGN8_ABS_R=<rows> (test hook) shortens the period: the largest power of two that is at most <rows>, at least 8 and at most
 // the derived R; anything that is not a number of at least 8 gives 8.
-uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw){
+uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw, bool *m3){
+	if(m3) *m3 = false;
 	const char *e = bsa_env("BSA_ALIGN8_ABS");
 	if((e && e[0] == '0') || pw > 1 || !(a.bw == 128u || a.bw == 256u) || !bsa_align8_x_supported(a, pw)) return 0u;
 	const int go = -(int)(int8_t)a.gapo1, ge = -(int)(int8_t)a.gape1, m = a.smax;
 	const int s = std::max(go, m + go + 2 * ge);
 	uint32_t r = 64u;
-	while(r >= 8u && s * (int)(a.bw + r) + 512 > 32767) r >>= 1;
-	if(r < 8u) return 0u;
+	while(r >= 8u && s * (int)(a.bw + r) + 512 > 15359) r >>= 1;
+	if(r >= 8u){ if(m3) *m3 = true; }
+	else {
+		r = 64u;
+		while(r >= 8u && s * (int)(a.bw + r) + 512 > 32767) r >>= 1;
+		if(r < 8u || a.bw != 256u) return 0u;
+	}
 	if(const char *re = bsa_env("BSA_ALIGN8_ABS_R")){
 		const long want = std::max(atol(re), 8L);
 		uint32_t f = 8u;
@@ -1626,11 +1684,11 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 			hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, true>), dim3(b4), dim3(256), 0, st, a);
 			bsa_last_fwd_kernel = "k_align8_fwd_x_static (exact-arithmetic forward DP, band in place, traceback codes with two-bit D/Od fields)";
 		} else if(rr && x_launch_xq<16, 4, 1, true, 3, false, true>(a, st, qe, rr)){
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", rr);
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", rr, true);
 			return qe;
 		} else if(rr){
 			hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, true>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", rr);
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", rr, true);
 		} else if(x_launch_xq<16, 4, 1, true>(a, st, qe)){
 			bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, traceback codes with two-bit D/Od fields)";
 			return qe;
@@ -1675,13 +1733,16 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 	hipError_t qerr = hipSuccess;
 	if(pw == 0){
 		if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 0>(a, st, qerr)) return qerr;
-		if(const uint32_t rr = bsa_align8_abs_rows(a, pw)){
-			// absolute-score form (bandwidth 128, 256): row segments, else whole pairs
+		bool m3 = false;
+		if(const uint32_t rr = bsa_align8_abs_rows(a, pw, &m3)){
+			// absolute-score form (bandwidth 128, 256): row segments, else whole pairs; integer maxima at bandwidth 256 alone
 			if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
-			if(a.bw == 256u && x_launch_xq<16, 8, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
+			if(a.bw == 256u && m3 && x_launch_xq<16, 8, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
+			if(a.bw == 256u && !m3 && x_launch_xq<16, 8, 0, false, 3, false, true, false>(a, st, qerr, rr)) return qerr;
 			if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 0, false>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
-			else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr);
+			else if(m3) hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
+			else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
+			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr, m3);
 			return hipGetLastError();
 		}
 		if(a.bw == 128u && x_launch_xq<16, 4, 0>(a, st, qerr)) return qerr;
@@ -1698,12 +1759,14 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 		return hipGetLastError();
 	}
 	if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 1>(a, st, qerr)) return qerr;
-	const uint32_t rr1 = bsa_align8_abs_rows(a, pw);          // rebase period of the absolute-score form, 0: the difference form
+	bool m31 = false;
+	const uint32_t rr1 = bsa_align8_abs_rows(a, pw, &m31);          // rebase period of the absolute-score form, 0: the difference form; m31: its three-operand maxima (bandwidth 128: always)
 	if(rr1 && a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1, false, 3, false, true>(a, st, qerr, rr1)) return qerr;
 	if(rr1 && a.bw == 256u){
-		if(x_launch_xq<16, 8, 1, false, 3, false, true>(a, st, qerr, rr1)) return qerr;
-		hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
-		bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1);
+		if(m31 ? x_launch_xq<16, 8, 1, false, 3, false, true>(a, st, qerr, rr1) : x_launch_xq<16, 8, 1, false, 3, false, true, false>(a, st, qerr, rr1)) return qerr;
+		if(m31) hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
+		else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
+		bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1, m31);
 		return hipGetLastError();
 	}
 	if(a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1>(a, st, qerr)) return qerr;
@@ -1728,14 +1791,14 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
 			// (the four-lane shape runs the absolute-score form where it applies; the eight-lane one, eight cells a half, has none)
 			if(n4 == a.count && rr1){
 				hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, false>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a, rr1 - 1u);
-				bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1);
+				bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1, true);
 			} else if(n4 == a.count) hipLaunchKernelGGL((k_align8_fwd_x<16, 4>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a);
 			else if(n4 == 0) hipLaunchKernelGGL((k_align8_fwd_x<8, 8>), dim3(b8), dim3(256), 0, st, a);
 			else {
 				const uint32_t n8 = a.count - n4, nb8 = (n8 + 31u) / 32u;
 				if(rr1){
 					hipLaunchKernelGGL((k_align8_fwd_x_mix<true>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, rr1 - 1u);
-					bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x_mix (exact-arithmetic forward DP, absolute scores in the four-lane blocks, 4-bit traceback codes)", rr1);
+					bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x_mix (exact-arithmetic forward DP, absolute scores in the four-lane blocks, 4-bit traceback codes)", rr1, true);
 				} else hipLaunchKernelGGL((k_align8_fwd_x_mix<false>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, 0u);
 			}
 			break;

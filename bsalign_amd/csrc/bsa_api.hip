@@ -945,6 +945,26 @@ static uint32_t align8_widened_bw(const bsa_align_params_t *par, uint32_t cols){
 	return (bsa_align8_codes_supported(t, pwa) && bsa_align8_x_supported(t, pwa)) ? kbw : 0u;
 }
 
+// What bsa_align8_abs_rows decides for a scoring at par->bandwidth (128 or 256), for tests of its bound; needs no device.  Returns -1 when the exact-arithmetic
+// forward kernel does not take the scoring (bsa_align8_x_supported, or two-piece gaps), 0 for the difference form, 1 for the absolute-score form with integer maxima,
+// 2 with three-operand maxima in the biased frame; *rows = the rebase period.
+extern "C" int bsa_align8_abs_form_internal(const bsa_align_params_t *par, uint32_t *rows){
+	if(!par) return -1;
+	if(rows) *rows = 0u;
+	const int pw = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, (int)par->bandwidth);
+	Align8Args t;
+	memset(&t, 0, sizeof(t));
+	t.bw = par->bandwidth; t.mode = par->mode & 3; t.gapo1 = par->gapo1; t.gape1 = par->gape1; t.gapo2 = par->gapo2; t.gape2 = par->gape2;
+	int smax = -127, smin = 127;
+	for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); }
+	t.smax = smax; t.smin = smin;
+	if(pw > 1 || !bsa_align8_x_supported(t, pw)) return -1;
+	bool m3 = false;
+	const uint32_t r = bsa_align8_abs_rows(t, pw, &m3);
+	if(rows) *rows = r;
+	return r == 0u ? 0 : m3 ? 2 : 1;
+}
+
 extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, size_t n, const bsa_align_params_t *par, bsa_align_plan_t **out){
 	if(!c || !out || !par || (n && (!qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;

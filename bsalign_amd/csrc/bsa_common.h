@@ -286,7 +286,7 @@ bool bsa_align8_codes_supported(const Align8Args &a, int pw);          // global
 hipError_t bsa_launch_align8_fwd_codes(const Align8Args &a, int pw, hipStream_t st);
 bool bsa_align8_x_supported(const Align8Args &a, int pw);              // exact-arithmetic forward kernel of the compact path (bsa_align8_x.hip)
 bool bsa_align8_do2_supported(const Align8Args &a, int pw);            // ... able to write code format 1
-uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw);            // ... in the absolute-score form: its rebase period in rows, 0 = the difference form
+uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw, bool *m3 = nullptr);      // ... in the absolute-score form: its rebase period in rows, 0 = the difference form; *m3: three-operand maxima in the biased frame (else integer maxima)
 bool bsa_align8_trace_reads_do2(const Align8Args &a, int pw);          // the traceback kernel the launcher would pick reads code format 1
 hipError_t bsa_launch_diagdp(const uint8_t *d_planes, const bsa_diagdp_prob_t *d_probs, uint32_t *d_T, const uint64_t *d_toff, uint8_t *d_matrix,
 		uint32_t n, uint32_t W, uint32_t max_len, hipStream_t st);

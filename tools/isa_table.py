@@ -2,12 +2,14 @@
 """Per-kernel resource table of two builds of one .hip file, from the compiler's assembly.
 
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S parent/bsa_align8_x.hip -o parent.s      (the same for the candidate)
-    python tools/isa_table.py parent.s candidate.s [-o profiles/x_shared_isa.json]
+    python tools/isa_table.py parent.s candidate.s [-o profiles/x_shared_isa.json] [--rename REGEX REPL ...]
 
-Reads the registers, scratch, LDS and spill count of every kernel from the assembly's metadata and counts each kernel's instruction lines (all, and those
-that begin with v_).  Prints the kernels whose figures differ; exit status 1 when the sets of kernels differ or scratch, LDS, a spill count or the
+Reads the registers, scratch, LDS and spill count of every kernel from the assembly's metadata, counts each kernel's instruction lines (all, and those
+that begin with v_) and hashes its instruction text (labels without the function's number, so that kernels added before it do not change it).  --rename
+rewrites the candidate's mangled kernel names before they are matched (the first pattern that matches a name decides), for a change that adds a template parameter: the kernels keep their rows.  Prints the kernels whose figures differ; exit status 1 when the sets of kernels differ or scratch, LDS, a spill count or the
 occupancy (waves per SIMD that the vector registers allow) of some kernel changed."""
 import argparse
+import hashlib
 import json
 import re
 import subprocess
@@ -24,9 +26,9 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def read_asm(path):
+def read_asm(path, renames=()):
     kernels, cur, body, meta = {}, None, None, False
-    counts = {}
+    counts, text = {}, {}
     for line in open(path):
         if line.startswith("amdhsa.kernels:"):
             meta = True
@@ -43,14 +45,24 @@ def read_asm(path):
             if m and not line.startswith(".L"):
                 body = m.group(1)
                 counts[body] = [0, 0]
+                text[body] = hashlib.sha1()
         elif line.startswith(".Lfunc_end"):
             body = None
         elif line.startswith("\t") and not line.startswith(("\t.", "\t;")):
             counts[body][0] += 1
             counts[body][1] += line.startswith("\tv_")
+            text[body].update(re.sub(r"\.LBB\d+_", ".LBB_", line.replace(body, "@")).encode())
     for name, k in kernels.items():
         k["instructions"], k["v_instructions"] = counts[name]
-    return kernels
+        k["text_sha1"] = text[name].hexdigest()[:16]
+    out = {}
+    for name, k in kernels.items():
+        for pat, repl in renames:          # the first pattern that matches decides
+            if re.search(pat, name):
+                name = re.sub(pat, repl, name)
+                break
+        out[name] = k
+    return out
 
 
 def waves(k):
@@ -64,8 +76,9 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("candidate")
     ap.add_argument("-o", "--out")
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     a = ap.parse_args()
-    par, cand = read_asm(a.parent), read_asm(a.candidate)
+    par, cand = read_asm(a.parent), read_asm(a.candidate, a.rename)
     names = demangle(sorted(set(par) | set(cand)))
     bad = set(par) != set(cand)
     table = {}
@@ -76,7 +89,7 @@ def main():
             print("only in one build:", names[sym])
             continue
         if p != c:
-            print(names[sym] + ": " + ", ".join("%s %d -> %d" % (k, p[k], c[k]) for k in p if p[k] != c[k]))
+            print(names[sym] + ": " + ", ".join("%s %s -> %s" % (k, p[k], c[k]) for k in p if p[k] != c[k]))
         if any(p[k] != c[k] for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count")) or waves(p) != waves(c):
             print("  ^ scratch, LDS, spills or occupancy changed")
             bad = True
