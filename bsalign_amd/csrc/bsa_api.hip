@@ -20,6 +20,17 @@
 #include <cstring>
 #include <cstdlib>
 
+// (start, stop) event pairs around the launches of one kind in the last run; the events are created once and kept
+struct EventList {
+	std::vector<hipEvent_t> ev;
+	size_t used = 0;
+	int grow(bsa_ctx *c, size_t count);                         // at least `count` events
+	int pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b);         // the next pair
+	int sum_ms(bsa_ctx *c, double *ms, long *launches);         // over the pairs in use; the caller has synchronised
+	int mean_ms(bsa_ctx *c, double *ms, long *launches);
+	void destroy(){ for(hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
+
 struct bsa_ctx {
 	int device = 0;
 	hipStream_t own_stream = nullptr;
@@ -31,19 +42,15 @@ struct bsa_ctx {
 	uint8_t *ws = nullptr; size_t ws_bytes = 0;
 	std::string err;
 	// timing of the dominant kernel in the last run
-	std::vector<hipEvent_t> ev;      // pairs (start, stop)
-	size_t ev_used = 0;
+	EventList ev;                    // the forward launches
 	double last_cells = 0;
-	std::vector<hipEvent_t> tev;     // the same for the traceback launches (on the stream they run on)
-	size_t tev_used = 0;
-	std::vector<hipEvent_t> mev;     // ... and for the BSA_MODE_BAND_MARGIN pass
-	size_t mev_used = 0;
+	EventList tev;                   // the same for the traceback launches (on the stream they run on)
+	EventList mev;                   // ... and for the BSA_MODE_BAND_MARGIN pass
 	std::string fwd_name, trace_name;    // kernels behind those two timings
 	long last_handover = 0;              // pairs the last bsa_align_batch re-ran through the literal kernels
 	double diagdp_ms = 0;
 	double kmer_chain_ms = 0; long kmer_on_device = 0, kmer_on_host = 0;      // last bsa_kmer_chain_batch / bsa_kmer_edit_batch2 (bsa_ctx_last_kmer_chain_ms)
-	std::vector<hipEvent_t> kev;     // ... or, after bsa_kmer_chain_run (asynchronous), a (start, stop) pair a workspace chunk, read when the time is asked for
-	size_t kev_used = 0;
+	EventList kev;                   // ... or, after bsa_kmer_chain_run (asynchronous), a (start, stop) pair a workspace chunk, read when the time is asked for
 	// small device buffers kept between calls (slot 0: a plan's metadata pool, slot 1: the host-pointer wrapper's buffers): a batch
 	// of one pair otherwise spends more time in hipMalloc / hipFree than in its kernels
 	size_t budget_last = 0;          // last answer of ctx_ws_budget
@@ -143,11 +150,8 @@ extern "C" void bsa_ctx_destroy(bsa_ctx_t *c){
 	(void)hipSetDevice(c->device);
 	(void)hipStreamSynchronize(c->stream);
 	(void)hipStreamSynchronize(c->aux_stream);
-	for(hipEvent_t e : c->ev) (void)hipEventDestroy(e);
+	for(EventList *l : {&c->ev, &c->tev, &c->mev, &c->kev}) l->destroy();
 	for(hipEvent_t e : c->sev) (void)hipEventDestroy(e);
-	for(hipEvent_t e : c->tev) (void)hipEventDestroy(e);
-	for(hipEvent_t e : c->mev) (void)hipEventDestroy(e);
-	for(hipEvent_t e : c->kev) (void)hipEventDestroy(e);
 	if(c->ws) (void)hipFree(c->ws);
 	for(int k = 0; k < 2; k++) if(c->keep[k]) (void)hipFree(c->keep[k]);
 	for(int k = 0; k < 3; k++) if(c->scratch[k]) (void)hipFree(c->scratch[k]);
@@ -162,88 +166,65 @@ extern "C" int bsa_ctx_set_workspace_limit(bsa_ctx_t *c, size_t b){ if(!c) retur
 extern "C" int bsa_ctx_sync(bsa_ctx_t *c){ if(!c) return BSA_E_ARG; (void)hipSetDevice(c->device); HIPCHK(c, hipStreamSynchronize(c->stream)); return BSA_OK; }
 extern "C" const char *bsa_last_error(bsa_ctx_t *c){ return c ? c->err.c_str() : "no context"; }
 
-extern "C" int bsa_ctx_last_kernel_ms(bsa_ctx_t *c, double *ms, long *launches, double *cells){
-	if(!c) return BSA_E_ARG;
-	(void)hipSetDevice(c->device);
-	HIPCHK(c, hipStreamSynchronize(c->stream));
+int EventList::grow(bsa_ctx *c, size_t count){
+	while(ev.size() < count){
+		hipEvent_t e;
+		HIPCHK(c, hipEventCreate(&e));
+		ev.push_back(e);
+	}
+	return BSA_OK;
+}
+int EventList::pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
+	const int rc = grow(c, used + 2);
+	if(rc != BSA_OK) return rc;
+	*a = ev[used]; *b = ev[used + 1];
+	used += 2;
+	return BSA_OK;
+}
+int EventList::sum_ms(bsa_ctx *c, double *ms, long *launches){
 	double tot = 0; long n = 0;
-	for(size_t i = 0; i + 1 < c->ev_used; i += 2){
+	for(size_t i = 0; i + 1 < used; i += 2){
 		float t = 0;
-		HIPCHK(c, hipEventElapsedTime(&t, c->ev[i], c->ev[i + 1]));
+		HIPCHK(c, hipEventElapsedTime(&t, ev[i], ev[i + 1]));
 		tot += t; n++;
 	}
+	*ms = tot; *launches = n;
+	return BSA_OK;
+}
+int EventList::mean_ms(bsa_ctx *c, double *ms, long *launches){
+	double tot = 0; long n = 0;
+	const int rc = sum_ms(c, &tot, &n);
+	if(rc != BSA_OK) return rc;
 	if(ms) *ms = n ? tot / (double)n : 0.0;
 	if(launches) *launches = n;
-	if(cells) *cells = c->last_cells;
 	return BSA_OK;
 }
 
-extern "C" int bsa_ctx_last_trace_ms(bsa_ctx_t *c, double *ms, long *launches){
+// the timing getters wait for the work they report on: the forward launches are on the context's stream, the traceback and margin ones may be on the auxiliary one
+static int ctx_sync_for_timing(bsa_ctx *c, bool aux){
 	if(!c) return BSA_E_ARG;
 	(void)hipSetDevice(c->device);
 	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
-	double tot = 0; long n = 0;
-	for(size_t i = 0; i + 1 < c->tev_used; i += 2){
-		float t = 0;
-		HIPCHK(c, hipEventElapsedTime(&t, c->tev[i], c->tev[i + 1]));
-		tot += t; n++;
-	}
-	if(ms) *ms = n ? tot / (double)n : 0.0;
-	if(launches) *launches = n;
+	if(aux) HIPCHK(c, hipStreamSynchronize(c->aux_stream));
 	return BSA_OK;
 }
+extern "C" int bsa_ctx_last_kernel_ms(bsa_ctx_t *c, double *ms, long *launches, double *cells){
+	int rc = ctx_sync_for_timing(c, false);
+	if(rc == BSA_OK) rc = c->ev.mean_ms(c, ms, launches);
+	if(rc == BSA_OK && cells) *cells = c->last_cells;
+	return rc;
+}
+extern "C" int bsa_ctx_last_trace_ms(bsa_ctx_t *c, double *ms, long *launches){
+	const int rc = ctx_sync_for_timing(c, true);
+	return rc != BSA_OK ? rc : c->tev.mean_ms(c, ms, launches);
+}
 extern "C" int bsa_ctx_last_margin_ms(bsa_ctx_t *c, double *ms, long *launches){
-	if(!c) return BSA_E_ARG;
-	(void)hipSetDevice(c->device);
-	HIPCHK(c, hipStreamSynchronize(c->stream));
-	HIPCHK(c, hipStreamSynchronize(c->aux_stream));
-	double tot = 0; long n = 0;
-	for(size_t i = 0; i + 1 < c->mev_used; i += 2){
-		float t = 0;
-		HIPCHK(c, hipEventElapsedTime(&t, c->mev[i], c->mev[i + 1]));
-		tot += t; n++;
-	}
-	if(ms) *ms = n ? tot / (double)n : 0.0;
-	if(launches) *launches = n;
-	return BSA_OK;
+	const int rc = ctx_sync_for_timing(c, true);
+	return rc != BSA_OK ? rc : c->mev.mean_ms(c, ms, launches);
 }
 thread_local const char *bsa_last_fwd_kernel = nullptr, *bsa_last_trace_kernel = nullptr;
 extern "C" long bsa_ctx_last_handover(bsa_ctx_t *c){ return c ? c->last_handover : 0; }
 extern "C" const char *bsa_ctx_last_kernel_name(bsa_ctx_t *c, int traceback){ return !c ? "" : traceback ? c->trace_name.c_str() : c->fwd_name.c_str(); }
-
-static int ctx_trace_event_pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
-	while(c->tev.size() < c->tev_used + 2){
-		hipEvent_t e;
-		HIPCHK(c, hipEventCreate(&e));
-		c->tev.push_back(e);
-	}
-	*a = c->tev[c->tev_used]; *b = c->tev[c->tev_used + 1];
-	c->tev_used += 2;
-	return BSA_OK;
-}
-
-static int ctx_margin_event_pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
-	while(c->mev.size() < c->mev_used + 2){
-		hipEvent_t e;
-		HIPCHK(c, hipEventCreate(&e));
-		c->mev.push_back(e);
-	}
-	*a = c->mev[c->mev_used]; *b = c->mev[c->mev_used + 1];
-	c->mev_used += 2;
-	return BSA_OK;
-}
-
-static int ctx_event_pair(bsa_ctx *c, hipEvent_t *a, hipEvent_t *b){
-	while(c->ev.size() < c->ev_used + 2){
-		hipEvent_t e;
-		HIPCHK(c, hipEventCreate(&e));
-		c->ev.push_back(e);
-	}
-	*a = c->ev[c->ev_used]; *b = c->ev[c->ev_used + 1];
-	c->ev_used += 2;
-	return BSA_OK;
-}
 
 static int ctx_sync_event(bsa_ctx *c, hipEvent_t *e){
 	if(c->sev.size() <= c->sev_used){
@@ -752,20 +733,20 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 		uint8_t *half = c->ws + (k % p->nbuf) * p->half_bytes;
 		if(p->two_halves && k >= p->nbuf) HIPCHK(c, hipStreamWaitEvent(sf, trace_done[k - p->nbuf], 0));
 		hipEvent_t e0, e1;
-		rc = ctx_event_pair(c, &e0, &e1); if(rc != BSA_OK) return rc;
+		rc = c->ev.pair(c, &e0, &e1); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(e0, sf));
 		rc = fwd(ch, half, sf); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(e1, sf));
 		if(p->two_halves) HIPCHK(c, hipStreamWaitEvent(stt, e1, 0));
 		hipEvent_t t0, t1;
-		rc = ctx_trace_event_pair(c, &t0, &t1); if(rc != BSA_OK) return rc;
+		rc = c->tev.pair(c, &t0, &t1); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(t0, stt));
 		rc = trace(ch, half, stt); if(rc != BSA_OK) return rc;
 		HIPCHK(c, hipEventRecord(t1, stt));
 		if(p->margin){
 			// BSA_MODE_BAND_MARGIN: behind the chunk's walkers on their stream, in front of everything that replaces the plain word counts or reuses the slots
 			hipEvent_t m0, m1;
-			rc = ctx_margin_event_pair(c, &m0, &m1); if(rc != BSA_OK) return rc;
+			rc = c->mev.pair(c, &m0, &m1); if(rc != BSA_OK) return rc;
 			HIPCHK(c, hipEventRecord(m0, stt));
 			HIPCHK(c, bsa_launch_band_margin(half, p->d_slot, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_order, p->d_qlen, p->d_tlen, p->eqx_out,
 				p->margin_bandwidth, p->margin_status, stt));
@@ -806,7 +787,7 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 static int run_prologue(PlanBase *p, bool want_cig, size_t cigar_cap_words){
 	bsa_ctx *c = p->ctx;
 	(void)hipSetDevice(c->device);
-	c->ev_used = 0; c->tev_used = 0; c->mev_used = 0; c->last_cells = 0;
+	c->ev.used = 0; c->tev.used = 0; c->mev.used = 0; c->last_cells = 0;
 	int rc = ctx_ws_reserve(c, p->half_bytes * p->nbuf);
 	if(rc != BSA_OK) return rc;
 	const bool direct = p->chunks.size() == 1 && !p->two_halves && !bsa_env("BSA_CIGAR_VIA_ARENA");          // (run_pipeline: no pass through the arena)
@@ -892,8 +873,22 @@ static int batch_host(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes, size_t
 // ------------------------------------------------------------------------------------------------
 // 8-bit alignment plan (banded_striped_epi8_seqalign_pairwise, bsalign.h:3854)
 // ------------------------------------------------------------------------------------------------
+// What bsa_align_run launches.  A plan runs the kernels that the knobs chose when it was made: the path, the code format and the slot sizes are
+// decided together in bsa_align_plan_create (align8_choose_path), and bsa_align_run reads no path knob of its own.
+enum Align8Path {
+	A8_SCORE,           // BSA_MODE_SCORE_ONLY on the SCORE kernels: a record a pair, no traceback codes
+	A8_SYS,             // whole-query bands above 256 columns: the systolic wavefront and its own traceback
+	A8_CODES_X,         // compact codes, the exact-arithmetic forward kernel
+	A8_CODES_PK,        // compact codes, the packed forward kernel
+	A8_GENERIC,         // run-time width, row records
+	A8_ROWS,            // register kernels, row records
+};
 struct bsa_align_plan : PlanBase {
 	bsa_align_params_t par;
+	Align8Path path = A8_ROWS;
+	uint32_t code_fmt = 0;                       // Align8Args::code_fmt of the compact slots
+	bool reads_codes() const { return codes || sys; }       // the traceback is read off codes: a pair may be left undecided and handed over to the literal kernels
+	bool fwd_x() const { return path == A8_SCORE || path == A8_CODES_X; }
 	uint32_t bw = 0, rowb = 0; int pw = 0;       // bw == 0: per-pair bandwidth = roundup(qlen, 16)
 	bool generic = false;                        // run the LDS-resident generic kernels
 	bool codes = false;                          // compact 4-bit-code traceback (global mode, bsa_align8_pk.hip CODES)
@@ -923,6 +918,23 @@ static void score_only_trim(bsa_result_t &r){ r.qb = r.tb = -1; r.mat = r.mis = 
 extern "C" void bsa_align_plan_destroy(bsa_align_plan_t *p){ plan_free(p); }
 extern "C" double bsa_align_plan_cells(const bsa_align_plan_t *p){ return p ? p->cells : 0.0; }
 
+// The scoring part of the kernels' arguments (everything else zero) for a width and a mode: what the bsa_align8_*_supported questions are asked of
+// and what bsa_align_run starts from.
+static Align8Args align8_scoring_args(const bsa_align_params_t *par, uint32_t bw, int mode){
+	Align8Args a;
+	memset(&a, 0, sizeof(a));
+	a.bw = bw; a.mode = mode; a.gapo1 = par->gapo1; a.gape1 = par->gape1; a.gapo2 = par->gapo2; a.gape2 = par->gape2;
+	int smax = -127, smin = 127;
+	for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); a.matrix[i] = par->matrix[i]; }
+	a.smax = smax; a.smin = smin;
+	for(int t = 0; t < 4; t++){
+		uint32_t w = 0;
+		for(int q = 0; q < 4; q++) w |= (uint32_t)(uint8_t)par->matrix[q * 4 + t] << (8 * q);
+		a.mrow[t] = w;
+	}
+	return a;
+}
+
 // Can a whole-query band of `cols` columns (a multiple of 16, at most 256) run at a register-kernel width on the compact path?
 // Returns that width, or 0.  (See bsa_align_plan_create.)
 static uint32_t align8_widened_bw(const bsa_align_params_t *par, uint32_t cols){
@@ -936,12 +948,7 @@ static uint32_t align8_widened_bw(const bsa_align_params_t *par, uint32_t cols){
 	if(pwa != pwb) return 0u;
 	// (two-piece gaps: the compact path exists at bandwidth 128 in global mode only -- the checks below say so)
 	const uint32_t kbw = (cols <= 64u && pwa <= 1) ? 64u : cols <= 128u ? 128u : 256u;
-	Align8Args t;
-	memset(&t, 0, sizeof(t));
-	t.bw = kbw; t.mode = type; t.gapo1 = par->gapo1; t.gape1 = par->gape1; t.gapo2 = par->gapo2; t.gape2 = par->gape2;
-	int smax = -127, smin = 127;
-	for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); }
-	t.smax = smax; t.smin = smin;
+	const Align8Args t = align8_scoring_args(par, kbw, type);
 	return (bsa_align8_codes_supported(t, pwa) && bsa_align8_x_supported(t, pwa)) ? kbw : 0u;
 }
 
@@ -952,17 +959,25 @@ extern "C" int bsa_align8_abs_form_internal(const bsa_align_params_t *par, uint3
 	if(!par) return -1;
 	if(rows) *rows = 0u;
 	const int pw = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, (int)par->bandwidth);
-	Align8Args t;
-	memset(&t, 0, sizeof(t));
-	t.bw = par->bandwidth; t.mode = par->mode & 3; t.gapo1 = par->gapo1; t.gape1 = par->gape1; t.gapo2 = par->gapo2; t.gape2 = par->gape2;
-	int smax = -127, smin = 127;
-	for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); }
-	t.smax = smax; t.smin = smin;
+	const Align8Args t = align8_scoring_args(par, par->bandwidth, par->mode & 3);
 	if(pw > 1 || !bsa_align8_x_supported(t, pw)) return -1;
 	bool m3 = false;
 	const uint32_t r = bsa_align8_abs_rows(t, pw, &m3);
 	if(rows) *rows = r;
 	return r == 0u ? 0 : m3 ? 2 : 1;
+}
+
+// The one place that decides what bsa_align_run launches for a plan whose codes / sys / generic flags stand; t: the plan's scoring at its width and mode.
+static void align8_choose_path(bsa_align_plan *p, const Align8Args &t){
+	const char *fe = bsa_env("BSA_ALIGN8_FWD");
+	const bool force_pk = fe && fe[0] == 'p';        // keeps the saturating packed kernel: same code rows, the reference point of the tests
+	const bool x_ok = bsa_align8_x_supported(t, p->pw);
+	// score only: the SCORE forms of the exact-arithmetic forward kernels where the full forms would run with one-piece gaps; otherwise the full path, its results trimmed
+	p->score_only = (p->par.mode & BSA_MODE_SCORE_ONLY) != 0;
+	p->score_fast = p->score_only && p->codes && p->pw <= 1 && !force_pk && x_ok;
+	// (two-piece gaps: the exact-arithmetic kernel is the only forward kernel of the compact path)
+	p->path = p->score_fast ? A8_SCORE : p->sys ? A8_SYS : p->codes ? ((p->pw == 2 || (!force_pk && x_ok)) ? A8_CODES_X : A8_CODES_PK) : p->generic ? A8_GENERIC : A8_ROWS;
+	p->code_fmt = (p->path == A8_CODES_X && bsa_align8_do2_supported(t, p->pw) && bsa_align8_trace_reads_do2(t, p->pw)) ? 1u : 0u;      // two-bit D / Od fields (bsa_common.h)
 }
 
 extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const uint32_t *qlen,
@@ -982,6 +997,8 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	if(type != BSA_MODE_GLOBAL && type != BSA_MODE_OVERLAP && type != BSA_MODE_EXTEND){ c->err = "bad mode"; return BSA_E_ARG; }
 	if((par->mode & BSA_MODE_SCORE_ONLY) && (par->mode & BSA_MODE_ROWRECORDS)){ c->err = "BSA_MODE_SCORE_ONLY and BSA_MODE_ROWRECORDS exclude each other"; return BSA_E_ARG; }
 	(void)hipSetDevice(c->device);
+	const char *le = bsa_env("BSA_ALIGN8_LITERAL");
+	const bool literal = le && le[0] == '1';                      // keeps every batch on the row-record kernels
 	const uint32_t bw_req = (par->bandwidth + 15u) / 16u * 16u;   // bsalign.h:3862; 0 = per pair roundup(qlen, 16) (bsalign.h:3861)
 	uint32_t bw = bw_req;
 	uint32_t max_bw = bw;
@@ -1010,14 +1027,9 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	if(!widened && n > 0 && (bw == 0 || !bsa_align8_supported_bw(bw)) && max_bw > sys_from && max_qlen <= 60000u && !(par->mode & BSA_MODE_ROWRECORDS)){
 		bool full = true;
 		if(bw != 0) for(size_t k = 0; k < n && full; k++) full = qlen[k] <= bw;
-		const char *se = bsa_env("BSA_ALIGN8_SYS"), *le = bsa_env("BSA_ALIGN8_LITERAL");
-		if(full && !(se && se[0] == '0') && !(le && le[0] == '1')){
-			Align8Args t;
-			memset(&t, 0, sizeof(t));
-			t.mode = type; t.gapo1 = par->gapo1; t.gape1 = par->gape1; t.gapo2 = par->gapo2; t.gape2 = par->gape2;
-			int smax = -127, smin = 127;
-			for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); }
-			t.smax = smax; t.smin = smin;
+		const char *se = bsa_env("BSA_ALIGN8_SYS");
+		if(full && !(se && se[0] == '0') && !literal){
+			const Align8Args t = align8_scoring_args(par, 0u, type);
 			const int pwa = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, 16), pwb = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, (int)max_bw);
 			const int lvl = pwa == pwb ? bsa_align8_sys_supported(t, pwb) : 0;
 			const char *ce = bsa_env("BSA_ALIGN8_SYS_CHK");                 // =0: scores outside the static guard keep the run-time-width kernel; =1: the checked kernel inside the guard as well (tests)
@@ -1027,7 +1039,7 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 				// the kernel carries scores times 32 in 32-bit registers: |H| <= (qlen + tlen) x the largest step
 				uint32_t max_tlen = 0;
 				for(size_t k = 0; k < n; k++) max_tlen = std::max(max_tlen, tlen[k]);
-				const long long step = std::max(std::max(-(long long)par->gapo1 - par->gape1, -(long long)par->gapo2 - par->gape2), std::max((long long)smax, -(long long)smin));
+				const long long step = std::max(std::max(-(long long)par->gapo1 - par->gape1, -(long long)par->gapo2 - par->gape2), std::max((long long)t.smax, -(long long)t.smin));
 				if(((long long)max_qlen + max_tlen) * std::max(step, 1ll) >= (1ll << 25)) sys = false;
 			}
 		}
@@ -1053,20 +1065,11 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 	p->qpad = max_bw + BSA_QPAD_TAIL;          // (the forward kernels' query window reads up to 48 bytes behind the band's last block: bsa_align8_x.hip, x_qwin)
 	{
 		// compact traceback where its preconditions hold (BSA_ALIGN8_LITERAL=1 keeps the row-record path)
-		const char *le = bsa_env("BSA_ALIGN8_LITERAL");
-		Align8Args t;
-		memset(&t, 0, sizeof(t));
-		t.bw = bw; t.mode = par->mode; t.gapo1 = par->gapo1; t.gape1 = par->gape1; t.gapo2 = par->gapo2; t.gape2 = par->gape2;
-		int smax = -127, smin = 127;
-		for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)par->matrix[i]); smin = std::min(smin, (int)par->matrix[i]); }
-		t.smax = smax; t.smin = smin;
-		p->codes = !p->sys && !p->generic && !(le && le[0] == '1') && !(par->mode & BSA_MODE_ROWRECORDS) && bsa_align8_codes_supported(t, p->pw);
+		const Align8Args t = align8_scoring_args(par, bw, par->mode);
+		p->codes = !p->sys && !p->generic && !literal && !(par->mode & BSA_MODE_ROWRECORDS) && bsa_align8_codes_supported(t, p->pw);
 		// the compact traceback packs band offsets into 26 bits of its ring entries
 		for(size_t k = 0; k < n && p->codes; k++) if(qlen[k] >= (1u << 26)) p->codes = false;
-		// score only: the SCORE forms of the exact-arithmetic forward kernels where bsa_align_run would take their full forms with one-piece gaps
-		const char *fe = bsa_env("BSA_ALIGN8_FWD");
-		p->score_only = (par->mode & BSA_MODE_SCORE_ONLY) != 0;
-		p->score_fast = p->score_only && p->codes && p->pw <= 1 && !(fe && fe[0] == 'p') && bsa_align8_x_supported(t, p->pw);
+		align8_choose_path(p, t);
 	}
 	std::vector<uint32_t> order(n);
 	for(size_t k = 0; k < n; k++) order[k] = (uint32_t)k;
@@ -1083,9 +1086,15 @@ extern "C" int bsa_align_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const u
 		tpoff[k] = tacc; tacc += ((size_t)tlen[k] + p->tpad + 15) & ~(size_t)15;
 		if(qlen[k] && tlen[k]) cells += (double)tlen[k] * (double)bw_ref(k);
 	}
-	for(size_t pos = 0; pos < n; pos++)
-		need[pos] = p->score_fast ? bsa_score_rec_bytes(bw, type) : p->sys ? bsa_align8_sys_slot_bytes(qlen[order[pos]], tlen[order[pos]], p->pw)
-			: p->codes ? bsa_code_slot_bytes(tlen[order[pos]], bw / 16u, p->pw) : bsa_slot_bytes(tlen[order[pos]], bw_of(order[pos]) / 16u, p->pw);
+	for(size_t pos = 0; pos < n; pos++){
+		const uint32_t k = order[pos];
+		switch(p->path){
+			case A8_SCORE: need[pos] = bsa_score_rec_bytes(bw, type); break;
+			case A8_SYS: need[pos] = bsa_align8_sys_slot_bytes(qlen[k], tlen[k], p->pw); break;
+			case A8_CODES_X: case A8_CODES_PK: need[pos] = bsa_code_slot_bytes(tlen[k], bw / 16u, p->pw); break;
+			case A8_GENERIC: case A8_ROWS: need[pos] = bsa_slot_bytes(tlen[k], bw_of(k) / 16u, p->pw); break;
+		}
+	}
 	p->cells = cells;
 	p->stage_bytes = qacc + tacc;
 	int rc = plan_chunks(p, order, need, bwv, slot, slot_end);
@@ -1133,41 +1142,26 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 #undef BSA_STAGE
 	}
 	HIPCHK(c, hipGetLastError());
-	Align8Args a;
-	memset(&a, 0, sizeof(a));
+	Align8Args a = align8_scoring_args(&p->par, p->bw, p->par.mode);
 	a.qst = p->d_qst; a.tst = p->d_tst; a.qpoff = p->d_qpoff; a.tpoff = p->d_tpoff;
 	a.qlen = p->d_qlen; a.tlen = p->d_tlen; a.order = p->d_order; a.slot_off = p->d_slot;
-	a.status = status; a.bw = p->bw; a.rowb = p->rowb; a.mode = p->par.mode; a.ref_bw = p->ref_bw; a.static_band = p->static_band ? 1u : 0u; a.sys_chk = p->sys_chk ? 1u : 0u;
-	a.gapo1 = p->par.gapo1; a.gape1 = p->par.gape1; a.gapo2 = p->par.gapo2; a.gape2 = p->par.gape2;
-	int smax = -127, smin = 127;
-	for(int i = 0; i < 16; i++){ smax = std::max(smax, (int)p->par.matrix[i]); smin = std::min(smin, (int)p->par.matrix[i]); a.matrix[i] = p->par.matrix[i]; }
-	a.smax = smax; a.smin = smin;
-	for(int t = 0; t < 4; t++){
-		uint32_t w = 0;
-		for(int q = 0; q < 4; q++) w |= (uint32_t)(uint8_t)p->par.matrix[q * 4 + t] << (8 * q);
-		a.mrow[t] = w;
-	}
+	a.status = status; a.rowb = p->rowb; a.ref_bw = p->ref_bw; a.static_band = p->static_band ? 1u : 0u; a.sys_chk = p->sys_chk ? 1u : 0u;
+	a.code_fmt = p->code_fmt;
 	const int pw = p->pw;
 	uint32_t *cnt = p->d_cnt_pos;
-	const bool generic = p->generic, codes = p->codes, sys = p->sys; const uint32_t max_bw = p->max_bw;
-	// forward kernel of the compact path: the exact-arithmetic one wherever its guard holds (BSA_ALIGN8_FWD=pk keeps the
-	// saturating packed kernel: same code rows, the reference point of the tests)
-	bool fwd_x = false;
-	if(codes){
-		const char *fe = bsa_env("BSA_ALIGN8_FWD");
-		const bool force_pk = fe && fe[0] == 'p';
-		fwd_x = (pw == 2) || (!force_pk && bsa_align8_x_supported(a, pw));       // (two-piece gaps: the only forward kernel of the compact path)
+	const Align8Path path = p->path;          // (decided by the plan, whose slots are sized for it)
+	switch(path){
+		case A8_SCORE: c->fwd_name = "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)"; c->trace_name = "k_align8_score_finish"; break;
+		case A8_SYS: c->fwd_name = p->sys_chk ? "k_align8_fwd_sys<CHK> (whole-query band, systolic wavefront checking every pair against the int8 range, 4-bit traceback codes)"
+			: "k_align8_fwd_sys (whole-query band, systolic wavefront, 4-bit traceback codes)"; c->trace_name = "k_align8_trace_sys"; break;
+		case A8_CODES_X: c->fwd_name = pw == 2 ? "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)" : "k_align8_fwd_x (exact-arithmetic forward DP, 4-bit traceback codes)";
+			c->trace_name = ""; break;
+		case A8_CODES_PK: c->fwd_name = "k_align8_fwd_pk<.,.,true> (packed forward DP, 4-bit traceback codes)"; c->trace_name = ""; break;
+		case A8_GENERIC: c->fwd_name = "k_align8_fwd_gen (run-time bandwidth, row records)"; c->trace_name = "k_align8_backcal"; break;
+		case A8_ROWS: c->fwd_name = "k_align8_fwd_pk / k_align8_fwd (row records)"; c->trace_name = "k_align8_backcal"; break;
 	}
-	const bool score_fast = p->score_fast;          // (decided by the plan, whose slots are records of that size)
-	if(score_fast) fwd_x = true;
-	if(codes && fwd_x && !score_fast && bsa_align8_do2_supported(a, pw) && bsa_align8_trace_reads_do2(a, pw)) a.code_fmt = 1u;      // two-bit D / Od fields (bsa_common.h)
-	c->fwd_name = (sys && p->sys_chk) ? "k_align8_fwd_sys<CHK> (whole-query band, systolic wavefront checking every pair against the int8 range, 4-bit traceback codes)" : sys ? "k_align8_fwd_sys (whole-query band, systolic wavefront, 4-bit traceback codes)" : (fwd_x && pw == 2) ? "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)"
-		: fwd_x ? "k_align8_fwd_x (exact-arithmetic forward DP, 4-bit traceback codes)" : codes ? "k_align8_fwd_pk<.,.,true> (packed forward DP, 4-bit traceback codes)"
-		: generic ? "k_align8_fwd_gen (run-time bandwidth, row records)" : "k_align8_fwd_pk / k_align8_fwd (row records)";
-	c->trace_name = sys ? "k_align8_trace_sys" : codes ? "" : "k_align8_backcal";
-	if(score_fast){ c->fwd_name = "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)"; c->trace_name = "k_align8_score_finish"; }
 	bsa_last_trace_kernel = nullptr; bsa_last_fwd_kernel = nullptr;
-	if(codes && fwd_x && !p->static_band){
+	if(p->fwd_x() && !p->static_band){
 		// the persistent form of the forward kernel hands band states from one row segment to the next through this buffer
 		size_t need = 0;
 		for(const Chunk &ch : p->chunks) need = std::max(need, bsa_align8_xq_bytes(p->bw, pw, ch.count));
@@ -1179,26 +1173,30 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	}
 	auto fwd = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		Align8Args b = a; b.first = ch.first; b.count = ch.count; b.rows = half; b.max_tlen = ch.max_tlen;
-		if(score_fast) HIPCHK(c, bsa_launch_align8_fwd_x_score(b, pw, s));
-		else if(sys) HIPCHK(c, bsa_launch_align8_fwd_sys(b, pw, p->max_qlen, s));
-		else if(codes && fwd_x) HIPCHK(c, bsa_launch_align8_fwd_x(b, pw, s));
-		else if(codes) HIPCHK(c, bsa_launch_align8_fwd_codes(b, pw, s));
-		else if(generic) HIPCHK(c, bsa_launch_align8_fwd_gen(b, pw, max_bw, s));
-		else HIPCHK(c, bsa_launch_align8_fwd(b, pw, s));
+		switch(path){
+			case A8_SCORE: HIPCHK(c, bsa_launch_align8_fwd_x_score(b, pw, s)); break;
+			case A8_SYS: HIPCHK(c, bsa_launch_align8_fwd_sys(b, pw, p->max_qlen, s)); break;
+			case A8_CODES_X: HIPCHK(c, bsa_launch_align8_fwd_x(b, pw, s)); break;
+			case A8_CODES_PK: HIPCHK(c, bsa_launch_align8_fwd_codes(b, pw, s)); break;
+			case A8_GENERIC: HIPCHK(c, bsa_launch_align8_fwd_gen(b, pw, p->max_bw, s)); break;
+			case A8_ROWS: HIPCHK(c, bsa_launch_align8_fwd(b, pw, s)); break;
+		}
 		return BSA_OK;
 	};
 	auto trace = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		Align8Args b = a; b.first = ch.first; b.count = ch.count; b.rows = half;
-		if(score_fast) HIPCHK(c, bsa_launch_align8_score_finish(b, d_out, s));
-		else if(sys) HIPCHK(c, bsa_launch_align8_trace_sys(b, pw, d_out, cnt, p->d_slot_end, s));
-		else if(codes) HIPCHK(c, bsa_launch_align8_trace_codes(b, pw, d_out, cnt, s));
-		else HIPCHK(c, bsa_launch_align8_backcal(b, pw, d_out, cnt, s));
+		switch(path){
+			case A8_SCORE: HIPCHK(c, bsa_launch_align8_score_finish(b, d_out, s)); break;
+			case A8_SYS: HIPCHK(c, bsa_launch_align8_trace_sys(b, pw, d_out, cnt, p->d_slot_end, s)); break;
+			case A8_CODES_X: case A8_CODES_PK: HIPCHK(c, bsa_launch_align8_trace_codes(b, pw, d_out, cnt, s)); break;
+			case A8_GENERIC: case A8_ROWS: HIPCHK(c, bsa_launch_align8_backcal(b, pw, d_out, cnt, s)); break;
+		}
 		return BSA_OK;
 	};
 	const int rc8 = run_pipeline(p, want_cig, d_cigar, cigar_cap_words, d_cigar_off, fwd, trace);
-	if(codes && bsa_last_trace_kernel) c->trace_name = bsa_last_trace_kernel;
-	if(codes && fwd_x && bsa_last_fwd_kernel) c->fwd_name = bsa_last_fwd_kernel;
-	if(rc8 == BSA_OK && p->score_only && !score_fast){
+	if(p->codes && bsa_last_trace_kernel) c->trace_name = bsa_last_trace_kernel;
+	if(p->fwd_x() && bsa_last_fwd_kernel) c->fwd_name = bsa_last_fwd_kernel;
+	if(rc8 == BSA_OK && p->score_only && path != A8_SCORE){
 		// the full path ran (a configuration without SCORE kernels): the same result contract
 		hipLaunchKernelGGL(k_score_only_trim, dim3((n + 255u) / 256u), dim3(256), 0, st, d_out, n);
 		HIPCHK(c, hipGetLastError());
@@ -1367,7 +1365,7 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	rc = bsa_align_plan_create(c, qoff, qlen, toff, tlen, nA, par, &pA);
 	t_plan = since();
 	if(rc != BSA_OK){ upl.join(); cleanup(); return rc; }
-	*codes_out = pA->codes || pA->sys;
+	*codes_out = pA->reads_codes();
 	// slice A as soon as its plan stands and its bytes are on their way (a wait on an event that is not recorded yet would be no wait); slice B is
 	// planned while A's kernels run and goes behind them on the same stream: B's kernels wait for B's bytes only
 	if(wait_recorded(1) < 0) rc = BSA_E_HIP;
@@ -1426,6 +1424,26 @@ static int align_batch_sliced(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes
 	return rc;
 }
 
+// A sub-batch of a host-pointer batch (one width class, or the pairs handed over to the literal kernels): the pairs idx[] of the caller's arrays through
+// bsa_align_batch with `par` and an arena of their own that no CIGAR can outgrow; records, status words and -- with want_cig -- words and offsets by position in idx
+struct SubBatch { std::vector<bsa_result_t> out; std::vector<uint32_t> st, cig; std::vector<uint64_t> off; };
+static int align_sub_batch(bsa_ctx *c, const uint8_t *seqs, size_t seqs_bytes, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
+		const std::vector<size_t> &idx, const bsa_align_params_t *par, bool want_cig, SubBatch &r){
+	const size_t m = idx.size();
+	std::vector<uint64_t> sq(m), stt(m);
+	std::vector<uint32_t> sql(m), stl(m);
+	size_t cap = 16;
+	for(size_t j = 0; j < m; j++){ sq[j] = qoff[idx[j]]; stt[j] = toff[idx[j]]; sql[j] = qlen[idx[j]]; stl[j] = tlen[idx[j]]; cap += (size_t)sql[j] + stl[j] + 2; }
+	r.out.resize(m); r.st.assign(m, 0u); r.off.assign(m + 1, 0); r.cig.assign(want_cig ? cap : 0, 0u);
+	return bsa_align_batch(c, seqs, seqs_bytes, sq.data(), sql.data(), stt.data(), stl.data(), m, par, r.out.data(),
+		want_cig ? r.cig.data() : nullptr, cap, want_cig ? r.off.data() : nullptr, r.st.data());
+}
+// a caller that passed no status array cannot see a flag: pairs left undecided are an error for it, never a silent zeroed record
+static int undecided_unseen(bsa_ctx *c, const uint32_t *status, size_t still_flagged){
+	if(status == nullptr && still_flagged){ c->err = "pairs left undecided (BSA_ST_TRACE) and no status array to report them in"; return BSA_E_UNSUPPORTED; }
+	return BSA_OK;
+}
+
 static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen, size_t n,
 		const bsa_align_params_t *par, bsa_result_t *out, uint32_t *cigar, size_t cigar_cap_words,
@@ -1455,6 +1473,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 	if(!seqs || !qoff || !qlen || !toff || !tlen) return BSA_E_ARG;
 	int rc = check_blob(c, par->mode, seqs_bytes, qoff, qlen, toff, tlen, n);          // the staging kernel reads seqs + qoff[k] .. + qlen[k] unconditionally
 	if(rc != BSA_OK) return rc;
+	const bool want_cig = cigar && cigar_off;
 	(void)hipSetDevice(c->device);
 	// Whole-query bands (bandwidth 0, or one the register kernels do not have): a plan runs at ONE width, so a batch whose pairs
 	// fall into different width classes of the widened dispatch (bsa_align_plan_create) -- or some of whose queries are too long
@@ -1477,27 +1496,20 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 				size_t still_flagged = 0; long handed = 0;
 				for(int cl = 0; cl < 4; cl++){
 					if(!cnt[cl]) continue;
-					const size_t m = cnt[cl];
-					std::vector<size_t> idx; idx.reserve(m);
+					std::vector<size_t> idx; idx.reserve(cnt[cl]);
 					for(size_t k = 0; k < n; k++) if(slot_of(klass(k)) == cl) idx.push_back(k);
-					std::vector<uint64_t> sq(m), stt(m), soff(m + 1);
-					std::vector<uint32_t> sql(m), stl(m), sst(m);
-					std::vector<bsa_result_t> sout(m);
-					size_t scap = 16;
-					for(size_t j = 0; j < m; j++){ sq[j] = qoff[idx[j]]; stt[j] = toff[idx[j]]; sql[j] = qlen[idx[j]]; stl[j] = tlen[idx[j]]; scap += (size_t)sql[j] + stl[j] + 2; }
-					std::vector<uint32_t> scig(cigar ? scap : 0);
-					const int rcs = bsa_align_batch(c, seqs, seqs_bytes, sq.data(), sql.data(), stt.data(), stl.data(), m, par, sout.data(),
-						cigar ? scig.data() : nullptr, scap, (cigar && cigar_off) ? soff.data() : nullptr, sst.data());
+					SubBatch r;
+					const int rcs = align_sub_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, idx, par, want_cig, r);
 					if(rcs != BSA_OK) return rcs;
 					handed += c->last_handover;
-					for(size_t j = 0; j < m; j++){
-						out[idx[j]] = sout[j];
-						if(sst[j] & BSA_ST_TRACE) still_flagged++;
-						if(status) status[idx[j]] = sst[j];
-						if(cigar && cigar_off) pc[idx[j]].assign(scig.begin() + soff[j], scig.begin() + soff[j + 1]);
+					for(size_t j = 0; j < idx.size(); j++){
+						out[idx[j]] = r.out[j];
+						if(r.st[j] & BSA_ST_TRACE) still_flagged++;
+						if(status) status[idx[j]] = r.st[j];
+						if(want_cig) pc[idx[j]].assign(r.cig.begin() + r.off[j], r.cig.begin() + r.off[j + 1]);
 					}
 				}
-				if(cigar && cigar_off){
+				if(want_cig){
 					uint64_t w = 0;
 					for(size_t k = 0; k < n; k++){ cigar_off[k] = w; w += pc[k].size(); }
 					cigar_off[n] = w;
@@ -1505,9 +1517,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 					for(size_t k = 0; k < n; k++) if(!pc[k].empty()) memcpy(cigar + cigar_off[k], pc[k].data(), pc[k].size() * 4);
 				}
 				c->last_handover = handed;
-				// the rule of the single-plan path below (finish()): without a status array an undecided pair is an error, never a silent zeroed record
-				if(status == nullptr && still_flagged){ c->err = "pairs left undecided (BSA_ST_TRACE) and no status array to report them in"; return BSA_E_UNSUPPORTED; }
-				return BSA_OK;
+				return undecided_unseen(c, status, still_flagged);
 			}
 		}
 	}
@@ -1526,7 +1536,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		[&]{ const int r = bsa_align_plan_create(c, qoff, qlen, toff, tlen, n, par, &p); tm1 = std::chrono::steady_clock::now(); return r; },
 		[&](uint8_t *ds, bsa_result_t *dout, uint32_t *dc, uint64_t *doff, uint32_t *dst){ return bsa_align_run(p, ds, dout, dc, cigar_cap_words, doff, dst); });
 	if(!p) return rc;
-	codes = p->codes || p->sys;           // both read the traceback off codes and may hand a pair over
+	codes = p->reads_codes();
 	if(timing){
 		const auto tm2 = std::chrono::steady_clock::now();
 		fprintf(stderr, "[bsa_align_batch] %zu pairs, mode %d, bandwidth %u: plan %.3f s (workspace %.1f GB, %zu chunks), staging + kernels + copies %.3f s, forward kernel %s\n", n, par->mode & 3, par->bandwidth,
@@ -1557,43 +1567,32 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		if(literal_can_take(k)) idx.push_back(k);
 		else if(st[k] & BSA_ST_TRACE) left_flagged ++;
 	}
-	// a caller that passed no status array cannot see a flag: undecided pairs are an error for it, never a silent zeroed result
-	auto finish = [&](size_t still_flagged) -> int {
-		if(status == nullptr && still_flagged){ c->err = "pairs left undecided (BSA_ST_TRACE) and no status array to report them in"; return BSA_E_UNSUPPORTED; }
-		return BSA_OK;
-	};
-	if(idx.empty()) return finish(left_flagged);
+	if(idx.empty()) return undecided_unseen(c, status, left_flagged);
 	const size_t m = idx.size();
 	c->last_handover = (long)m;
 	if(timing) fprintf(stderr, "[bsa_align_batch] %zu pairs handed over to the literal kernels\n", m);
-	std::vector<uint64_t> sq(m), stt(m), soff(m + 1);
-	std::vector<uint32_t> sql(m), stl(m), sst(m);
-	std::vector<bsa_result_t> sout(m);
-	size_t scap = 16;
-	for(size_t k = 0; k < m; k++){ sq[k] = qoff[idx[k]]; stt[k] = toff[idx[k]]; sql[k] = qlen[idx[k]]; stl[k] = tlen[idx[k]]; scap += (size_t)sql[k] + stl[k] + 2; }
-	std::vector<uint32_t> scig(cigar ? scap : 0);
 	bsa_align_params_t lp = *par;
 	lp.mode = (lp.mode | BSA_MODE_ROWRECORDS) & ~BSA_MODE_SCORE_ONLY;
 	const std::string keep_fwd = c->fwd_name, keep_trace = c->trace_name;         // the batch's kernels stay the ones reported, not the re-run's
-	rc = bsa_align_batch(c, seqs, seqs_bytes, sq.data(), sql.data(), stt.data(), stl.data(), m, &lp, sout.data(),
-		cigar ? scig.data() : nullptr, scap, (cigar && cigar_off) ? soff.data() : nullptr, sst.data());
+	SubBatch r;
+	rc = align_sub_batch(c, seqs, seqs_bytes, qoff, qlen, toff, tlen, idx, &lp, want_cig, r);
 	c->fwd_name = keep_fwd; c->trace_name = keep_trace;
 	// (literal_can_take filtered what the literal kernels decline, so BSA_E_UNSUPPORTED here is a real error of the re-run, not a pair
 	// to leave flagged: it is returned like any other)
 	if(rc != BSA_OK) return rc;
 	for(size_t k = 0; k < m; k++){
-		out[idx[k]] = sout[k]; st[idx[k]] = sst[k]; if(sst[k] & BSA_ST_TRACE) left_flagged ++;
+		out[idx[k]] = r.out[k]; st[idx[k]] = r.st[k]; if(r.st[k] & BSA_ST_TRACE) left_flagged ++;
 		if(par->mode & BSA_MODE_SCORE_ONLY) score_only_trim(out[idx[k]]);
 	}
-	if(cigar && cigar_off){
+	if(want_cig){
 		// splice the re-run pairs' CIGARs into the arena (the compact pass left them empty or, in the debug hook, filled)
 		std::vector<uint32_t> merged;
 		std::vector<uint64_t> noff(n + 1);
-		merged.reserve((size_t)cigar_off[n] + (size_t)soff[m]);
+		merged.reserve((size_t)cigar_off[n] + (size_t)r.off[m]);
 		size_t j = 0;
 		for(size_t k = 0; k < n; k++){
 			noff[k] = merged.size();
-			if(j < m && idx[j] == k){ merged.insert(merged.end(), scig.begin() + soff[j], scig.begin() + soff[j + 1]); j++; }
+			if(j < m && idx[j] == k){ merged.insert(merged.end(), r.cig.begin() + r.off[j], r.cig.begin() + r.off[j + 1]); j++; }
 			else merged.insert(merged.end(), cigar + cigar_off[k], cigar + cigar_off[k + 1]);
 		}
 		noff[n] = merged.size();
@@ -1601,7 +1600,7 @@ static int align_batch(bsa_ctx_t *c, const uint8_t *seqs, size_t seqs_bytes,
 		if(merged.size() > cigar_cap_words){ c->err = "cigar arena too small"; return BSA_E_CIGAR_CAP; }
 		if(!merged.empty()) memcpy(cigar, merged.data(), merged.size() * 4);
 	}
-	return finish(left_flagged);
+	return undecided_unseen(c, status, left_flagged);
 }
 
 // debug / test hook: copy the stored row records of `pair` to host.  Only meaningful right after a single-chunk run.
@@ -1628,9 +1627,9 @@ extern "C" int bsa_align_debug_rows(bsa_align_plan_t *p, uint32_t pair, uint8_t 
 // kernel timing for launches made outside this file (bsa_rows.hip): one (start, stop) event pair around the launch
 extern "C" int bsa_ctx_time_begin_internal(bsa_ctx_t *c, double cells, void **stop_event){
 	if(!c || !stop_event) return BSA_E_ARG;
-	c->ev_used = 0; c->last_cells = cells;
+	c->ev.used = 0; c->last_cells = cells;
 	hipEvent_t e0, e1;
-	int rc = ctx_event_pair(c, &e0, &e1);
+	int rc = c->ev.pair(c, &e0, &e1);
 	if(rc != BSA_OK) return rc;
 	HIPCHK(c, hipEventRecord(e0, c->stream));
 	*stop_event = (void*)e1;
@@ -1673,36 +1672,30 @@ extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *c, hipStream_t *st){
 extern "C" size_t bsa_ctx_workspace_limit_internal(bsa_ctx_t *c){ return c ? c->ws_limit : 0; }
 extern "C" void bsa_ctx_set_kmer_chain_stats_internal(bsa_ctx_t *c, double ms, long on_device, long on_host){
 	if(!c) return;
-	c->kmer_chain_ms = ms; c->kmer_on_device = on_device; c->kmer_on_host = on_host; c->kev_used = 0;
+	c->kmer_chain_ms = ms; c->kmer_on_device = on_device; c->kmer_on_host = on_host; c->kev.used = 0;
 }
 // bsa_kmer_chain_run (bsa_kmer_dev.hip) cannot wait for its kernels: it records a (start, stop) pair of the context's events around every chunk, *ev gets
 // 2 * chunks of them, and bsa_ctx_last_kmer_chain_ms adds them up when it is asked
 extern "C" int bsa_ctx_kmer_chain_events_internal(bsa_ctx_t *c, size_t chunks, long on_device, hipEvent_t **ev){
 	if(!c || !ev) return BSA_E_ARG;
 	(void)hipSetDevice(c->device);
-	while(c->kev.size() < 2 * chunks){
-		hipEvent_t e;
-		HIPCHK(c, hipEventCreate(&e));
-		c->kev.push_back(e);
-	}
-	c->kev_used = 2 * chunks;
+	const int rc = c->kev.grow(c, 2 * chunks);
+	if(rc != BSA_OK) return rc;
+	c->kev.used = 2 * chunks;
 	c->kmer_chain_ms = 0; c->kmer_on_device = on_device; c->kmer_on_host = 0;
-	*ev = c->kev.data();
+	*ev = c->kev.ev.data();
 	return BSA_OK;
 }
 extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *c, const char *msg){ if(c) c->err = msg ? msg : ""; }
 extern "C" int bsa_ctx_last_kmer_chain_ms(bsa_ctx_t *c, double *ms, long *pairs_on_device, long *pairs_on_host){
 	if(!c) return BSA_E_ARG;
-	if(c->kev_used){
+	if(c->kev.used){
 		(void)hipSetDevice(c->device);
-		HIPCHK(c, hipEventSynchronize(c->kev[c->kev_used - 1]));
-		double tot = 0;
-		for(size_t i = 0; i + 1 < c->kev_used; i += 2){
-			float t = 0;
-			HIPCHK(c, hipEventElapsedTime(&t, c->kev[i], c->kev[i + 1]));
-			tot += t;
-		}
-		c->kmer_chain_ms = tot; c->kev_used = 0;
+		HIPCHK(c, hipEventSynchronize(c->kev.ev[c->kev.used - 1]));
+		double tot = 0; long chunks = 0;
+		const int rc = c->kev.sum_ms(c, &tot, &chunks);          // (a sum, not a mean: the chunks ran one after the other)
+		if(rc != BSA_OK) return rc;
+		c->kmer_chain_ms = tot; c->kev.used = 0;
 	}
 	if(ms) *ms = c->kmer_chain_ms;
 	if(pairs_on_device) *pairs_on_device = c->kmer_on_device;

@@ -298,7 +298,9 @@ double bsa_align_plan_cells(const bsa_align_plan_t *plan);
  *     cigar_cap_words in processing order, so a pair can fit by pair order and not by processing order: WHICH of the fitting pairs are
  *     present after an overflow is unspecified.  Do not use a short run's words; run again with d_cigar_off[n] words.
  * A run leaves nothing behind that a later run reads: a plan may be run again on other sequences of the same lengths, after a short run,
- * and in turn with other plans of the same context.  bsa_edit_run has the same contract. */
+ * and in turn with other plans of the same context.  bsa_edit_run has the same contract.
+ * A plan runs the kernels that the BSA_* knobs chose when it was made (bsa_align_plan_create sizes the workspace slots for them): a knob that
+ * picks a kernel path, changed between the two calls, does not reach a plan that already stands. */
 int  bsa_align_run(bsa_align_plan_t *plan, const uint8_t *d_seqs,
                    bsa_result_t *d_out, uint32_t *d_cigar, size_t cigar_cap_words,
                    uint64_t *d_cigar_off, uint32_t *d_status);

@@ -1,0 +1,39 @@
+"""Generate tests/golden/align_dispatch.json: what the library of ONE named commit does with every case of tests/align_dispatch_cases.py -- the
+return code, the kernel names, the hand-over count and a SHA-256 over everything the call leaves.  The file is the reference of
+tests/test_align_dispatch_gpu.py for a change that must not alter behaviour, so it is recorded from the commit BEFORE such a change, never from
+the code under test: build that commit's library, point BSA_LIB_PATH at it, and say which commit it is.
+
+Run on the MI355X:  BSA_LIB_PATH=/path/to/that/libbsalign_hip.so python tests/golden/make_golden_align_dispatch.py --commit <sha>"""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, os.path.join(HERE, "..", ".."))
+import align_dispatch_cases as AD  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--commit", required=True, help="the commit whose library is loaded (written into the file)")
+    a = ap.parse_args()
+    if len(a.commit) < 7 or any(ch not in "0123456789abcdef" for ch in a.commit):
+        ap.error("--commit takes the hash of the commit being recorded")
+    import bsalign_amd as B
+    ctx = B.Context(0)
+    cases = {}
+    for case in AD.CASES:
+        cases[case["id"]] = AD.run_case(ctx, case)
+        print(case["id"], json.dumps(cases[case["id"]]), flush=True)
+    ctx.close()
+    with open(AD.FIXTURE, "w") as f:
+        json.dump({"commit": a.commit, "library": os.path.basename(B.LIB_PATH), "cases": cases}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    handed = sum(1 for r in cases.values() if r.get("handover"))
+    print("wrote %s: %d cases (%d with a hand-over), %d bytes" % (AD.FIXTURE, len(cases), handed, os.path.getsize(AD.FIXTURE)))
+
+
+if __name__ == "__main__":
+    main()
