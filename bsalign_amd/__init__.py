@@ -139,6 +139,9 @@ def lib():
         L.bsa_align_plan_create.argtypes = [vp, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(AlignParams), C.POINTER(vp)]
         if hasattr(L, "bsa_align8_abs_form_internal"):          # (a BSA_LIB_PATH build from before it: everything else still runs)
             L.bsa_align8_abs_form_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
+        if hasattr(L, "bsa_align8_x_choice_internal"):
+            L.bsa_align8_x_choice_internal.argtypes = [C.POINTER(AlignParams), C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_int,
+                                                       C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         L.bsa_align_plan_destroy.argtypes = [vp]
         L.bsa_align_plan_destroy.restype = None
         L.bsa_align_plan_cells.argtypes = [vp]
@@ -233,6 +236,25 @@ def align8_abs_form(par):
     rows = C.c_uint32(0)
     form = lib().bsa_align8_abs_form_internal(C.byref(par), C.byref(rows))
     return int(form), int(rows.value)
+
+
+X_CHOICE_FIELDS = ("form", "W", "L", "pw", "do2", "score", "abs", "m3", "wps", "rebase_rows", "grid", "groups", "nseg", "seg_rows", "spin_cap", "rmask", "ctl_bytes",
+                   "state_bytes", "n8", "nb8", "gap_model", "xq_need")
+X_NONE, X_STATIC, X_SEG, X_WHOLE, X_MIX = range(5)
+
+
+def align8_x_choice(par, count, max_tlen, static_band=False, code_fmt=0, score=False, xq_bytes=0, cus=256):
+    """what the 8-bit exact-arithmetic forward launcher would launch for a chunk of `count` pairs of par's scoring at par.bandwidth (x_choose; host only, under the
+    BSA_ALIGN8_* knobs as they stand): a dict of X_CHOICE_FIELDS plus "name" and "launch" (False: the launcher returns an error); xq_need is what bsa_align_run
+    sizes the row-segment buffer to"""
+    out = (C.c_uint64 * len(X_CHOICE_FIELDS))()
+    name = C.create_string_buffer(400)
+    rc = lib().bsa_align8_x_choice_internal(C.byref(par), count, max_tlen, int(static_band), code_fmt, int(score), xq_bytes, cus, out, name, len(name))
+    if rc < 0:
+        raise ValueError("bsa_align8_x_choice_internal: bad arguments")
+    d = dict(zip(X_CHOICE_FIELDS, (int(v) for v in out)))
+    d.update(name=name.value.decode(), launch=rc == 1)
+    return d
 
 
 def pack2bit(codes):

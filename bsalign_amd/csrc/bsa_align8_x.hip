@@ -1550,49 +1550,31 @@ static int x_cus(){
 	}();
 	return cus;
 }
-// bytes of a.xq the persistent form needs for `count` pairs (0: the shape has no persistent form)
+// THE SHAPE RULE: cells per lane and half W and lanes per pair L of the kernels of a bandwidth and a gap model (2 W L = bw); false: there are none.  One-piece and
+// linear gaps: 64 <8, 4>, 128 <16, 4>, 256 <16, 8>; two-piece gaps keep eight cells a half at 128: <8, 8>.  x_choose leaves it in two places, both behind a knob or
+// a check of their own: BSA_ALIGN8_X_LANES=8 runs <4, 8> at 64 (whole pairs only), and two-piece row segments at 128 run <16, 4> (unless BSA_ALIGN8_X2_LANES=8).
+static bool x_shape(uint32_t bw, int pw, uint32_t &W, uint32_t &L){
+	if(pw < 0 || pw > 2 || !(bw == 64u || bw == 128u || bw == 256u)) return false;
+	L = (bw == 256u || (pw == 2 && bw == 128u)) ? 8u : 4u;
+	W = bw / (2u * L);
+	return true;
+}
+// bytes of a.xq the persistent form needs for `count` pairs at the rule's shape (0: there are no such kernels): 64 dwords of control block and one a group, rounded
+// up by a whole 256 where x_segments rounds to one, so its check passes at this shape for every count.  The <16, 4, 2> first try at bandwidth 128 is not sized for:
+// it takes 59 state words a lane at sixteen pairs a wave where <8, 8, 2> takes 35 at eight, 15104 bytes a group of sixteen pairs against 2 x 8960, so it fits
+// whenever count mod 16 is 0 or above 8, or count > 48; for 1..8, 17..24 and 33..40 pairs in a buffer of exactly this size it does not, and x_choose falls back to
+// the <8, 8, 2> segments, which do.  (The context's buffer only grows: after a larger batch the first try fits there as well.)
 size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count){
-	const uint32_t W = bw / 16u;
-	if(pw > 2 || !(W == 4u || W == 8u || W == 16u)) return 0;
-	const uint32_t L = (W == 16u || (pw == 2 && W == 8u)) ? 8u : 4u, Wl = (W == 4u || (pw == 2 && W == 8u)) ? 8u : 16u;          // lanes per pair, cells per lane and half
+	uint32_t W, L;
+	if(!x_shape(bw, pw, W, L)) return 0;
 	const size_t groups = ((size_t)count * L + 63u) / 64u;
-	return (16u + groups) * 4u + 256u + groups * (size_t)(XS_WORDS(Wl, pw) * 64u * 4u);
+	return (16u + groups) * 4u + 256u + groups * (size_t)(XS_WORDS(W, pw) * 64u * 4u);
 }
 // name of a launch in the absolute-score form: the family's description, the rebase period and the form of the maxima that bsa_align8_abs_rows chose (tests read it)
 static const char *x_abs_name(const char *what, uint32_t rebase_rows, bool m3){
 	static thread_local char buf[320];
 	snprintf(buf, sizeof buf, "%s [rebase every %u rows] [%s]", what, rebase_rows, m3 ? "three-operand maxima, biased frame" : "integer maxima");
 	return buf;
-}
-// true when the launch was made
-template<int W, int L, int PW, bool DO2 = false, int WPS = 3, bool SCORE = false, bool ABS = false, bool M3 = ABS>
-static bool x_launch_xq(const Align8Args &a, hipStream_t st, hipError_t &err, uint32_t rebase_rows = 0u){
-	const char *qe = bsa_env("BSA_ALIGN8_XQ");
-	if(!a.xq || (qe && qe[0] == '0')) return false;
-	const uint32_t groups = (uint32_t)(((size_t)a.count * L + 63u) / 64u);
-	const uint32_t workers = (uint32_t)x_cus() * 4u * (uint32_t)WPS;          // waves per SIMD x SIMDs
-	if(!(qe && qe[0] == '1') && groups <= workers) return false;       // one generation: whole pairs
-	const size_t ctl_bytes = ((16u + (size_t)groups) * 4u + 255u) & ~(size_t)255u;
-	if(ctl_bytes + (size_t)groups * (XS_WORDS(W, PW) * 64u * 4u) > a.xq_bytes) return false;
-	// segments: the last item of the launch should be a few percent of a wave slot's share
-	uint32_t nseg = (uint32_t)std::min<uint64_t>(64u, (48ull * workers + groups - 1u) / groups);
-	uint32_t seg_rows = ((a.max_tlen + nseg - 1u) / std::max(nseg, 1u) + 7u) & ~7u;
-	if(const char *se = bsa_env("BSA_ALIGN8_XQ_SEG")){ const long v = atol(se); if(v >= 8) seg_rows = ((uint32_t)v + 7u) & ~7u; }
-	seg_rows = std::max(seg_rows, 64u);
-	nseg = std::max(1u, (a.max_tlen + seg_rows - 1u) / seg_rows);
-	XQArgs q;
-	q.ctl = a.xq; q.state = (uint32_t*)((uint8_t*)a.xq + ctl_bytes); q.ngroups = groups; q.nseg = nseg; q.seg_rows = seg_rows;
-	q.spin_cap = 1u << 22;
-	q.rmask = ABS ? rebase_rows - 1u : 0u;
-	if(const char *sc = bsa_env("BSA_ALIGN8_XQ_SPIN_CAP")){ const long v = atol(sc); if(v >= 1) q.spin_cap = (uint32_t)v; }          // (test hook: a cap of a few turns makes hand-over waits give up)
-	err = hipMemsetAsync(a.xq, 0, ctl_bytes, st);
-	if(err != hipSuccess) return true;
-	hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE, ABS, M3>), dim3(groups * nseg), dim3(64), 0, st, a, q);
-	err = hipGetLastError();
-	bsa_last_fwd_kernel = SCORE ? "k_align8_fwd_xq score-only (exact-arithmetic forward DP in row segments, no traceback codes)"
-		: ABS ? x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, 4-bit traceback codes)", rebase_rows, M3)
-		: "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
-	return true;
 }
 
 // Exact arithmetic is the reference's arithmetic only while nothing saturates: the guard of the compact path
@@ -1664,183 +1646,196 @@ uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw, bool *m3){
 	return r;
 }
 
+// The launcher's BSA_ALIGN8_* knobs, each read here and nowhere else (BSA_ALIGN8_ABS and _ABS_R: bsa_align8_abs_rows); x_choose takes them anew at every launch.
+struct XKnobs {
+	char xq = 0, lanes = 0;          // first character of _XQ (0: never row segments, 1: wherever there is a form and room) and of _X_LANES (4 / 8: one shape for all pairs)
+	bool lanes_set, n8_set, x2_lanes8, no_static, do2_off;
+	long xq_seg = 0, spin_cap = 0, n8 = -1;          // _XQ_SEG rows a segment, _XQ_SPIN_CAP (test hook: a cap of a few turns makes hand-over waits give up), _X_N8 (tuning: pairs that go eight lanes per pair)
+	XKnobs(){
+		const char *e;
+		if((e = bsa_env("BSA_ALIGN8_XQ"))) xq = e[0];
+		if((e = bsa_env("BSA_ALIGN8_XQ_SEG"))) xq_seg = atol(e);
+		if((e = bsa_env("BSA_ALIGN8_XQ_SPIN_CAP"))) spin_cap = atol(e);
+		if((lanes_set = (e = bsa_env("BSA_ALIGN8_X_LANES")) != nullptr)) lanes = e[0];
+		if((n8_set = (e = bsa_env("BSA_ALIGN8_X_N8")) != nullptr)) n8 = atol(e);
+		x2_lanes8 = (e = bsa_env("BSA_ALIGN8_X2_LANES")) && e[0] == '8';
+		no_static = bsa_env("BSA_ALIGN8_NO_STATIC") != nullptr;
+		do2_off = (e = bsa_env("BSA_ALIGN8_DO2")) && e[0] == '0';
+	}
+};
+
 // the code rows with two-bit D / Od fields (Align8Args::code_fmt 1): what the forward kernels need; the traceback side is asked in bsa_api.hip
 bool bsa_align8_do2_supported(const Align8Args &a, int pw){
 	const int go = -(int)(int8_t)a.gapo1;
-	const char *e = bsa_env("BSA_ALIGN8_DO2");
-	return pw == 1 && a.bw == 128u && go >= 1 && go <= 3 && !(e && e[0] == '0') && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && bsa_align8_x_supported(a, pw);
+	const XKnobs k;
+	return pw == 1 && a.bw == 128u && go >= 1 && go <= 3 && !k.do2_off && !k.lanes_set && !k.n8_set && bsa_align8_x_supported(a, pw);
 }
 
-static bool x8_at_64(){ const char *e = bsa_env("BSA_ALIGN8_X_LANES"); return e && e[0] == '8'; }
-hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){
-	if(a.count == 0) return hipSuccess;
-	const uint32_t b4 = (a.count + 63u) / 64u, b8 = (a.count + 31u) / 32u;          // blocks of 256 lanes at four / eight lanes per pair
-	if(a.code_fmt == 1u){
-		// two-bit D / Od fields (bsa_align8_do2_supported): bandwidth 128, one-piece gaps, four lanes per pair
-		if(pw != 1 || a.bw != 128u) return hipErrorInvalidValue;
-		hipError_t qe = hipSuccess;
-		const uint32_t rr = bsa_align8_abs_rows(a, pw);          // rebase period of the absolute-score form, 0: the difference form
-		if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
-			hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, true>), dim3(b4), dim3(256), 0, st, a);
-			bsa_last_fwd_kernel = "k_align8_fwd_x_static (exact-arithmetic forward DP, band in place, traceback codes with two-bit D/Od fields)";
-		} else if(rr && x_launch_xq<16, 4, 1, true, 3, false, true>(a, st, qe, rr)){
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", rr, true);
-			return qe;
-		} else if(rr){
-			hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, true>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", rr, true);
-		} else if(x_launch_xq<16, 4, 1, true>(a, st, qe)){
-			bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, traceback codes with two-bit D/Od fields)";
-			return qe;
-		} else {
-			hipLaunchKernelGGL((k_align8_fwd_x<16, 4, true>), dim3(b4), dim3(256), 0, st, a);
-			bsa_last_fwd_kernel = "k_align8_fwd_x (exact-arithmetic forward DP, traceback codes with two-bit D/Od fields)";
+// ONE LAUNCH of the forward DP, as x_choose decides it and x_run makes it
+enum XForm : uint32_t { X_NONE, X_STATIC, X_SEG, X_WHOLE, X_MIX };          // no such launch; band in place; row segments; whole pairs; whole pairs, four and eight lanes per pair in one launch
+struct XLaunch {
+	XForm form; uint32_t W, L; int pw;          // the kernel's shape and gap model (X_MIX: the four-lane share's <16, 4>; its eight-lane blocks are <8, 8>)
+	bool do2, score, abs, m3;                   // code format 1; score only; absolute-score form (X_MIX: in the four-lane blocks), with three-operand maxima
+	uint32_t wps, rebase_rows;                  // X_SEG: waves per SIMD the kernel is built for; abs: the rebase period
+	uint32_t grid;                              // blocks: of one wave for X_SEG, of four otherwise
+	XQArgs q; size_t ctl_bytes;                 // X_SEG: the kernel's arguments but for the two pointers, and the bytes of the control block in front of the states
+	uint32_t n8, nb8;                           // X_MIX: pairs and blocks at eight lanes per pair (the batch's last n8 pairs, the launch's first nb8 blocks)
+	const char *name;                           // for bsa_last_fwd_kernel; nullptr: none, bsa_align_run's default for the path shows
+};
+// The name of a launch.  Kept as they were when every launch site set (or did not set) its own, so some misdescribe their kernel: the in-place kernels without
+// code format 1 or score-only and the difference-form mix report nothing (the default names k_align8_fwd_x / k_align8_fwd_x2, whole pairs), the two-piece row
+// segments at bandwidth 64 report 4-bit codes (HISTORY §14 has the list).
+static const char *x_name(const XLaunch &l){
+	switch(l.form){
+		case X_STATIC:
+			return l.do2 ? "k_align8_fwd_x_static (exact-arithmetic forward DP, band in place, traceback codes with two-bit D/Od fields)"
+				: l.score ? "k_align8_fwd_x_static score-only (exact-arithmetic forward DP, band in place, no traceback codes)" : nullptr;
+		case X_SEG:
+			if(l.score) return "k_align8_fwd_xq score-only (exact-arithmetic forward DP in row segments, no traceback codes)";
+			if(l.do2) return l.abs ? x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, traceback codes with two-bit D/Od fields)", l.rebase_rows, l.m3)
+				: "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, traceback codes with two-bit D/Od fields)";
+			if(l.abs) return x_abs_name("k_align8_fwd_xq (exact-arithmetic forward DP in row segments, absolute scores, 4-bit traceback codes)", l.rebase_rows, l.m3);
+			if(l.pw == 2 && l.W == 16u) return "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, two-piece gaps, four lanes per pair, 8-bit traceback codes)";
+			if(l.pw == 2 && l.L == 8u) return "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, two-piece gaps, 8-bit traceback codes)";
+			return "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, 4-bit traceback codes)";
+		case X_WHOLE:
+			if(l.score) return "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)";
+			if(l.do2) return l.abs ? x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, traceback codes with two-bit D/Od fields)", l.rebase_rows, l.m3)
+				: "k_align8_fwd_x (exact-arithmetic forward DP, traceback codes with two-bit D/Od fields)";
+			if(l.abs) return x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", l.rebase_rows, l.m3);
+			return l.pw == 2 && l.W * l.L != 64u ? "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)" : nullptr;
+		case X_MIX:
+			return l.abs ? x_abs_name("k_align8_fwd_x_mix (exact-arithmetic forward DP, absolute scores in the four-lane blocks, 4-bit traceback codes)", l.rebase_rows, l.m3) : nullptr;
+		default: return nullptr;
+	}
+}
+// Row segments at l's shape: where the batch is more than one generation of resident waves (or BSA_ALIGN8_XQ=1) and a.xq holds its control block and states
+static bool x_segments(XLaunch &l, const Align8Args &a, const XKnobs &k, int cus){
+	const uint32_t groups = (uint32_t)(((size_t)a.count * l.L + 63u) / 64u);
+	const uint32_t workers = (uint32_t)cus * 4u * l.wps;          // waves per SIMD x SIMDs
+	if(k.xq != '1' && groups <= workers) return false;       // one generation: whole pairs
+	const size_t ctl_bytes = ((16u + (size_t)groups) * 4u + 255u) & ~(size_t)255u;
+	if(ctl_bytes + (size_t)groups * (XS_WORDS(l.W, l.pw) * 64u * 4u) > a.xq_bytes) return false;
+	// segments: the last item of the launch should be a few percent of a wave slot's share
+	uint32_t nseg = (uint32_t)std::min<uint64_t>(64u, (48ull * workers + groups - 1u) / groups);
+	uint32_t seg_rows = ((a.max_tlen + nseg - 1u) / std::max(nseg, 1u) + 7u) & ~7u;
+	if(k.xq_seg >= 8) seg_rows = ((uint32_t)k.xq_seg + 7u) & ~7u;
+	seg_rows = std::max(seg_rows, 64u);
+	nseg = std::max(1u, (a.max_tlen + seg_rows - 1u) / seg_rows);
+	l.form = X_SEG; l.grid = groups * nseg; l.ctl_bytes = ctl_bytes;
+	l.q = XQArgs{nullptr, nullptr, groups, nseg, seg_rows, k.spin_cap >= 1 ? (uint32_t)k.spin_cap : 1u << 22, l.abs ? l.rebase_rows - 1u : 0u};
+	return true;
+}
+// What to launch for a chunk of a.count > 0 pairs on a device of `cus` CUs (form X_NONE: nothing, the arguments name no kernel).  No HIP call.  In order: the shape;
+// band in place; absolute scores or differences; row segments; else whole pairs, at bandwidth 128 with one-piece gaps and plain codes split between lane counts.
+static XLaunch x_choose(const Align8Args &a, int pw, bool score, int cus){
+	const XKnobs k;
+	XLaunch l{};
+	l.pw = pw; l.score = score; l.do2 = a.code_fmt == 1u; l.wps = 3u;
+	// score only: one-piece and linear gaps, no codes; two-bit D / Od fields (bsa_align8_do2_supported): bandwidth 128, one-piece gaps, four lanes per pair
+	if(!x_shape(a.bw, pw, l.W, l.L) || (score && (pw > 1 || a.code_fmt != 0u)) || (l.do2 && (pw != 1 || a.bw != 128u))) return l;
+	auto done = [&a](XLaunch &r){ if(r.form != X_SEG && r.form != X_MIX) r.grid = (uint32_t)(((uint64_t)a.count * r.L + 255u) / 256u); r.name = x_name(r); return r; };
+	// bands that cover their whole queries stay in place (two-piece gaps: a kernel at 128 alone)
+	if(a.static_band && !k.no_static && !(pw == 2 && a.bw != 128u)){ l.form = X_STATIC; return done(l); }
+	// absolute-score form (bandwidth 128, 256; never score only); integer maxima at bandwidth 256 alone
+	if(!score && (l.rebase_rows = bsa_align8_abs_rows(a, pw, &l.m3)) != 0u) l.abs = true;
+	const bool mixable = !score && !l.do2 && pw == 1 && a.bw == 128u;
+	if(!score && pw <= 1 && a.bw == 64u && k.lanes == '8'){ l.W = 4u; l.L = 8u; }          // BSA_ALIGN8_X_LANES=8 at 64: eight lanes per pair, whole pairs only
+	if(a.xq && k.xq != '0' && l.W != 4u && !(mixable && (k.lanes_set || k.n8_set))){
+		if(pw == 2 && a.bw == 128u && !k.x2_lanes8){
+			// four lanes per pair at two waves per SIMD (sixteen pairs a wave share the per-row work: 126 ms against 137 for the eight-lane shape
+			// at three waves, C2's shape); bsa_align8_xq_bytes does not size for it: where it does not fit, the rule's own shape below
+			XLaunch f = l; f.W = 16u; f.L = 4u; f.wps = 2u;
+			if(x_segments(f, a, k, cus)) return done(f);
 		}
-		return hipGetLastError();
+		if(!(pw == 2 && a.bw == 256u) && x_segments(l, a, k, cus)) return done(l);
 	}
-	if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
-		if(pw == 2 && a.bw == 128u){ hipLaunchKernelGGL((k_align8_fwd_x_static<8, 8, 2>), dim3(b8), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 1 && a.bw == 64u){ hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 1>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 1 && a.bw == 128u){ hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 1 && a.bw == 256u){ hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 1>), dim3(b8), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 0 && a.bw == 64u){ hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 0>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 0 && a.bw == 128u){ hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 0>), dim3(b4), dim3(256), 0, st, a); return hipGetLastError(); }
-		if(pw == 0 && a.bw == 256u){ hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 0>), dim3(b8), dim3(256), 0, st, a); return hipGetLastError(); }
+	l.form = X_WHOLE;
+	if(mixable){
+		// Four lanes per pair (16 pairs per wave) cost 620 instructions per row of a wave, eight lanes per pair 387.  Pairs of one length finish together, so what
+		// counts is the largest number of waves any SIMD gets: whole rounds of one four-lane wave per SIMD, and a remainder of at most half a round as eight-lane
+		// waves (0.62 of a round instead of a whole one).  BSA_ALIGN8_X_LANES=4 / 8 forces one shape.
+		const uint32_t round4 = (uint32_t)cus * 4u * 16u;
+		uint32_t n4 = a.count / round4 * round4;
+		if(a.count - n4 > round4 / 2u) n4 = a.count;
+		if(k.lanes == '8') n4 = 0;
+		if(k.lanes == '4') n4 = a.count;
+		if(k.n8 >= 0 && (uint32_t)k.n8 <= a.count) n4 = a.count - (uint32_t)k.n8;
+		// (the four-lane shape runs the absolute-score form where it applies; the eight-lane one, eight cells a half, has none)
+		if(n4 == 0){ l.W = l.L = 8u; l.abs = l.m3 = false; l.rebase_rows = 0u; }
+		else if(n4 != a.count){ l.form = X_MIX; l.n8 = a.count - n4; l.nb8 = (l.n8 + 31u) / 32u; l.grid = l.nb8 + (n4 + 63u) / 64u; }
 	}
-	if(pw == 2 && a.bw == 64u){
-		hipError_t qe2 = hipSuccess;
-		bsa_last_fwd_kernel = "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)";
-		if(x_launch_xq<8, 4, 2>(a, st, qe2)) return qe2;
-		hipLaunchKernelGGL((k_align8_fwd_x2w<8, 4>), dim3(b4), dim3(256), 0, st, a);
-		return hipGetLastError();
-	}
-	if(pw == 2 && a.bw == 256u){
-		bsa_last_fwd_kernel = "k_align8_fwd_x2 (exact-arithmetic forward DP, two-piece gaps, 8-bit traceback codes)";
-		hipLaunchKernelGGL((k_align8_fwd_x2w<16, 8>), dim3(b8), dim3(256), 0, st, a);
-		return hipGetLastError();
-	}
-	if(pw == 2){
-		if(a.bw != 128u) return hipErrorInvalidValue;
-		hipError_t qe2 = hipSuccess;
-		// row segments: four lanes per pair at two waves per SIMD (sixteen pairs a wave share the per-row work: 126 ms against 137 for the
-		// eight-lane shape at three waves, C2's shape); BSA_ALIGN8_X2_LANES=8 keeps the eight-lane shape
-		{ const char *le = bsa_env("BSA_ALIGN8_X2_LANES");
-		  if(!(le && le[0] == '8') && x_launch_xq<16, 4, 2, false, 2>(a, st, qe2)){ bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, two-piece gaps, four lanes per pair, 8-bit traceback codes)"; return qe2; } }
-		if(x_launch_xq<8, 8, 2>(a, st, qe2)){ bsa_last_fwd_kernel = "k_align8_fwd_xq (exact-arithmetic forward DP in row segments, two-piece gaps, 8-bit traceback codes)"; return qe2; }
-		hipLaunchKernelGGL(k_align8_fwd_x2, dim3(b8), dim3(256), 0, st, a);
-		return hipGetLastError();
-	}
-	hipError_t qerr = hipSuccess;
-	if(pw == 0){
-		if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 0>(a, st, qerr)) return qerr;
-		bool m3 = false;
-		if(const uint32_t rr = bsa_align8_abs_rows(a, pw, &m3)){
-			// absolute-score form (bandwidth 128, 256): row segments, else whole pairs; integer maxima at bandwidth 256 alone
-			if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
-			if(a.bw == 256u && m3 && x_launch_xq<16, 8, 0, false, 3, false, true>(a, st, qerr, rr)) return qerr;
-			if(a.bw == 256u && !m3 && x_launch_xq<16, 8, 0, false, 3, false, true, false>(a, st, qerr, rr)) return qerr;
-			if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 0, false>), dim3(b4), dim3(256), 0, st, a, rr - 1u);
-			else if(m3) hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
-			else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 0, false, false>), dim3(b8), dim3(256), 0, st, a, rr - 1u);
-			bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr, m3);
-			return hipGetLastError();
-		}
-		if(a.bw == 128u && x_launch_xq<16, 4, 0>(a, st, qerr)) return qerr;
-		if(a.bw == 256u && x_launch_xq<16, 8, 0>(a, st, qerr)) return qerr;
-		switch(a.bw / 16){
-			case 4:
-				if(x8_at_64()) hipLaunchKernelGGL((k_align8_fwd_x0<4, 8>), dim3(b8), dim3(256), 0, st, a);
-				else hipLaunchKernelGGL((k_align8_fwd_x0<8, 4>), dim3(b4), dim3(256), 0, st, a);
-				break;
-			case 8:  hipLaunchKernelGGL((k_align8_fwd_x0<16, 4>), dim3(b4), dim3(256), 0, st, a); break;
-			case 16: hipLaunchKernelGGL((k_align8_fwd_x0<16, 8>), dim3(b8), dim3(256), 0, st, a); break;
-			default: return hipErrorInvalidValue;
-		}
-		return hipGetLastError();
-	}
-	if(a.bw == 64u && !x8_at_64() && x_launch_xq<8, 4, 1>(a, st, qerr)) return qerr;
-	bool m31 = false;
-	const uint32_t rr1 = bsa_align8_abs_rows(a, pw, &m31);          // rebase period of the absolute-score form, 0: the difference form; m31: its three-operand maxima (bandwidth 128: always)
-	if(rr1 && a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1, false, 3, false, true>(a, st, qerr, rr1)) return qerr;
-	if(rr1 && a.bw == 256u){
-		if(m31 ? x_launch_xq<16, 8, 1, false, 3, false, true>(a, st, qerr, rr1) : x_launch_xq<16, 8, 1, false, 3, false, true, false>(a, st, qerr, rr1)) return qerr;
-		if(m31) hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
-		else hipLaunchKernelGGL((k_align8_fwd_x_abs<8, 1, false, false>), dim3(b8), dim3(256), 0, st, a, rr1 - 1u);
-		bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1, m31);
-		return hipGetLastError();
-	}
-	if(a.bw == 128u && !bsa_env("BSA_ALIGN8_X_LANES") && !bsa_env("BSA_ALIGN8_X_N8") && x_launch_xq<16, 4, 1>(a, st, qerr)) return qerr;
-	if(a.bw == 256u && x_launch_xq<16, 8, 1>(a, st, qerr)) return qerr;
-	switch(a.bw / 16){
-		case 4:      // bandwidth 64: four lanes per pair (16 pairs per wave, eight cells per half); BSA_ALIGN8_X_LANES=8: eight lanes
-			if(x8_at_64()) hipLaunchKernelGGL((k_align8_fwd_x<4, 8>), dim3(b8), dim3(256), 0, st, a);
-			else hipLaunchKernelGGL((k_align8_fwd_x<8, 4>), dim3(b4), dim3(256), 0, st, a);
-			break;
-		case 8: {
-			// Four lanes per pair (16 pairs per wave) cost 620 instructions per row of a wave, eight lanes per pair 387.
-			// Pairs of one length finish together, so what counts is the largest number of waves any SIMD gets: whole
-			// rounds of one four-lane wave per SIMD, and a remainder of at most half a round as eight-lane waves (0.62 of
-			// a round instead of a whole one).  BSA_ALIGN8_X_LANES=4 / 8 forces one shape.
-			const char *le = bsa_env("BSA_ALIGN8_X_LANES");
-			const uint32_t round4 = (uint32_t)x_cus() * 4u * 16u;
-			uint32_t n4 = a.count / round4 * round4;
-			if(a.count - n4 > round4 / 2u) n4 = a.count;
-			if(le && le[0] == '8') n4 = 0;
-			if(le && le[0] == '4') n4 = a.count;
-			if(const char *ne = bsa_env("BSA_ALIGN8_X_N8")){ const long v = atol(ne); if(v >= 0 && (uint32_t)v <= a.count) n4 = a.count - (uint32_t)v; }      // tuning: pairs that go eight lanes per pair
-			// (the four-lane shape runs the absolute-score form where it applies; the eight-lane one, eight cells a half, has none)
-			if(n4 == a.count && rr1){
-				hipLaunchKernelGGL((k_align8_fwd_x_abs<4, 1, false>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a, rr1 - 1u);
-				bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x (exact-arithmetic forward DP, absolute scores, 4-bit traceback codes)", rr1, true);
-			} else if(n4 == a.count) hipLaunchKernelGGL((k_align8_fwd_x<16, 4>), dim3((n4 + 63u) / 64u), dim3(256), 0, st, a);
-			else if(n4 == 0) hipLaunchKernelGGL((k_align8_fwd_x<8, 8>), dim3(b8), dim3(256), 0, st, a);
-			else {
-				const uint32_t n8 = a.count - n4, nb8 = (n8 + 31u) / 32u;
-				if(rr1){
-					hipLaunchKernelGGL((k_align8_fwd_x_mix<true>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, rr1 - 1u);
-					bsa_last_fwd_kernel = x_abs_name("k_align8_fwd_x_mix (exact-arithmetic forward DP, absolute scores in the four-lane blocks, 4-bit traceback codes)", rr1, true);
-				} else hipLaunchKernelGGL((k_align8_fwd_x_mix<false>), dim3(nb8 + (n4 + 63u) / 64u), dim3(256), 0, st, a, nb8, n8, 0u);
-			}
-			break;
-		}
-		case 16: hipLaunchKernelGGL((k_align8_fwd_x<16, 8>), dim3(b8), dim3(256), 0, st, a); break;
-		default: return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
+	return done(l);
 }
 
-// BSA_MODE_SCORE_ONLY (bsa_api.hip): the SCORE forms of the one-piece kernels above at bandwidth 64, 128 and 256 -- the same choice between
-// whole-query bands in place, row segments and whole pairs as the launcher above makes, each pair leaving its record (bsa_score_rec_bytes)
-hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st){
-	if(a.count == 0) return hipSuccess;
-	if(pw > 1 || a.code_fmt != 0u || !(a.bw == 64u || a.bw == 128u || a.bw == 256u)) return hipErrorInvalidValue;
-	const dim3 b4((a.count + 63u) / 64u), b8((a.count + 31u) / 32u);
-	if(a.static_band && !bsa_env("BSA_ALIGN8_NO_STATIC")){
-		bsa_last_fwd_kernel = "k_align8_fwd_x_static score-only (exact-arithmetic forward DP, band in place, no traceback codes)";
-		if(pw == 1 && a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 1, false, true>), b4, dim3(256), 0, st, a);
-		if(pw == 1 && a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 1, false, true>), b4, dim3(256), 0, st, a);
-		if(pw == 1 && a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 1, false, true>), b8, dim3(256), 0, st, a);
-		if(pw == 0 && a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x_static<8, 4, 0, false, true>), b4, dim3(256), 0, st, a);
-		if(pw == 0 && a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 4, 0, false, true>), b4, dim3(256), 0, st, a);
-		if(pw == 0 && a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x_static<16, 8, 0, false, true>), b8, dim3(256), 0, st, a);
-		return hipGetLastError();
+// x_choose as plain numbers, for tests of its contract (bsa_align8_x_choice_internal; no device): false = no such launch
+bool bsa_align8_x_choice(const Align8Args &a, int pw, bool score, int cus, uint64_t out[BSA_X_CHOICE_WORDS], const char **name){
+	const XLaunch l = x_choose(a, pw, score, cus);
+	const uint64_t v[BSA_X_CHOICE_WORDS] = {l.form, l.W, l.L, (uint64_t)l.pw, l.do2, l.score, l.abs, l.m3, l.wps, l.rebase_rows, l.grid, l.q.ngroups, l.q.nseg, l.q.seg_rows,
+		l.q.spin_cap, l.q.rmask, l.ctl_bytes, l.form == X_SEG ? (uint64_t)l.q.ngroups * (XS_WORDS(l.W, l.pw) * 64u * 4u) : 0u, l.n8, l.nb8};
+	std::copy(v, v + BSA_X_CHOICE_WORDS, out);
+	*name = l.name;
+	return l.form != X_NONE;
+}
+
+// The one place that launches: every instance of the forward kernels is one row of the table in x_run, keyed by the description that runs it (a key twice does not
+// compile).  The row macros stay defined to the end of the file: x_run and the two launchers.
+constexpr uint32_t x_key(uint32_t form, uint32_t W, uint32_t L, int pw, bool do2, bool score, bool abs, bool m3, uint32_t wps){
+	return form | W << 3 | L << 8 | (uint32_t)pw << 12 | (uint32_t)do2 << 14 | (uint32_t)score << 15 | (uint32_t)abs << 16 | (uint32_t)m3 << 17 | wps << 18;
+}
+#define X_STATIC_K(W, L, PW, DO2, SCORE) case x_key(X_STATIC, W, L, PW, DO2, SCORE, false, false, 3): hipLaunchKernelGGL((k_align8_fwd_x_static<W, L, PW, DO2, SCORE>), grid, dim3(256), 0, st, a); break;
+#define X_SEG_K(W, L, PW, DO2, WPS, SCORE, ABS, M3) case x_key(X_SEG, W, L, PW, DO2, SCORE, ABS, M3, WPS): hipLaunchKernelGGL((k_align8_fwd_xq<W, L, PW, DO2, WPS, SCORE, ABS, M3>), grid, dim3(64), 0, st, a, q); break;
+#define X_ABS_K(L, PW, DO2, M3) case x_key(X_WHOLE, 16, L, PW, DO2, false, true, M3, 3): hipLaunchKernelGGL((k_align8_fwd_x_abs<L, PW, DO2, M3>), grid, dim3(256), 0, st, a, rmask); break;
+#define X_K1(W, L, DO2, SCORE) case x_key(X_WHOLE, W, L, 1, DO2, SCORE, false, false, 3): hipLaunchKernelGGL((k_align8_fwd_x<W, L, DO2, SCORE>), grid, dim3(256), 0, st, a); break;
+#define X_K0(W, L, SCORE) case x_key(X_WHOLE, W, L, 0, false, SCORE, false, false, 3): hipLaunchKernelGGL((k_align8_fwd_x0<W, L, SCORE>), grid, dim3(256), 0, st, a); break;
+#define X_K2W(W, L) case x_key(X_WHOLE, W, L, 2, false, false, false, false, 3): hipLaunchKernelGGL((k_align8_fwd_x2w<W, L>), grid, dim3(256), 0, st, a); break;
+#define X_MIX_K(ABS) case x_key(X_MIX, 16, 4, 1, false, false, ABS, ABS, 3): hipLaunchKernelGGL(k_align8_fwd_x_mix<ABS>, grid, dim3(256), 0, st, a, l.nb8, l.n8, ABS ? rmask : 0u); break;
+static hipError_t x_run(const XLaunch &l, const Align8Args &a, hipStream_t st){
+	XQArgs q = l.q;
+	if(l.form == X_SEG){
+		q.ctl = a.xq; q.state = (uint32_t*)((uint8_t*)a.xq + l.ctl_bytes);
+		const hipError_t err = hipMemsetAsync(a.xq, 0, l.ctl_bytes, st);
+		if(err != hipSuccess) return err;
 	}
-	hipError_t qerr = hipSuccess;
-	if(pw == 0){
-		if(a.bw == 64u && x_launch_xq<8, 4, 0, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 128u && x_launch_xq<16, 4, 0, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 256u && x_launch_xq<16, 8, 0, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x0<8, 4, true>), b4, dim3(256), 0, st, a);
-		if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x0<16, 4, true>), b4, dim3(256), 0, st, a);
-		if(a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x0<16, 8, true>), b8, dim3(256), 0, st, a);
-	} else {
-		if(a.bw == 64u && x_launch_xq<8, 4, 1, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 128u && x_launch_xq<16, 4, 1, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 256u && x_launch_xq<16, 8, 1, false, 3, true>(a, st, qerr)) return qerr;
-		if(a.bw == 64u) hipLaunchKernelGGL((k_align8_fwd_x<8, 4, false, true>), b4, dim3(256), 0, st, a);
-		if(a.bw == 128u) hipLaunchKernelGGL((k_align8_fwd_x<16, 4, false, true>), b4, dim3(256), 0, st, a);
-		if(a.bw == 256u) hipLaunchKernelGGL((k_align8_fwd_x<16, 8, false, true>), b8, dim3(256), 0, st, a);
+	const dim3 grid(l.grid);
+	const uint32_t rmask = l.rebase_rows - 1u;          // (read by the absolute-score forms alone)
+	switch(x_key(l.form, l.W, l.L, l.pw, l.do2, l.score, l.abs, l.m3, l.wps)){
+		// band in place: linear, one-piece (plain codes, code format 1, score only), two-piece gaps
+		X_STATIC_K(8, 4, 0, false, false) X_STATIC_K(16, 4, 0, false, false) X_STATIC_K(16, 8, 0, false, false)
+		X_STATIC_K(8, 4, 0, false, true) X_STATIC_K(16, 4, 0, false, true) X_STATIC_K(16, 8, 0, false, true)
+		X_STATIC_K(8, 4, 1, false, false) X_STATIC_K(16, 4, 1, false, false) X_STATIC_K(16, 8, 1, false, false)
+		X_STATIC_K(8, 4, 1, false, true) X_STATIC_K(16, 4, 1, false, true) X_STATIC_K(16, 8, 1, false, true)
+		X_STATIC_K(16, 4, 1, true, false) X_STATIC_K(8, 8, 2, false, false)
+		// row segments: the difference form, score only, absolute scores (integer maxima at <16, 8> alone), code format 1, two-piece gaps
+		X_SEG_K(8, 4, 0, false, 3, false, false, false) X_SEG_K(16, 4, 0, false, 3, false, false, false) X_SEG_K(16, 8, 0, false, 3, false, false, false)
+		X_SEG_K(8, 4, 1, false, 3, false, false, false) X_SEG_K(16, 4, 1, false, 3, false, false, false) X_SEG_K(16, 8, 1, false, 3, false, false, false)
+		X_SEG_K(8, 4, 0, false, 3, true, false, false) X_SEG_K(16, 4, 0, false, 3, true, false, false) X_SEG_K(16, 8, 0, false, 3, true, false, false)
+		X_SEG_K(8, 4, 1, false, 3, true, false, false) X_SEG_K(16, 4, 1, false, 3, true, false, false) X_SEG_K(16, 8, 1, false, 3, true, false, false)
+		X_SEG_K(16, 4, 0, false, 3, false, true, true) X_SEG_K(16, 8, 0, false, 3, false, true, true) X_SEG_K(16, 8, 0, false, 3, false, true, false)
+		X_SEG_K(16, 4, 1, false, 3, false, true, true) X_SEG_K(16, 8, 1, false, 3, false, true, true) X_SEG_K(16, 8, 1, false, 3, false, true, false)
+		X_SEG_K(16, 4, 1, true, 3, false, false, false) X_SEG_K(16, 4, 1, true, 3, false, true, true)
+		X_SEG_K(8, 4, 2, false, 3, false, false, false) X_SEG_K(8, 8, 2, false, 3, false, false, false) X_SEG_K(16, 4, 2, false, 2, false, false, false)
+		// whole pairs in absolute scores
+		X_ABS_K(4, 0, false, true) X_ABS_K(8, 0, false, true) X_ABS_K(8, 0, false, false)
+		X_ABS_K(4, 1, false, true) X_ABS_K(8, 1, false, true) X_ABS_K(8, 1, false, false) X_ABS_K(4, 1, true, true)
+		// whole pairs in differences: one-piece gaps (plain codes, code format 1, score only), linear gaps, two-piece gaps
+		X_K1(4, 8, false, false) X_K1(8, 4, false, false) X_K1(8, 8, false, false) X_K1(16, 4, false, false) X_K1(16, 8, false, false)
+		X_K1(16, 4, true, false) X_K1(8, 4, false, true) X_K1(16, 4, false, true) X_K1(16, 8, false, true)
+		X_K0(4, 8, false) X_K0(8, 4, false) X_K0(16, 4, false) X_K0(16, 8, false) X_K0(8, 4, true) X_K0(16, 4, true) X_K0(16, 8, true)
+		X_K2W(8, 4) X_K2W(16, 8) case x_key(X_WHOLE, 8, 8, 2, false, false, false, false, 3): hipLaunchKernelGGL(k_align8_fwd_x2, grid, dim3(256), 0, st, a); break;
+		// four and eight lanes per pair in one launch
+		X_MIX_K(false) X_MIX_K(true)
+		default: return hipErrorInvalidValue;          // (a description x_choose does not make: no instance is built for it)
 	}
-	bsa_last_fwd_kernel = "k_align8_fwd_x score-only (exact-arithmetic forward DP, no traceback codes)";
+	if(l.name) bsa_last_fwd_kernel = l.name;
 	return hipGetLastError();
 }
+static hipError_t x_launch(const Align8Args &a, int pw, bool score, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	const XLaunch l = x_choose(a, pw, score, x_cus());
+	return l.form == X_NONE ? hipErrorInvalidValue : x_run(l, a, st);
+}
+// Called once per chunk; chunks of one run may choose differently, and bsa_last_fwd_kernel is left by the last one that names its launch
+hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){ return x_launch(a, pw, false, st); }
+// BSA_MODE_SCORE_ONLY (bsa_api.hip): the SCORE forms of the one-piece and linear kernels at bandwidth 64, 128 and 256, each pair leaving its record (bsa_score_rec_bytes)
+hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st){ return x_launch(a, pw, true, st); }

@@ -967,6 +967,24 @@ extern "C" int bsa_align8_abs_form_internal(const bsa_align_params_t *par, uint3
 	return r == 0u ? 0 : m3 ? 2 : 1;
 }
 
+// What bsa_launch_align8_fwd_x (score: ..._x_score) would launch for a chunk of `count` pairs of this scoring at par->bandwidth, targets of up to max_tlen rows, on a device of
+// `cus` CUs with a row-segment buffer of xq_bytes (0: none), under the BSA_ALIGN8_* knobs as they stand; needs no device.  out: the BSA_X_CHOICE_WORDS numbers of
+// bsa_align8_x_choice, the gap model and what bsa_align_run would size the buffer to (bsa_align8_xq_bytes); name: what the launch reports ("" = nothing).  1 = a launch, 0 = none
+// (the launcher returns hipErrorInvalidValue), -1 = bad arguments.
+extern "C" int bsa_align8_x_choice_internal(const bsa_align_params_t *par, uint32_t count, uint32_t max_tlen, int static_band, uint32_t code_fmt, int score, uint64_t xq_bytes,
+		int cus, uint64_t *out, char *name, size_t name_cap){
+	if(!par || !out || !name || !name_cap || count == 0u || cus <= 0) return -1;
+	static uint32_t never_read;          // (the launcher asks only whether there is a buffer)
+	const int pw = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, (int)par->bandwidth);
+	Align8Args a = align8_scoring_args(par, par->bandwidth, par->mode & 3);
+	a.count = count; a.max_tlen = max_tlen; a.static_band = static_band ? 1u : 0u; a.code_fmt = code_fmt; a.xq = xq_bytes ? &never_read : nullptr; a.xq_bytes = (size_t)xq_bytes;
+	const char *nm = nullptr;
+	const bool ok = bsa_align8_x_choice(a, pw, score != 0, cus, out, &nm);
+	out[BSA_X_CHOICE_WORDS] = (uint64_t)pw; out[BSA_X_CHOICE_WORDS + 1] = bsa_align8_xq_bytes(par->bandwidth, pw, count);
+	snprintf(name, name_cap, "%s", nm ? nm : "");
+	return ok ? 1 : 0;
+}
+
 // The one place that decides what bsa_align_run launches for a plan whose codes / sys / generic flags stand; t: the plan's scoring at its width and mode.
 static void align8_choose_path(bsa_align_plan *p, const Align8Args &t){
 	const char *fe = bsa_env("BSA_ALIGN8_FWD");

@@ -300,6 +300,11 @@ hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st);
 hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st);
 hipError_t bsa_launch_align8_score_finish(const Align8Args &a, bsa_result_t *out, hipStream_t st);
 size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count);       // what Align8Args::xq must hold for a launch of `count` pairs (0: no persistent form)
+// what the two launchers above would launch for a chunk on a device of `cus` CUs, as plain numbers (bsa_align8_x.hip: x_choose; no device, for tests): form (0 none, 1 band in
+// place, 2 row segments, 3 whole pairs, 4 four- and eight-lane blocks), W, L, pw, do2, score, abs, m3, waves per SIMD, rebase rows, grid, segment groups, segments, rows a
+// segment, spin cap, rmask, control-block bytes, state bytes, n8, nb8
+#define BSA_X_CHOICE_WORDS 20
+bool bsa_align8_x_choice(const Align8Args &a, int pw, bool score, int cus, uint64_t out[BSA_X_CHOICE_WORDS], const char **name);
 // whole-query bands above 256 columns, global mode: systolic wavefront + its own code layout and traceback (bsa_align8_sys.hip)
 int bsa_align8_sys_supported(const Align8Args &a, int pw);          // 0 no, 1 inside the static guard, 2 with the kernel checking every pair (Align8Args::sys_chk)
 size_t bsa_align8_sys_slot_bytes(uint32_t qlen, uint32_t tlen, int pw);
