@@ -139,6 +139,8 @@ def lib():
         L.bsa_align_plan_create.argtypes = [vp, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(AlignParams), C.POINTER(vp)]
         if hasattr(L, "bsa_align8_abs_form_internal"):          # (a BSA_LIB_PATH build from before it: everything else still runs)
             L.bsa_align8_abs_form_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
+        if hasattr(L, "bsa_align8_flag_span_internal"):
+            L.bsa_align8_flag_span_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
         if hasattr(L, "bsa_align8_x_choice_internal"):
             L.bsa_align8_x_choice_internal.argtypes = [C.POINTER(AlignParams), C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_int,
                                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
@@ -236,6 +238,17 @@ def align8_abs_form(par):
     rows = C.c_uint32(0)
     form = lib().bsa_align8_abs_form_internal(C.byref(par), C.byref(rows))
     return int(form), int(rows.value)
+
+
+FLAG_SPAN_TERMS = ("M: f - d", "D: d - E", "D: f - E", "D: d - E, row -1", "D: f - E, row -1", "R, Od")
+
+
+def align8_flag_span(par):
+    """largest difference a one-bit flag insert of the absolute-score forward DP sees in a stored cell, for a scoring at par.bandwidth (bsa_align8_flag_span;
+    host only): (span, terms) with terms the FLAG_SPAN_TERMS it is the maximum of; span 0 = the difference form, -1 = not taken by the exact-arithmetic kernel"""
+    terms = (C.c_uint32 * len(FLAG_SPAN_TERMS))()
+    span = lib().bsa_align8_flag_span_internal(C.byref(par), terms)
+    return int(span), tuple(int(v) for v in terms)
 
 
 X_CHOICE_FIELDS = ("form", "W", "L", "pw", "do2", "score", "abs", "m3", "wps", "rebase_rows", "grid", "groups", "nseg", "seg_rows", "spin_cap", "rmask", "ctl_bytes",

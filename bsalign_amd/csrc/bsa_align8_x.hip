@@ -53,6 +53,15 @@ static __device__ __forceinline__ uint32_t x_satsubu(uint32_t a, uint32_t b){ re
 static __device__ __forceinline__ uint32_t x_acc(uint32_t acc, uint32_t flag, uint32_t two){
 	return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, acc) * __builtin_bit_cast(xv2u, two) + __builtin_bit_cast(xv2u, flag)));
 }
+// One-bit flag "a == b" of a cell of x_forward_abs, put into its accumulator from n = b - a per half, where 0 <= a - b <= 256 (bsa_align8_flag_span has the
+// bound): such an n is 0 or has bits 8 .. 15 all set, so any one of those bits is the flag inverted, and `bit` (one bit of 8 .. 15 in both halves, a constant of
+// the cell that the compiler keeps in an SGPR) picks the place: acc = (bit & ~n) | (acc & ~bit), ONE v_bitop3_b32 (table 0x4E; of the operands a, b, c the table is
+// the same expression of 0xF0, 0xCC, 0xAA).  By the builtin: from the plain expression the compiler, which knows the other bits of acc, makes a v_and_b32 per cell
+// and a tree of three-operand exclusive-ors, half an instruction a cell more.  Nothing but the cell's own bit changes, so a cell outside the bound spoils its
+// own flag only.  x_ins0 is the first cell of an accumulator, bit & ~n (table 0x0A): no zero to read.
+static __device__ __forceinline__ uint32_t x_ins(uint32_t acc, uint32_t n, uint32_t bit){ return __builtin_amdgcn_bitop3_b32(n, acc, bit, 0x4E); }
+static __device__ __forceinline__ uint32_t x_ins0(uint32_t n, uint32_t bit){ return __builtin_amdgcn_bitop3_b32(n, n, bit, 0x0A); }
+static __device__ __forceinline__ uint32_t x_shl15(uint32_t a){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) << 15)); }
 static __device__ __forceinline__ uint32_t x_ashr8(uint32_t a){ return __builtin_bit_cast(uint32_t, (xv2s)(__builtin_bit_cast(xv2s, a) >> 8)); }
 static __device__ __forceinline__ uint32_t x_shl8(uint32_t a){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) << 8)); }
 // x = take ? y : x, in place (the band corrections: a plain C select makes the register allocator copy the whole band)
@@ -930,7 +939,12 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 // window's selector of a column is {byte of its code, sign of that byte} per half (selectors 8 .. 11 replicate the top bit of bytes 1, 3, 5, 7);
 // code 4 (beyond the query end) selects the PADS byte and the constant 0xFF: a fifth entry at no cost, queries shorter than the band included.
 // REBASE: every (rmask + 1) rows the H^ of lane 0's first slot is subtracted from Hp and E and added to base (bsa_align8_abs_rows has the bound).
-// Flags are bit 0 of a half, M and R accumulated as they are stored (not inverted); accumulators and two-bit fields fill the low byte.
+// FLAGS.  M, R (and D, Od of the four planes) are one bit a cell, accumulated as they are stored (not inverted), eight cells to an accumulator per half: cell k & 7 == 0
+// in bit 15, so they fill the HIGH byte of a half in the code row's byte order.  A flag is "two scores are equal" where the difference a - b is known to lie in 0 .. 256
+// (bsa_align8_flag_span derives it for every scoring of the guard), so of n = b - a bits 8 .. 15 are all clear (equal) or all set: two instructions a cell, the packed
+// difference and one v_bitop3_b32 that puts the cell's bit of ~n into the accumulator (x_ins; the saturating form it replaces took three, the last a v_pk_mad_u16):
+//     M: n = d - h     R: n = hg - fm     D: n = E - h     Od: n = hg - en   (= (h - en) + gapo: zero exactly where the field h - en equals -gapo)
+// Cell 0 alone keeps the saturating comparison for M (pass 2 says why).  The two-bit D / Od fields are a Horner multiply-add (x_acc) and fill the low byte.
 // PW: 1 one-piece gaps, 0 linear gaps (gapo = 0: E^ of a cell is its upper neighbour's H^, R and Od are always set).  DO2: the two-bit D / Od fields (four lanes, one piece);
 // otherwise the four planes, with D (h == E) and Od (field == -gapo) accumulated as they are stored too.  L = 8: bandwidth 256, a half is one reference block of sixteen cells.
 // EXT: the staging area and the window come from the caller (k_align8_fwd_x_mix).
@@ -972,10 +986,8 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 	const int GE = gape1, GO = gapo1;
 	const uint32_t GO16 = x_i16(GO), GE16 = x_i16(GE);
 	const uint32_t ONE1 = 0x00010001u;
-	uint32_t TWO = 0x00020002u;
-	asm volatile("" : "+s"(TWO));
 	uint32_t FOUR = 0x00040004u;
-	asm volatile("" : "+s"(FOUR));
+	asm volatile("" : "+s"(FOUR));                         // opaque multiplier of x_acc (the two-bit fields)
 	const uint32_t DOSP = (GO == -1) ? 2u : 1u;
 	const uint32_t MINF16 = x_i16(BSA_EPI8_MIN - 2 * GE);
 	const int gopen = gapo1 + gape1;
@@ -983,7 +995,6 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 	const uint32_t ENT16 = x_i16(cfirst - GE);             // the entering cell's H^ above the last cell's
 	const int NEWNE = (PW == 0) ? 0 : GE;                  // gape - e of an entering cell (e = 0; linear gaps: e is the constant gape)
 	const int NE0 = (PW == 0) ? 0 : GE - BSA_EPI8_MIN;     // ... of row -1 (e = -63)
-	const uint32_t NGO1 = x_i16(-GO - 1);
 	static_assert(M3 || L == 8, "no scoring inside bsa_align8_x_supported leaves the biased frame at bandwidth 128 (bsa_align8_abs_rows)");
 	constexpr int FB = M3 ? 0x4000 : 0;                    // where the frame sits: H^ of lane 0's first slot after a rebase
 	__shared__ __attribute__((aligned(8))) uint32_t xa_mtab[8];
@@ -1195,13 +1206,15 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		uint32_t tmpE0 = 0, hfirst = 0;
 #pragma unroll
 		for(int k = 0; k < W; k++){
-			uint32_t h, en;
+			const uint32_t BIT = 0x80008000u >> (k & 7);
+			auto ins = [&](uint32_t acc, uint32_t n) -> uint32_t { return (k & 7) == 0 ? x_ins0(n, BIT) : x_ins(acc, n, BIT); };
+			uint32_t h, en, hg = 0;
 			if constexpr (M3){
 				h = x_max3(E[k], (k == 0) ? d0h : d[k], f);
 				if constexpr (PW != 0){
-					const uint32_t hg = x_add(h, GO16);
+					hg = x_add(h, GO16);
 					const uint32_t fm = x_max(f, hg);
-					accR[k >> 3] = x_acc(accR[k >> 3], x_satsubu(ONE1, x_sub(fm, hg)), TWO);
+					accR[k >> 3] = ins(accR[k >> 3], x_sub(hg, fm));
 					f = fm;
 					en = x_max(E[k], hg);
 				} else { f = h; en = h; }
@@ -1209,8 +1222,12 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 			h = x_max(m[k], f);
 			const uint32_t fm = x_max(f, mg[k]);
 			f = fm;
-			if constexpr (PW != 0) accR[k >> 3] = x_acc(accR[k >> 3], x_satsubu(ONE1, x_sub(fm, mg[k])), TWO);
-			en = (PW == 0) ? h : x_max(E[k], x_add(h, GO16));          // (gapo = 0: h >= E)
+			if constexpr (PW != 0){
+				// R as fm == hg here too (the comment above: max(f, mg) = max(f, hg), and the two comparisons agree); fm - mg has no bound where f > m
+				hg = x_add(h, GO16);
+				accR[k >> 3] = ins(accR[k >> 3], x_sub(hg, fm));
+				en = x_max(E[k], hg);
+			} else en = h;          // (gapo = 0: h >= E)
 			}
 			if constexpr (DO2){
 				const uint32_t fld = x_sub(h, en);
@@ -1218,23 +1235,28 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 				if((k & 3) == 0) accDO[k >> 2] = fld;
 				else accDO[k >> 2] = x_acc(accDO[k >> 2], fld, FOUR);
 			} else {
-				accD[k >> 3] = x_acc(accD[k >> 3], x_satsubu(ONE1, x_sub(h, E[k])), TWO);
-				if constexpr (PW != 0) accO[k >> 3] = x_acc(accO[k >> 3], x_satsubu(x_sub(h, en), NGO1), TWO);          // field == -gapo
+				accD[k >> 3] = ins(accD[k >> 3], x_sub(E[k], h));
+				// field == -gapo: hg - en = (h - en) + gapo, in gapo .. 0 because hg <= en <= h
+				if constexpr (PW != 0) accO[k >> 3] = ins(accO[k >> 3], x_sub(hg, en));
 			}
-			accM[k >> 3] = x_acc(accM[k >> 3], x_satsubu(ONE1, x_sub(h, d[k])), TWO);
+			// Cell 0 keeps the saturating comparison, its flag put at bit 15: lane 0's h comes from d0h (the first-cell rule) while M compares with d0s, and where
+			// d0h < d0s the difference h - d0s can be negative, which saturates to "no match" and would read as a match from the bits of d0s - h.
+			if(k == 0) accM[0] = x_shl15(x_satsubu(ONE1, x_sub(h, d[0])));
+			else accM[k >> 3] = ins(accM[k >> 3], x_sub(d[k], h));
 			Hp[k] = h;
 			if(k == 0){ tmpE0 = en; hfirst = h; }
 			else E[k - 1] = en;
 		}
-		// ---- flags of special cells (x_forward's, on accumulators that are not inverted and sit in the low byte)
+		// ---- flags of special cells (x_forward's, on accumulators that are not inverted; the one-bit flags sit in the HIGH byte of a half, cell 0 of eight in
+		// bit 15, the two-bit fields in the low byte)
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull, 0)){
 			if(first && rbeg == 0u){
 				const uint32_t hl = hfirst & 0xffffu;
-				accM[0] = (accM[0] & ~0x80u) | ((hl == q0m) ? 0x80u : 0u);
+				accM[0] = (accM[0] & ~0x8000u) | ((hl == q0m) ? 0x8000u : 0u);
 				if constexpr (DO2){
 					const uint32_t fld = (accDO[0] >> 6) & 3u;
 					accDO[0] = (accDO[0] & ~0xC0u) | ((hl == q0d) ? 0x40u : 0u) | ((fld == (uint32_t)(-GO)) ? 0x80u : 0u);
-				} else accD[0] = (accD[0] & ~0x80u) | ((hl == q0d) ? 0x80u : 0u);
+				} else accD[0] = (accD[0] & ~0x8000u) | ((hl == q0d) ? 0x8000u : 0u);
 			}
 		}
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov > 1u) & actm) != 0ull, 0)){
@@ -1245,7 +1267,7 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 #pragma unroll
 				for(int n = 0; n < NACC; n++){
 					const int cd = min(max(nd - 8 * n, 0), 8), cm = min(max(nm - 8 * n, 0), 8);
-					const uint32_t md = ((1u << (8 - cd)) - 1u) << (16 * hf), mm = ((1u << (8 - cm)) - 1u) << (16 * hf);
+					const uint32_t md = ((1u << (8 - cd)) - 1u) << (16 * hf + 8), mm = ((1u << (8 - cm)) - 1u) << (16 * hf + 8);
 					if(mov != 0u){ if constexpr (!DO2) accD[n] &= ~md; accM[n] &= ~mm; }
 				}
 				if constexpr (DO2){
@@ -1261,19 +1283,20 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		} else if constexpr (DO2){
 			const uint32_t t = accDO[NDO - 1];
 			if(mov == 1u && last && (t & 0x00030000u) == 0u) accDO[NDO - 1] = t | (DOSP << 16);
-		} else accD[NACC - 1] &= ~((mov == 1u && last) ? 0x00010000u : 0u);          // band cell bw - 1 after a slide by one: no deletion there
+		} else accD[NACC - 1] &= ~((mov == 1u && last) ? 0x01000000u : 0u);          // band cell bw - 1 after a slide by one: no deletion there
 		if constexpr (PW == 0){
 #pragma unroll
-			for(int n = 0; n < NACC; n++){ accR[n] = 0x00FF00FFu; accO[n] = 0x00FF00FFu; }          // linear gaps: every gap is opened at length 1
+			for(int n = 0; n < NACC; n++){ accR[n] = 0xFF00FF00u; accO[n] = 0xFF00FF00u; }          // linear gaps: every gap is opened at length 1
 		}
 		// ---- the code row (bsa_common.h "COMPACT slot"), the layouts of x_forward
 		{
 			uint32_t cur[ND];
+			// (one-bit flags are bytes 1 and 3 of their accumulators, two-bit fields bytes 0 and 2)
 			if constexpr (DO2){
 				// M | R << 8 | two-bit fields << 16 per reference block
 #pragma unroll
 				for(int n = 0; n < NACC; n++){
-					const uint32_t t1 = __builtin_amdgcn_perm(accR[n], accM[n], 0x06020400u);
+					const uint32_t t1 = __builtin_amdgcn_perm(accR[n], accM[n], 0x07030501u);
 					const uint32_t t2 = __builtin_amdgcn_perm(accDO[2 * n], accDO[2 * n + 1], 0x06020400u);
 					cur[n] = __builtin_amdgcn_perm(t2, t1, 0x05040100u);
 					cur[NACC + n] = __builtin_amdgcn_perm(t2, t1, 0x07060302u);
@@ -1282,15 +1305,15 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 				// M | D << 8 | R << 16 | Od << 24 per reference block
 #pragma unroll
 				for(int n = 0; n < NACC; n++){
-					const uint32_t t1 = __builtin_amdgcn_perm(accD[n], accM[n], 0x06020400u);
-					const uint32_t t2 = __builtin_amdgcn_perm(accO[n], accR[n], 0x06020400u);
+					const uint32_t t1 = __builtin_amdgcn_perm(accD[n], accM[n], 0x07030501u);
+					const uint32_t t2 = __builtin_amdgcn_perm(accO[n], accR[n], 0x07030501u);
 					cur[n] = __builtin_amdgcn_perm(t2, t1, 0x05040100u);
 					cur[NACC + n] = __builtin_amdgcn_perm(t2, t1, 0x07060302u);
 				}
 			} else {
 				// sixteen cells a block: dword 0 = M | D << 16, dword 1 = R | Od << 16
-				const uint32_t xm = __builtin_amdgcn_perm(accM[0], accM[1], 0x06020400u), xd = __builtin_amdgcn_perm(accD[0], accD[1], 0x06020400u);
-				const uint32_t xr = __builtin_amdgcn_perm(accR[0], accR[1], 0x06020400u), xo = __builtin_amdgcn_perm(accO[0], accO[1], 0x06020400u);
+				const uint32_t xm = __builtin_amdgcn_perm(accM[0], accM[1], 0x07030501u), xd = __builtin_amdgcn_perm(accD[0], accD[1], 0x07030501u);
+				const uint32_t xr = __builtin_amdgcn_perm(accR[0], accR[1], 0x07030501u), xo = __builtin_amdgcn_perm(accO[0], accO[1], 0x07030501u);
 				cur[0] = __builtin_amdgcn_perm(xd, xm, 0x05040100u); cur[1] = __builtin_amdgcn_perm(xo, xr, 0x05040100u);
 				cur[2] = __builtin_amdgcn_perm(xd, xm, 0x07060302u); cur[3] = __builtin_amdgcn_perm(xo, xr, 0x07060302u);
 			}
@@ -1644,6 +1667,38 @@ uint32_t bsa_align8_abs_rows(const Align8Args &a, int pw, bool *m3){
 		r = f;
 	}
 	return r;
+}
+
+// Largest difference that a one-bit flag insert of x_forward_abs (x_ins) sees in a STORED cell of a live pair; the insert is exact for 0 .. 256.  terms (may be
+// null) receives the BSA_FLAG_SPAN_TERMS terms the maximum is taken over.  0: the scoring does not run the absolute-score form.
+// With m = smax, n = -smin, go, ge, g as in bsa_align8_abs_rows, P = 63 (-BSA_EPI8_MIN = BSA_EPI8_MAX) and, of a cell (x, y), A = Hp = H^(x - 1, y - 1) its diagonal
+// predecessor, U = H^(x, y - 1) its upper and Lf = H^(x - 1, y) its left neighbour:
+//   * S~ = S - 2 gape lies in [-max(n, P) + 2 ge, m + 2 ge]: the low end is a mismatch or the pad code beyond the query's end (-P - 2 gape), whichever is lower.
+//   * s1 = m + go + 2 ge bounds a step between computed neighbours from above, along a row (U - A, bsa_align8_abs_rows) and, by the same induction with rows and
+//     columns exchanged, down a column (Lf - A); both are at least -go (H >= F, H >= E of the next row).  The induction down a column starts at the band's first
+//     cell: after a slide its neighbours are computed cells; on a row that does not move or that jumps, the first-cell rule clamps it to at most BSA_EPI8_MAX above
+//     the virtual column, which is gape below the cell's upper neighbour: c0 = P + ge.  So Lf - A <= V = max(s1, c0).
+//   * E^ lies in [U - go, U] and f = F^ in [Lf - go, Lf] (or is the low -P - 2 gape sentinel), h = max(E, d, f) with d = A + S~.
+//   M  (h - d = max(0, E - d, f - d)):  E - d <= (U - A) - S~ <= s1 + max(n, P) - 2 ge  and  f - d <= (Lf - A) - S~ <= V + max(n, P) - 2 ge             [term 0: the latter]
+//   D  (h - E = max(0, d - E, f - E)):  d - E <= (A - U) + S~ + go <= m + 2 ge + 2 go [1];  f - E <= (Lf - A) + (A - U) + go <= V + 2 go [2];  in row -1 E^ is
+//      the -P sentinel, P - ge below A (global; P - 2 ge in overlap mode): d - E <= m + 2 ge + P - ge [3], f - E <= V + P - ge [4]
+//   R, Od  (fm - hg, en - hg with hg = h + gapo <= fm, en <= h):  go [5]
+//   * the row a jumping band starts from (Hp = -gape p, E^ = Hp + 2 ge one cell on) has steps of ge, and its first cell obeys the same clamp: E - d <= 2 ge - S~, d - E <= m,
+//     f - E <= max(P, m): all below the terms above.  The cell entering behind the band end (H^ = last + cfirst - gape, E^ = that - gape) is far BELOW its
+//     neighbours: as E of the new last cell it makes E - d negative, and M there has computed cells for A and Lf.
+//   * not covered, because a fix-up overwrites the flag and an insert touches its own bit only: M and D of lane 0's cell 0 at rbeg = 0 (and M of cell 0 keeps the
+//     saturating form everywhere: x_forward_abs), D of the cells whose upper neighbour is an entering cell and M of those whose diagonal predecessor is one (the
+//     `mov == 1 && last` bit and the md / mm masks of moves of two and more).
+// Inside bsa_align8_x_supported every term is at most 126: the third inequality (63 + 2 ge + n + m + 2 g <= 125) gives n <= 62 and m + go + ge + 63 <= 125, the first
+// m + 3 go + 2 ge <= 100; so there is one form of the inserts and the launcher has nothing to choose (tests/test_align8_flag_span_cpu.py walks a grid).
+uint32_t bsa_align8_flag_span(const Align8Args &a, int pw, uint32_t terms[BSA_FLAG_SPAN_TERMS]){
+	if(bsa_align8_abs_rows(a, pw) == 0u) return 0u;
+	const int go = -(int)(int8_t)a.gapo1, ge = -(int)(int8_t)a.gape1, m = a.smax, n = -a.smin, P = -BSA_EPI8_MIN;
+	static_assert(BSA_EPI8_MAX == -BSA_EPI8_MIN, "the first-cell rule's clamp and the sentinels are one figure here");
+	const int s1 = m + go + 2 * ge, V = std::max(s1, P + ge), lowS = std::max(n, P) - 2 * ge, hiS = m + 2 * ge;
+	const int t[BSA_FLAG_SPAN_TERMS] = {V + lowS, hiS + 2 * go, V + 2 * go, hiS + P - ge, V + P - ge, go};
+	if(terms) for(int k = 0; k < BSA_FLAG_SPAN_TERMS; k++) terms[k] = (uint32_t)std::max(t[k], 0);
+	return (uint32_t)std::max(*std::max_element(t, t + BSA_FLAG_SPAN_TERMS), 0);
 }
 
 // The launcher's BSA_ALIGN8_* knobs, each read here and nowhere else (BSA_ALIGN8_ABS and _ABS_R: bsa_align8_abs_rows); x_choose takes them anew at every launch.

@@ -967,6 +967,16 @@ extern "C" int bsa_align8_abs_form_internal(const bsa_align_params_t *par, uint3
 	return r == 0u ? 0 : m3 ? 2 : 1;
 }
 
+// bsa_align8_flag_span for a scoring at par->bandwidth, for tests of its bound; needs no device.  Returns the span (terms, if not null: the BSA_FLAG_SPAN_TERMS terms
+// it is the maximum of), 0 where the launcher keeps the difference form, -1 where the exact-arithmetic forward kernel does not take the scoring.
+extern "C" int bsa_align8_flag_span_internal(const bsa_align_params_t *par, uint32_t *terms){
+	if(!par) return -1;
+	const int pw = bsa_get_piecewise(par->gapo1, par->gape1, par->gapo2, par->gape2, (int)par->bandwidth);
+	const Align8Args t = align8_scoring_args(par, par->bandwidth, par->mode & 3);
+	if(pw > 1 || !bsa_align8_x_supported(t, pw)) return -1;
+	return (int)bsa_align8_flag_span(t, pw, terms);
+}
+
 // What bsa_launch_align8_fwd_x (score: ..._x_score) would launch for a chunk of `count` pairs of this scoring at par->bandwidth, targets of up to max_tlen rows, on a device of
 // `cus` CUs with a row-segment buffer of xq_bytes (0: none), under the BSA_ALIGN8_* knobs as they stand; needs no device.  out: the BSA_X_CHOICE_WORDS numbers of
 // bsa_align8_x_choice, the gap model and what bsa_align_run would size the buffer to (bsa_align8_xq_bytes); name: what the launch reports ("" = nothing).  1 = a launch, 0 = none

@@ -303,6 +303,8 @@ size_t bsa_align8_xq_bytes(uint32_t bw, int pw, uint32_t count);       // what A
 // what the two launchers above would launch for a chunk on a device of `cus` CUs, as plain numbers (bsa_align8_x.hip: x_choose; no device, for tests): form (0 none, 1 band in
 // place, 2 row segments, 3 whole pairs, 4 four- and eight-lane blocks), W, L, pw, do2, score, abs, m3, waves per SIMD, rebase rows, grid, segment groups, segments, rows a
 // segment, spin cap, rmask, control-block bytes, state bytes, n8, nb8
+#define BSA_FLAG_SPAN_TERMS 6
+uint32_t bsa_align8_flag_span(const Align8Args &a, int pw, uint32_t terms[BSA_FLAG_SPAN_TERMS] = nullptr);      // ... largest difference a one-bit flag insert of that form sees in a stored cell (exact up to 256); 0 = the difference form
 #define BSA_X_CHOICE_WORDS 20
 bool bsa_align8_x_choice(const Align8Args &a, int pw, bool score, int cus, uint64_t out[BSA_X_CHOICE_WORDS], const char **name);
 // whole-query bands above 256 columns, global mode: systolic wavefront + its own code layout and traceback (bsa_align8_sys.hip)
