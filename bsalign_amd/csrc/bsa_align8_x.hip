@@ -961,6 +961,8 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 // 0x8000 filler is no score; what leaves the scan is one) and the maxima of fm and En.  Lanes of dead pairs (tlen = 0) and of rows past a short target carry arbitrary
 // patterns, NaNs included, through the maxima: nothing they compute is stored, and nothing crosses from one pair's lanes into another's.
 // M3 = false keeps the integer recurrence above in the frame at 0, for the scorings whose bound does not fit the biased frame (bandwidth 256 only: bsa_align8_abs_rows).
+// ROWS THAT DO NOT MOVE BY ONE CELL are paid for by the whole wave, so their fix-ups have a constant form for the common cases (a move of two: one mask per flag in
+// the pair's last lane; a row that stays at rbeg > 0: the first cell's predecessor is fini's low half) and keep the general code for the wave that needs it.
 template<int L, int NWV, int PW = 1, bool DO2 = true, bool EXT = false, bool M3 = true>
 static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const uint32_t first_pos, const uint32_t count, const uint32_t tid_base, const uint32_t rmask,
 		const uint32_t row0 = 0u, const uint32_t row1 = 0xFFFFFFF8u, uint32_t *st = nullptr, uint32_t *ext_stage = nullptr, uint32_t *ext_qwin = nullptr){
@@ -1150,27 +1152,43 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		// ---- first cell of the band (bsalign.h:2899-2907), x_forward's rule with the scores made real: ubegs[0] = base + Hp[0] + gape (rbeg + i - 2)
 		const uint32_t d0s = x_add(Hp[0], S[0]);
 		uint32_t d0h = d0s;
-		uint32_t q0m = 0x10000u, q0d = 0x10000u;          // (never equal to a half)
+		// q0m and q0d are read by the fix-up of rbeg = 0 alone (behind pass 2), and every live row at rbeg = 0 sets them below: they start without a value, at no instruction
+		uint32_t q0m, q0d;
+		asm volatile("" : "=v"(q0m), "=v"(q0d));
+		const uint32_t fini = x_add(Hp[0], MINF16);
+		// (a row that stays, mov = 0, or whose band jumped; rbeg = 0 implies mov = 0 on that row, rbeg being the sum of the moves, so every live row at rbeg = 0 comes here)
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u) & actm) != 0ull, 0)){
-			int rh;
-			if(mov >= (uint32_t)BW) rh = rhj;
-			else if(rbeg) rh = BSA_SCORE_MIN;
-			else if(mode == BSA_MODE_OVERLAP || i == 0) rh = 0;
-			else rh = gapo1 + gape1 * (int)i;
 			const int hp0 = x_lo16(Hp[0]);
 			const int HBr = base + hp0 + GE * ((int)rbeg + (int)i - 2);
-			const int s0 = x_lo16(S[0]) + 2 * GE;
-			const int t0 = x_lo16(E[0]) - hp0 + 2 * GE;          // u + e
-			int hh = (rh - HBr) + s0;
-			hh = (hh >= t0) ? min(hh, BSA_EPI8_MAX) : BSA_EPI8_MIN;
-			if(first && (mov == 0u || mov >= (uint32_t)BW)) d0h = (d0s & 0xffff0000u) | ((uint32_t)(hp0 + hh - 2 * GE) & 0xffffu);
-			const int cm = rh - HBr + s0 - 2 * GE, cd = t0 + rh - HBr - 2 * GE;
-			q0m = (cm >= -128 && cm <= 127) ? ((uint32_t)(hp0 + cm) & 0xffffu) : 0x10000u;
-			q0d = (cd >= -128 && cd <= 127) ? ((uint32_t)(hp0 + cd) & 0xffffu) : 0x10000u;
+			// A ROW THAT STAYS AT rbeg > 0 has rh = SCORE_MIN, and then hh = (SCORE_MIN - HBr) + s0 with s0 <= 127 (a matrix entry or the pad score) while
+			// t0 = lo16(E[0]) - lo16(Hp[0]) + 2 gape > -2^17 (two int16 and |gape| <= 127).  So HBr > SCORE_MIN + 2^17 proves hh < t0 for the lane: hh becomes EPI8_MIN and
+			// the low half of d0h is Hp[0] + (EPI8_MIN - 2 gape), which is fini's.  The test is per lane and is the proof: a band that jumped has rebuilt base from
+			// SCORE_MIN, HBr is then near SCORE_MIN, the comparison can go either way, and such a lane takes the rule below as it stands.  A wave takes the rule whenever
+			// one of its live rows needs it: a jump, a row at rbeg = 0, a row that fails the test.
+			const bool near = mov == 0u && rbeg != 0u && HBr > BSA_SCORE_MIN + (1 << 17);
+			if((__builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u && !near) & actm) == 0ull){
+				if(first && mov == 0u) d0h = (d0s & 0xffff0000u) | (fini & 0xffffu);
+			} else {
+				int rh;
+				if(mov >= (uint32_t)BW) rh = rhj;
+				else if(rbeg) rh = BSA_SCORE_MIN;
+				else if(mode == BSA_MODE_OVERLAP || i == 0) rh = 0;
+				else rh = gapo1 + gape1 * (int)i;
+				const int s0 = x_lo16(S[0]) + 2 * GE;
+				const int t0 = x_lo16(E[0]) - hp0 + 2 * GE;          // u + e
+				int hh = (rh - HBr) + s0;
+				hh = (hh >= t0) ? min(hh, BSA_EPI8_MAX) : BSA_EPI8_MIN;
+				if(first && (mov == 0u || mov >= (uint32_t)BW)) d0h = (d0s & 0xffff0000u) | ((uint32_t)(hp0 + hh - 2 * GE) & 0xffffu);
+				// a wave whose rows all stay at rbeg > 0 does not form q0m and q0d
+				if((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull){
+					const int cm = rh - HBr + s0 - 2 * GE, cd = t0 + rh - HBr - 2 * GE;
+					q0m = (cm >= -128 && cm <= 127) ? ((uint32_t)(hp0 + cm) & 0xffffu) : 0x10000u;          // (0x10000: never equal to a half)
+					q0d = (cd >= -128 && cd <= 127) ? ((uint32_t)(hp0 + cd) & 0xffffu) : 0x10000u;
+				}
+			}
 		}
 		// ---- pass 1: F leaving every block when nothing but the sentinel enters it
 		uint32_t d[W], m[M3 ? 1 : W], mg[M3 ? 1 : W];
-		const uint32_t fini = x_add(Hp[0], MINF16);
 		uint32_t f = fini;
 		if constexpr (M3){
 			// (the opening is added once, behind the sixteen maxima)
@@ -1259,7 +1277,28 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 				} else accD[0] = (accD[0] & ~0x8000u) | ((hl == q0d) ? 0x8000u : 0u);
 			}
 		}
+		// Moves of two and more: the cells whose upper neighbour (D / Od) or diagonal predecessor (M) is an entering cell lose those flags.  GENERAL FORM, per lane,
+		// half hf and accumulator: block b = jl + L hf keeps D of its first nd = clamp(lim, 0, 16) cells and M of its first nm = clamp(lim + 1, 0, 16), with
+		// lim = BW - mov - 16 b.  BW = 32 L, so a block b <= 2 L - 2 has lim >= 32 - mov and the last block (jl = L - 1, hf = 1) has lim = 16 - mov.  For mov <= 2
+		// every block but the last keeps all (nd = nm = 16), and the last has
+		//     mov = 0: nd = 16, nm = 16: nothing;     mov = 1: nd = 15, nm = 16;     mov = 2: nd = 14, nm = 15
+		// which touches its second accumulator of eight alone (cd = nd - 8, cm = nm - 8; the first has cd = cm = 8: empty masks), in the high half:
+		//     md = ((1 << (8 - cd)) - 1) << 24 = 0x01000000 (mov = 1), 0x03000000 (mov = 2);     mm = ((1 << (8 - cm)) - 1) << 24 = 0 (mov = 1), 0x01000000 (mov = 2)
+		// and of the two-bit fields the fourth accumulator of four alone (c0 = nd - 12 = 3, 2; the others have c0 = 4: 0x55 & 0 = 0):
+		//     (0x55 & ((1 << (8 - 2 c0)) - 1)) << 16 = 0x00010000 (mov = 1), 0x00050000 (mov = 2)
+		// for L = 4 and L = 8 alike.  mov = 1 is what the branch below for rows without a move of two does.  So while no live pair of the wave moved by more than
+		// two, the CONSTANT FORM does the general form's work with one mask per flag, chosen by mov in the pair's last lane; a wave with a live move of three and
+		// more takes the general form for all its pairs.  (Rows past a short target may carry any mov into either form: nothing of theirs is stored.)
 		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov > 1u) & actm) != 0ull, 0)){
+			if((__builtin_amdgcn_ballot_w64(mov > 2u) & actm) == 0ull){
+				const bool l1 = last && mov == 1u, l2 = last && mov == 2u;
+				accM[NACC - 1] &= ~(l2 ? 0x01000000u : 0u);
+				if constexpr (DO2){
+					const uint32_t t = accDO[NDO - 1];
+					const uint32_t z = ~(t | (t >> 1)) & (l2 ? 0x00050000u : l1 ? 0x00010000u : 0u);
+					accDO[NDO - 1] = t | (z << (DOSP - 1u));          // z * DOSP, DOSP being 1 or 2
+				} else accD[NACC - 1] &= ~(l2 ? 0x03000000u : l1 ? 0x01000000u : 0u);
+			} else {
 #pragma unroll
 			for(int hf = 0; hf < 2; hf++){
 				const int lim = BW - (int)mov - (jl + L * hf) * W;
@@ -1279,6 +1318,7 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 					if(mov != 0u) accDO[n] |= z * DOSP;
 				}
 				}
+			}
 			}
 		} else if constexpr (DO2){
 			const uint32_t t = accDO[NDO - 1];
