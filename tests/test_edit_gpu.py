@@ -64,7 +64,8 @@ def test_rows_tiled_eight_at_a_time(ctx, mode, bw, monkeypatch):
     """row format 1 (round 6; bsa_common.h): k_edit_fwd_grp32 writes a pair's rows eight to a tile, a 64-byte block per 32-bit column word, and
     k_edit_trace_wave fetches three dwords per plane and row around the walk's diagonal.  Pairs that stay on the diagonal, pairs whose indels
     carry the path across the band (the window misses: the literal lookups), rows that end a tile and targets of 1 .. 17 rows; the oracle's
-    result, and the same bytes as format 0 (BSA_EDIT_TILED=0)"""
+    result, and the same bytes as format 0 (BSA_EDIT_TILED=0).  (Window misses on purpose -- runs of up to 100 columns at every tile phase -- are in
+    walk_cases.py / test_walk_corpus_gpu.py; here they come from accumulated drift.)"""
     rng = np.random.default_rng(600 + bw + mode)
     pairs = [_mk(rng, int(rng.choice([300, 700, 1500, 3000, 6000])), float(rng.choice([0.0, 0.01, 0.1, 0.2, 0.35])), float(rng.choice([1.0, 1.0, 0.97, 1.03])))
              for _ in range(80)]
