@@ -163,6 +163,9 @@ def lib():
             L.bsa_edit_plan_cells.argtypes = [vp]
             L.bsa_edit_plan_cells.restype = C.c_double
             L.bsa_edit_run.argtypes = [vp, u8p, vp, u32p, C.c_size_t, u64p, u32p]
+        if hasattr(L, "bsa_edit_choice_internal"):
+            L.bsa_edit_choice_internal.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_size_t]
         L.bsa_kmer_edit_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
                                           vp, u32p, C.c_size_t, u64p, u32p]
         L.bsa_kmer_edit_batch2.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
@@ -267,6 +270,26 @@ def align8_x_choice(par, count, max_tlen, static_band=False, code_fmt=0, score=F
         raise ValueError("bsa_align8_x_choice_internal: bad arguments")
     d = dict(zip(X_CHOICE_FIELDS, (int(v) for v in out)))
     d.update(name=name.value.decode(), launch=rc == 1)
+    return d
+
+
+EDIT_CHOICE_FIELDS = tuple("fwd%d_%s" % (i, f) for i in (0, 1) for f in ("form", "n", "tiled", "track", "lanes", "grid", "block")) \
+    + ("trace_form", "trace_tiled", "trace_lanes", "trace_grid", "row_fmt")
+E_NONE, E_REG, E_GRP, E_GRP32, E_WIDE, E_GEN = range(6)
+T_NONE, T_WAVE, T_PLAIN, T_COOP = range(4)
+
+
+def edit_choice(bw, wide, count, mode=MODE_GLOBAL, bandwidth=0, score=False, alone=True, cus=256, occ_plain=8, occ_coop=8):
+    """what the edit launchers would launch for a launch class of `count` pairs (edit_choose; host only, under the BSA_EDIT_* knobs as they stand): a band of bw
+    columns, or bw 0 and the class's words per lane `wide`; alone: the class fills its chunk; occ_plain / occ_coop: the waves of k_edit_trace<false> / <true> a
+    CU keeps.  A dict of EDIT_CHOICE_FIELDS (fwd1_*: the generic kernel beside the wave-per-pair one) plus "fwd_name", "trace_name" and "launch"."""
+    out = (C.c_uint64 * len(EDIT_CHOICE_FIELDS))()
+    fwd, trace = C.create_string_buffer(200), C.create_string_buffer(200)
+    rc = lib().bsa_edit_choice_internal(bw, wide, count, mode, bandwidth, int(score), int(alone), cus, occ_plain, occ_coop, out, fwd, trace, 200)
+    if rc < 0:
+        raise ValueError("bsa_edit_choice_internal: bad arguments")
+    d = dict(zip(EDIT_CHOICE_FIELDS, (int(v) for v in out)))
+    d.update(fwd_name=fwd.value.decode(), trace_name=trace.value.decode(), launch=rc == 1)
     return d
 
 

@@ -1605,14 +1605,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPS))) 
 		if(threadIdx.x == 0u) __hip_atomic_fetch_max(done, s + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (max: a successor that gave up may have written s + 2)
 	}
 }
-static int x_cus(){
-	static const int cus = [](){
-		int dev = 0, v = 0;
-		if(hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-		return v;
-	}();
-	return cus;
-}
 // THE SHAPE RULE: cells per lane and half W and lanes per pair L of the kernels of a bandwidth and a gap model (2 W L = bw); false: there are none.  One-piece and
 // linear gaps: 64 <8, 4>, 128 <16, 4>, 256 <16, 8>; two-piece gaps keep eight cells a half at 128: <8, 8>.  x_choose leaves it in two places, both behind a knob or
 // a check of their own: BSA_ALIGN8_X_LANES=8 runs <4, 8> at 64 (whole pairs only), and two-piece row segments at 128 run <16, 4> (unless BSA_ALIGN8_X2_LANES=8).
@@ -1927,7 +1919,7 @@ static hipError_t x_run(const XLaunch &l, const Align8Args &a, hipStream_t st){
 }
 static hipError_t x_launch(const Align8Args &a, int pw, bool score, hipStream_t st){
 	if(a.count == 0) return hipSuccess;
-	const XLaunch l = x_choose(a, pw, score, x_cus());
+	const XLaunch l = x_choose(a, pw, score, bsa_cus());
 	return l.form == X_NONE ? hipErrorInvalidValue : x_run(l, a, st);
 }
 // Called once per chunk; chunks of one run may choose differently, and bsa_last_fwd_kernel is left by the last one that names its launch

@@ -1749,6 +1749,21 @@ struct bsa_edit_plan : PlanBase {
 extern "C" void bsa_edit_plan_destroy(bsa_edit_plan_t *p){ plan_free(p); }
 extern "C" double bsa_edit_plan_cells(const bsa_edit_plan_t *p){ return p ? p->cells : 0.0; }
 
+// What bsa_launch_edit_fwd and bsa_launch_edit_trace would launch for a launch class of `count` pairs -- a band of bw columns (64 .. 1024 in steps of 64), or bw 0 and the
+// class's words per lane `wide` (0, 1, 2, 4, 8) -- in `mode` with the caller's `bandwidth`, score only or not, filling its chunk alone or not, on a device of `cus` CUs that
+// keeps occ_plain / occ_coop waves of k_edit_trace<false> / <true> on a CU, under the BSA_EDIT_* knobs as they stand; needs no device.  out: the BSA_EDIT_CHOICE_WORDS
+// numbers of bsa_edit_choice.  1 = a forward launch, 0 = none (the launcher returns hipErrorInvalidValue), -1 = bad arguments.
+extern "C" int bsa_edit_choice_internal(uint32_t bw, uint32_t wide, uint32_t count, int mode, uint32_t bandwidth, int score, int alone, int cus, int occ_plain, int occ_coop,
+		uint64_t *out, char *fwd_name, char *trace_name, size_t name_cap){
+	const bool wide_ok = wide == 0u || wide == 1u || wide == 2u || wide == 4u || wide == 8u;
+	if(!out || !fwd_name || !trace_name || !name_cap || count == 0u || cus <= 0 || occ_plain <= 0 || occ_coop <= 0 || (mode & 3) == 3) return -1;
+	if(bw ? (!bsa_edit_supported_bw(bw) || bw > BSA_EDIT_REG_BW || wide != 0u) : !wide_ok) return -1;
+	const char *fn = nullptr, *tn = nullptr;
+	const bool ok = bsa_edit_choice(bw, wide, count, mode, bandwidth, score != 0, alone != 0, cus, occ_plain, occ_coop, out, &fn, &tn);
+	snprintf(fwd_name, name_cap, "%s", fn ? fn : ""); snprintf(trace_name, name_cap, "%s", tn ? tn : "");
+	return ok ? 1 : 0;
+}
+
 extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const uint32_t *qlen,
 		const uint64_t *toff, const uint32_t *tlen, size_t n, const bsa_edit_params_t *par, bsa_edit_plan_t **out){
 	if(!c || !out || !par || (n && (!qoff || !qlen || !toff || !tlen))) return BSA_E_ARG;
@@ -1819,8 +1834,8 @@ extern "C" int bsa_edit_plan_create(bsa_ctx_t *c, const uint64_t *qoff, const ui
 	for(size_t pos = 0; pos < n; pos++){
 		const uint32_t k = order[pos];
 		bwv[pos] = cls[k];
-		// (score only: the pairs k_edit_fwd_gen takes -- wide classes it has to itself, moving wide bands -- keep two rows, bsa_launch_edit_fwd)
-		const bool gen = cls[k] > BSA_EDIT_REG_BW && ((cls[k] & 0xFFu) == 0u || bwk[k] != (qlen[k] + 63u) / 64u * 64u);
+		// (score only: the pairs k_edit_fwd_gen takes keep two rows)
+		const bool gen = cls[k] > BSA_EDIT_REG_BW && bsa_edit_gen_takes(cls[k] & 0xFFu, bwk[k] != (qlen[k] + 63u) / 64u * 64u);
 		need[pos] = p->score_fast ? bsa_edit_score_rec_bytes(bwk[k], gen) : ((size_t)tlen[k] + 1 + p->pad_rows) * (size_t)(bwk[k] / 64u) * 16;
 	}
 	int rc = plan_chunks(p, order, need, bwv, slot, slot_end, true);
@@ -1867,22 +1882,33 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	a.status = status; a.fwd_sbeg = p->d_sbeg; a.fwd_smin = p->d_sbeg + n; a.fwd_ry = p->d_sbeg + 2 * (size_t)n; a.pad_rows = p->pad_rows; a.mode = p->par.mode; a.bandwidth = p->par.bandwidth;
 	a.score = p->score_fast ? 1u : 0u;
 	uint32_t *cnt = p->d_cnt_pos;
+	// The launches are chosen here, once (bsa_edit.hip: edit_choose): a forward launch for every class, and for every chunk the traceback and the row format that
+	// its forward and traceback launches share -- those of its class where one class fills it alone, else chosen for the chunk, in row format 0
+	auto class_args = [&](uint32_t first, uint32_t count, uint32_t cls){
+		EditArgs b = a; b.first = first; b.count = count;
+		b.bw = cls <= BSA_EDIT_REG_BW ? cls : 0u;               // several classes or wide bands: every pair works out its own
+		return b;
+	};
+	auto sub_args = [&](const Sub &sb){ EditArgs b = class_args(sb.first, sb.count, sb.bw); b.wide = b.bw ? 0u : (sb.bw & 0xFFu); return b; };
+	std::vector<EditChoice> of_sub(p->subs.size()), of_chunk(p->chunks.size());
+	for(size_t k = 0; k < p->chunks.size(); k++){
+		const Chunk &ch = p->chunks[k];
+		const bool alone = ch.nsub == 1u && p->subs[ch.sub0].count == ch.count && p->subs[ch.sub0].bw == ch.bw;
+		for(uint32_t x = ch.sub0; x < ch.sub0 + ch.nsub; x++) of_sub[x] = bsa_edit_choose(sub_args(p->subs[x]), alone);
+		of_chunk[k] = alone ? of_sub[ch.sub0] : bsa_edit_choose(class_args(ch.first, ch.count, ch.bw), false);
+	}
 	auto fwd = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
 		for(uint32_t x = ch.sub0; x < ch.sub0 + ch.nsub; x++){      // one forward launch per class
-			const Sub &sb = p->subs[x];
-			EditArgs b = a; b.first = sb.first; b.count = sb.count; b.rows = half;
-			b.bw = sb.bw <= BSA_EDIT_REG_BW ? sb.bw : 0u; b.wide = sb.bw <= BSA_EDIT_REG_BW ? 0u : (sb.bw & 0xFFu);
-			b.row_fmt = (!p->score_fast && ch.nsub == 1u && sb.count == ch.count && ch.bw == sb.bw && bsa_edit_tiled_ok(b.bw, ch.count, b.mode)) ? 1u : 0u;
-			HIPCHK(c, bsa_launch_edit_fwd(b, s));
+			EditArgs b = sub_args(p->subs[x]); b.rows = half; b.row_fmt = of_sub[x].row_fmt;
+			HIPCHK(c, bsa_launch_edit_fwd(b, of_sub[x], s));
 		}
 		return BSA_OK;
 	};
 	auto trace = [&](const Chunk &ch, uint8_t *half, hipStream_t s) -> int {
-		EditArgs b = a; b.first = ch.first; b.count = ch.count; b.rows = half;
-		b.bw = ch.bw <= BSA_EDIT_REG_BW ? ch.bw : 0u;               // several classes or wide bands: every pair works out its own
+		const EditChoice &ec = of_chunk[&ch - p->chunks.data()];
+		EditArgs b = class_args(ch.first, ch.count, ch.bw); b.rows = half; b.row_fmt = ec.row_fmt;
 		if(p->score_fast){ HIPCHK(c, bsa_launch_edit_score_finish(b, d_out, s)); return BSA_OK; }
-		b.row_fmt = (ch.nsub == 1u && p->subs[ch.sub0].count == ch.count && p->subs[ch.sub0].bw == ch.bw && bsa_edit_tiled_ok(b.bw, ch.count, b.mode)) ? 1u : 0u;      // (the same test as the forward launch of this chunk)
-		HIPCHK(c, bsa_launch_edit_trace(b, d_out, cnt, s));
+		HIPCHK(c, bsa_launch_edit_trace(b, ec, d_out, cnt, s));
 		return BSA_OK;
 	};
 	bsa_last_fwd_kernel = bsa_last_trace_kernel = nullptr;

@@ -9,6 +9,12 @@
 // getenv on the launch path).  bsa_env_reload() takes a new snapshot (tests that flip a knob inside one process call it).
 const char *bsa_env(const char *name);
 extern "C" void bsa_env_reload(void);
+// compute units of the current device, for the launchers that size a launch by them (256 where the device does not say)
+static inline int bsa_cus(){
+	int dev = 0, v = 0;
+	if(hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+	return v;
+}
 
 #define BSA_LANES      16                      // running blocks per band row == lanes of one DPP row
 #define BSA_EPI8_MIN   (-63)                   // bsalign.h:56
@@ -314,13 +320,31 @@ hipError_t bsa_launch_align8_fwd_sys(const Align8Args &a, int pw, uint32_t max_q
 hipError_t bsa_launch_align8_trace_sys(const Align8Args &a, int pw, bsa_result_t *out, uint32_t *cig_cnt, const uint64_t *slot_end, hipStream_t st);
 hipError_t bsa_launch_align8_trace_codes(const Align8Args &a, int pw, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
 bool bsa_edit_supported_bw(uint32_t bw);
-bool bsa_edit_tiled_ok(uint32_t bw, uint32_t count, int mode);       // row format 1 for a launch class that fills its chunk alone (bsa_edit.hip)
+// k_edit_fwd_gen's pairs in a class above BSA_EDIT_REG_BW (`wide`: the class's words per lane of the wave-per-pair kernel): all of them where that kernel has no
+// form (wide 0), else those whose band moves -- in global mode with a bandwidth, nowhere else.  The plan sizes score-only records by it, the launcher launches by it.
+static inline bool bsa_edit_gen_takes(uint32_t wide, bool moving){ return wide == 0u || moving; }
+// WHAT THE EDIT LAUNCHERS LAUNCH for one launch class (bsa_edit.hip: edit_choose decides it once, the two launchers below run it).  fwd: the forward launch, or the
+// wave-per-pair and the generic kernel side by side; trace: the traceback of a class that fills its chunk alone, or of a chunk of several classes (chosen with bw 0).
+enum EForm : uint32_t { E_NONE, E_REG, E_GRP, E_GRP32, E_WIDE, E_GEN };          // k_edit_fwd<n = NW>, k_edit_fwd_grp<n = G>, k_edit_fwd_grp32<n = G>, k_edit_fwd_wide<n = WPL>, k_edit_fwd_gen
+enum ETrace : uint32_t { T_NONE, T_WAVE, T_PLAIN, T_COOP };                       // k_edit_trace_wave, k_edit_trace<false>, k_edit_trace<true>
+struct EditChoice {
+	struct { EForm form; uint32_t n; bool tiled, track; uint32_t lanes, grid, block; } fwd[2];          // lanes: pairs per wave where the kernel takes the figure (E_REG, E_GEN)
+	struct { ETrace form; bool tiled; uint32_t lanes, grid; } trace;                                    // lanes: walks per wave (T_WAVE: 1)
+	bool score; uint32_t row_fmt;                 // the forward kernels' SCORE forms; EditArgs::row_fmt of both launches: 1 = the tiled k_edit_fwd_grp32 writes, the tiled k_edit_trace_wave reads
+	const char *fwd_name, *trace_name;            // for bsa_last_fwd_kernel / bsa_last_trace_kernel
+};
+EditChoice bsa_edit_choose(const EditArgs &a, bool alone);          // a's class (bw, wide, count, mode, bandwidth, score) on the current device; alone: it fills its chunk
+#define BSA_EDIT_CHOICE_WORDS 19
+// edit_choose as plain numbers on a device of `cus` CUs that keeps occ_plain / occ_coop waves of k_edit_trace<false> / <true> on a CU (no device, for tests): of fwd[0]
+// and fwd[1] form, n, tiled, track, lanes, grid, block; of trace form, tiled, lanes, grid; row_fmt.  false = no forward launch
+bool bsa_edit_choice(uint32_t bw, uint32_t wide, uint32_t count, int mode, uint32_t bandwidth, bool score, bool alone, int cus, int occ_plain, int occ_coop,
+		uint64_t out[BSA_EDIT_CHOICE_WORDS], const char **fwd_name, const char **trace_name);
 hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
 		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit = false,       // seq2bit: BSA_MODE_SEQ2BIT words
 		bool qstrand = false);                                                                                          // qstrand: BSA_MODE_QSTRAND, bit 63 of qoff[k] asks for the reverse complement
-hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st);
-hipError_t bsa_launch_edit_trace(const EditArgs &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
+hipError_t bsa_launch_edit_fwd(const EditArgs &a, const EditChoice &c, hipStream_t st);
+hipError_t bsa_launch_edit_trace(const EditArgs &a, const EditChoice &c, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
 hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st);        // BSA_MODE_SCORE_ONLY: records -> results
 // BSA_MODE_CIGAR_EQX (bsa_cigar_eqx.hip): the pass that splits M words into = / X runs on their way out of the slots.  What it needs of a plan:
 // the staged 1 B/base copies and their offsets and lengths by pair, the processing order, the result records (qb / tb seed the walk)

@@ -1486,128 +1486,146 @@ bool bsa_edit_supported_bw(uint32_t bw){       // register kernels up to 16 word
 	return bw >= 64 && (bw % 64) == 0;
 }
 
+// Every launch of this file is one row of a switch over a packed key, one row macro per kernel wrapper (a key written twice does not compile; a description without
+// a row launches nothing and is hipErrorInvalidValue).  The staging kernels: keyed by the blob's format, the threads per pair and QS.
+constexpr uint32_t stage_key(bool seq2bit, uint32_t tpp, bool qs){ return (uint32_t)seq2bit | (uint32_t)qs << 1 | tpp << 2; }
+#define E_STAGE_ARGS qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n
+#define E_STAGE_K(TPP, QS) case stage_key(false, TPP, QS): hipLaunchKernelGGL((k_edit_stage<TPP, QS>), grid, dim3(256), 0, st, seqs, E_STAGE_ARGS); break;
+#define E_STAGE2B_K(TPP, QS) case stage_key(true, TPP, QS): hipLaunchKernelGGL((k_edit_stage2b<TPP, QS>), grid, dim3(256), 0, st, (const uint64_t*)seqs, E_STAGE_ARGS); break;
 hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
 		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
 		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit, bool qstrand){
 	if(n == 0) return hipSuccess;
 	// a wave per pair from 65 536 pairs on, a block below; the QS instantiations only for plans with BSA_MODE_QSTRAND
-	const bool wave = n >= 65536u;
-	const dim3 grid(wave ? (n + 3u) / 4u : n);
-#define BSA_ESTAGE(K, SEQS) hipLaunchKernelGGL(K, grid, dim3(256), 0, st, SEQS, qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n)
-	if(seq2bit){
-		const uint64_t *w = (const uint64_t*)seqs;
-		if(qstrand){ if(wave) BSA_ESTAGE((k_edit_stage2b<64, true>), w); else BSA_ESTAGE((k_edit_stage2b<256, true>), w); }
-		else if(wave) BSA_ESTAGE(k_edit_stage2b<64>, w); else BSA_ESTAGE(k_edit_stage2b<256>, w);
-	} else {
-		if(qstrand){ if(wave) BSA_ESTAGE((k_edit_stage<64, true>), seqs); else BSA_ESTAGE((k_edit_stage<256, true>), seqs); }
-		else if(wave) BSA_ESTAGE(k_edit_stage<64>, seqs); else BSA_ESTAGE(k_edit_stage<256>, seqs);
+	const uint32_t tpp = n >= 65536u ? 64u : 256u;
+	const dim3 grid(tpp == 64u ? (n + 3u) / 4u : n);
+	switch(stage_key(seq2bit, tpp, qstrand)){
+		E_STAGE_K(64, false) E_STAGE_K(256, false) E_STAGE_K(64, true) E_STAGE_K(256, true)
+		E_STAGE2B_K(64, false) E_STAGE2B_K(256, false) E_STAGE2B_K(64, true) E_STAGE2B_K(256, true)
+		default: return hipErrorInvalidValue;
 	}
-#undef BSA_ESTAGE
 	return hipGetLastError();
 }
 
-// Row format 1 (tiled, bsa_common.h) is a contract between ONE forward kernel and ONE traceback kernel: k_edit_fwd_grp32 and k_edit_trace_wave.  It is
-// taken for a launch class that both launchers below give to exactly those two -- a band of 64 / 128 / 256 columns, few enough pairs for a walk per
-// wave -- and that fills a chunk alone (bsa_edit_run sets EditArgs::row_fmt from this for the forward and the traceback launch of the chunk alike).
-// BSA_EDIT_TILED=0 keeps format 0; any of the kernel-choice knobs does as well.
-bool bsa_edit_tiled_ok(uint32_t bw, uint32_t count, int mode){
-	(void)mode;
-	const char *te = bsa_env("BSA_EDIT_TILED");
-	if(te && te[0] == '0') return false;
-	if(bsa_env("BSA_EDIT_GRP") || bsa_env("BSA_EDIT_GRP32") || bsa_env("BSA_EDIT_TRACE_WAVE") || bsa_env("BSA_EDIT_TRACE_LANES") || bsa_env("BSA_EDIT_TRACE_COOP") || bsa_env("BSA_EDIT_FWD_LANES")) return false;
+// The launchers' BSA_EDIT_* knobs, each read here and nowhere else (BSA_EDIT_NO_MERGE is the plan's, bsa_api.hip); edit_choose takes them anew for every choice.
+struct EditKnobs {
+	int tiled, grp, grp32, wave, coop;          // first character of _TILED, _GRP, _GRP32, _TRACE_WAVE, _TRACE_COOP; -1: not set
+	int fwd_lanes, gen_lanes, trace_lanes;      // _FWD_LANES, _GEN_LANES: 1..64, _TRACE_LANES: a power of two of those; 0: set to something else, -1: not set
+	EditKnobs(){
+		auto first = [](const char *name){ const char *e = bsa_env(name); return e ? (int)(unsigned char)e[0] : -1; };
+		auto lanes = [](const char *name){ const char *e = bsa_env(name); const int v = e ? atoi(e) : -1; return !e ? -1 : v >= 1 && v <= 64 ? v : 0; };
+		tiled = first("BSA_EDIT_TILED"); grp = first("BSA_EDIT_GRP"); grp32 = first("BSA_EDIT_GRP32"); wave = first("BSA_EDIT_TRACE_WAVE"); coop = first("BSA_EDIT_TRACE_COOP");
+		fwd_lanes = lanes("BSA_EDIT_FWD_LANES"); gen_lanes = lanes("BSA_EDIT_GEN_LANES"); trace_lanes = lanes("BSA_EDIT_TRACE_LANES");
+		if(trace_lanes > 0 && (trace_lanes & (trace_lanes - 1))) trace_lanes = 0;
+	}
+	bool chooses_kernel() const { return grp >= 0 || grp32 >= 0 || wave >= 0 || coop >= 0 || fwd_lanes >= 0 || trace_lanes >= 0; }          // (each of these keeps row format 0)
+};
+// The name of a forward launch, by its first kernel's form.  Kept as the launch sites had them, so some misdescribe their kernel (HISTORY §18 has the list).
+static const char *edit_fwd_name(EForm form, bool tiled, bool score){
+	switch(form){
+		case E_GRP32: return score ? "k_edit_fwd_grp32 score-only (forward DP, 32-bit words, 2 NW lanes per pair, last row only)"
+			: tiled ? "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair, rows tiled eight at a time)" : "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair)";
+		case E_GRP: return score ? "k_edit_fwd_grp score-only (forward DP, NW lanes per pair, last row only)" : "k_edit_fwd_grp (forward DP, NW lanes per pair)";
+		case E_REG: return score ? "k_edit_fwd score-only (forward DP, one pair per lane, last row only)" : "k_edit_fwd (forward DP, one pair per lane)";
+		default: return score ? "k_edit_fwd_wide / k_edit_fwd_gen score-only (forward DP, bands above 1024 columns, last row only)" : "k_edit_fwd_wide / k_edit_fwd_gen (forward DP, bands above 1024 columns)";
+	}
+}
+// What to launch for a launch class of count > 0 pairs: a band of bw columns (a multiple of 64 up to 1024), or bw 0 and the words per lane `wide` of the wave-per-pair
+// kernel (1, 2, 4, 8; 0: none); alone: the class fills its chunk; cus, occ_plain, occ_coop: the device's CUs and the waves of k_edit_trace<false> / <true> one keeps
+// resident.  No HIP call.  In order: the forward form, the traceback form, then the row format that the two share.
+static EditChoice edit_choose(uint32_t bw, uint32_t wide, uint32_t count, int mode, uint32_t bandwidth, bool score, bool alone, int cus, int occ_plain, int occ_coop){
+	const EditKnobs k;
+	EditChoice c{}; c.score = score;
 	const uint32_t nw = bw / 64u;
-	if(!(bw == 64u || bw == 128u || bw == 256u) || count == 0u) return false;
-	const uint32_t G32 = nw <= 1u ? 2u : nw <= 2u ? 4u : 8u;
-	if((uint64_t)count * G32 / 64u > 65536u) return false;                          // k_edit_fwd_grp32's own condition
-	int dev = 0, cus = 256;
-	if(hipGetDevice(&dev) == hipSuccess){ int v = 0; if(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-	return count <= 8u * (uint32_t)cus * 32u;                                         // k_edit_trace_wave's (narrow bands)
-}
-
-// SCORE: the score-only forms (EditArgs::score), same dispatch; the kernel names say which
-template<bool SCORE>
-static hipError_t launch_edit_fwd(const EditArgs &a, hipStream_t st){
-	// pairs per wave of the register kernels (BSA_EDIT_FWD_LANES overrides, for measurements).  64 is best: a wave's time
-	// is its own serial chain (~600 instructions per row of 64-bit funnel shifts and block updates) whatever its lane
-	// count -- 16384 pairs x 100 kbp, ms per launch: 64 lanes 102, 32 -> 104, 16 -> 136, 8 -> 261, 4 -> 374
-	uint32_t lanes = 64;
-	if(const char *e = bsa_env("BSA_EDIT_FWD_LANES")){ const int v = atoi(e); if(v >= 1 && v <= 64) lanes = (uint32_t)v; }
-	const uint32_t fblocks = (a.count + lanes - 1) / lanes;
-#define EDIT_CASE(N) case N: if(track) hipLaunchKernelGGL((k_edit_fwd<N, true, SCORE>), dim3(fblocks), dim3(64), 0, st, a, lanes); \
-		else hipLaunchKernelGGL((k_edit_fwd<N, false, SCORE>), dim3(fblocks), dim3(64), 0, st, a, lanes); break;
-	const bool track = (a.mode & 3) != BSA_MODE_GLOBAL;
-	// few pairs: G lanes per pair (waves stay few, every row is a third of the serial chain); many pairs: one per lane
-	{
-		const uint32_t nw = a.bw / 64u;
-		const uint32_t G = nw <= 2u ? 2u : nw <= 4u ? 4u : nw <= 8u ? 8u : 16u;
-		bool grp = a.bw != 0u && nw >= 2u && nw <= 16u && (uint64_t)a.count * G / 64u <= 4096u;
-		if(const char *e = bsa_env("BSA_EDIT_GRP")) grp = a.bw != 0u && nw >= 2u && nw <= 16u && e[0] == '1';
-		// 32-bit words, twice the lanes per pair (bands up to 512 columns): BSA_EDIT_GRP32=0/1 overrides
-		{
-			const uint32_t G32 = nw <= 1u ? 2u : nw <= 2u ? 4u : nw <= 4u ? 8u : 16u;
-			bool g32 = a.bw != 0u && nw >= 1u && nw <= 8u && (uint64_t)a.count * G32 / 64u <= 65536u;      // (faster than the other two kernels on every shape of tools/edit_shapes.sh)
-			if(const char *e = bsa_env("BSA_EDIT_GRP32")) g32 = a.bw != 0u && nw >= 1u && nw <= 8u && e[0] == '1';
-			if(bsa_env("BSA_EDIT_GRP")) g32 = false;
-			if(g32){
-				bsa_last_fwd_kernel = SCORE ? "k_edit_fwd_grp32 score-only (forward DP, 32-bit words, 2 NW lanes per pair, last row only)"
-					: "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair)";
-				const uint32_t ppw = 64u / G32, gblocks = ((a.count + ppw - 1) / ppw + 3) / 4;
-				if(!SCORE && a.row_fmt == 1u){
-					bsa_last_fwd_kernel = "k_edit_fwd_grp32 (forward DP, 32-bit words, 2 NW lanes per pair, rows tiled eight at a time)";
-					switch(G32){
-						case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-						case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-						default: hipLaunchKernelGGL((k_edit_fwd_grp32<8, true, false>), dim3(gblocks), dim3(256), 0, st, a); break;
-					}
-					return hipGetLastError();
-				}
-				switch(G32){
-					case 2: hipLaunchKernelGGL((k_edit_fwd_grp32<2, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-					case 4: hipLaunchKernelGGL((k_edit_fwd_grp32<4, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-					case 8: hipLaunchKernelGGL((k_edit_fwd_grp32<8, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-					default: hipLaunchKernelGGL((k_edit_fwd_grp32<16, false, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-				}
-				return hipGetLastError();
-			}
-		}
-		if(grp){
-			bsa_last_fwd_kernel = SCORE ? "k_edit_fwd_grp score-only (forward DP, NW lanes per pair, last row only)" : "k_edit_fwd_grp (forward DP, NW lanes per pair)";
-			const uint32_t ppw = 64u / G, gblocks = ((a.count + ppw - 1) / ppw + 3) / 4;
-			switch(G){
-				case 2: hipLaunchKernelGGL((k_edit_fwd_grp<2, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-				case 4: hipLaunchKernelGGL((k_edit_fwd_grp<4, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-				case 8: hipLaunchKernelGGL((k_edit_fwd_grp<8, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-				default: hipLaunchKernelGGL((k_edit_fwd_grp<16, SCORE>), dim3(gblocks), dim3(256), 0, st, a); break;
-			}
-			return hipGetLastError();
+	const bool global = (mode & 3) == BSA_MODE_GLOBAL;
+	auto &f = c.fwd[0];
+	// few pairs: G lanes per pair (waves stay few, every row is a third of the serial chain), in 32-bit words twice as many (bands up to 512 columns: faster than
+	// the other two kernels on every shape of tools/edit_shapes.sh); many pairs: one per lane.  BSA_EDIT_GRP32=0/1 and BSA_EDIT_GRP=0/1 override, the latter rules grp32 out
+	const uint32_t G = nw <= 2u ? 2u : nw <= 4u ? 4u : nw <= 8u ? 8u : 16u, G32 = nw <= 1u ? 2u : nw <= 2u ? 4u : nw <= 4u ? 8u : 16u;
+	const bool g32 = k.grp < 0 && nw >= 1u && nw <= 8u && (k.grp32 >= 0 ? k.grp32 == '1' : (uint64_t)count * G32 / 64u <= 65536u);
+	const bool grp = nw >= 2u && nw <= 16u && (k.grp >= 0 ? k.grp == '1' : (uint64_t)count * G / 64u <= 4096u);
+	if(g32 || grp){
+		f.form = g32 ? E_GRP32 : E_GRP; f.n = g32 ? G32 : G; f.block = 256u;
+		f.grid = ((count + 64u / f.n - 1u) / (64u / f.n) + 3u) / 4u;
+	} else if(bw != 0u){
+		// pairs per wave of the register kernels (BSA_EDIT_FWD_LANES overrides, for measurements).  64 is best: a wave's time is its own serial chain (~600
+		// instructions per row of 64-bit funnel shifts and block updates) whatever its lane count -- 16384 pairs x 100 kbp, ms per launch: 64 lanes 102, 32 -> 104,
+		// 16 -> 136, 8 -> 261, 4 -> 374
+		f.form = E_REG; f.n = nw; f.track = !global; f.lanes = k.fwd_lanes > 0 ? (uint32_t)k.fwd_lanes : 64u; f.block = 64u; f.grid = (count + f.lanes - 1u) / f.lanes;
+	} else {
+		// bands above 1024: static ones (overlap / extend / bandwidth 0) one pair per wave, the rest one pair per lane
+		auto *g = &f;
+		if(wide == 1u || wide == 2u || wide == 4u || wide == 8u){ f.form = E_WIDE; f.n = wide; f.block = 256u; f.grid = (count + 3u) / 4u; g = &c.fwd[1]; }
+		if(bsa_edit_gen_takes(wide, global && bandwidth != 0u)){
+			uint32_t gl = 64;
+			while(gl > 2u && (count + gl / 2 - 1) / (gl / 2) <= 8192u) gl >>= 1;
+			if(k.gen_lanes > 0) gl = (uint32_t)k.gen_lanes;
+			g->form = E_GEN; g->lanes = gl; g->block = 64u; g->grid = (count + gl - 1u) / gl;
 		}
 	}
-	if(SCORE) bsa_last_fwd_kernel = a.bw ? "k_edit_fwd score-only (forward DP, one pair per lane, last row only)" : "k_edit_fwd_wide / k_edit_fwd_gen score-only (forward DP, bands above 1024 columns, last row only)";
-	else bsa_last_fwd_kernel = a.bw ? "k_edit_fwd (forward DP, one pair per lane)" : "k_edit_fwd_wide / k_edit_fwd_gen (forward DP, bands above 1024 columns)";
-	switch(a.bw / 64){
-		EDIT_CASE(1) EDIT_CASE(2) EDIT_CASE(3) EDIT_CASE(4) EDIT_CASE(5) EDIT_CASE(6) EDIT_CASE(7) EDIT_CASE(8)
-		EDIT_CASE(9) EDIT_CASE(10) EDIT_CASE(11) EDIT_CASE(12) EDIT_CASE(13) EDIT_CASE(14) EDIT_CASE(15) EDIT_CASE(16)
-		default: {
-			// bands above 1024: static ones (overlap / extend / bandwidth 0) one pair per wave, the rest one pair per lane
-			if(a.wide == 1u) hipLaunchKernelGGL((k_edit_fwd_wide<1, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 2u) hipLaunchKernelGGL((k_edit_fwd_wide<2, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 4u) hipLaunchKernelGGL((k_edit_fwd_wide<4, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			else if(a.wide == 8u) hipLaunchKernelGGL((k_edit_fwd_wide<8, SCORE>), dim3((a.count + 3) / 4), dim3(256), 0, st, a);
-			if(a.wide == 0u || ((a.mode & 3) == BSA_MODE_GLOBAL && a.bandwidth != 0u)){
-				uint32_t gl = 64;
-				while(gl > 2u && (a.count + gl / 2 - 1) / (gl / 2) <= 8192u) gl >>= 1;
-				if(const char *e = bsa_env("BSA_EDIT_GEN_LANES")){ const int v = atoi(e); if(v >= 1 && v <= 64) gl = (uint32_t)v; }
-				hipLaunchKernelGGL(k_edit_fwd_gen<SCORE>, dim3((a.count + gl - 1) / gl), dim3(64), 0, st, a, gl);
-			}
-		} break;
+	// traceback.  Few long walks: one walk per wave (k_edit_trace_wave); BSA_EDIT_TRACE_WAVE=0/1 overrides, BSA_EDIT_TRACE_LANES and _COOP rule it out
+	// (measured, tools/edit_shapes.sh: 65536 x 20 kbp at bandwidth 256 16.9 ms against 23.5 pair-per-lane, at bandwidth 512 -- rows wider than the LDS window -- 43
+	// against 22; 262144 x 3 kbp 10.1 against 8.5)
+	auto &t = c.trace;
+	const bool narrow = bw != 0u && bw <= 64u * EW_WW, coop_ok = k.coop != '0';
+	if(k.trace_lanes < 0 && k.coop < 0 && (k.wave >= 0 ? k.wave == '1' : count <= (narrow ? 8u : 2u) * (uint32_t)cus * 32u)){ t.form = T_WAVE; t.lanes = 1u; t.grid = count; }
+	else {
+		// fewest pairs per wave that keep every wave resident, a power of two in [2, 64]; up to 8 pairs per wave the idle lanes prefetch rows for the walking ones (COOP)
+		uint32_t lanes = 2;
+		while(lanes < 64u && (count + lanes - 1) / lanes > (uint32_t)cus * (uint32_t)(lanes <= 8u && coop_ok ? occ_coop : occ_plain)) lanes <<= 1;
+		if(k.trace_lanes > 0) lanes = (uint32_t)k.trace_lanes;
+		t.form = lanes <= 8u && lanes >= 2u && coop_ok ? T_COOP : T_PLAIN; t.lanes = lanes; t.grid = (count + lanes - 1u) / lanes;
 	}
-#undef EDIT_CASE
-	return hipGetLastError();
+	// Row format 1 (tiled, bsa_common.h) is a contract between ONE forward kernel and ONE traceback kernel, k_edit_fwd_grp32 and k_edit_trace_wave, whose tiled forms
+	// exist for bands of 64 / 128 / 256 columns (G 2 / 4 / 8): it is taken where both were just chosen, for a class that fills its chunk alone (its rows are walked by
+	// one launch), never score only.  BSA_EDIT_TILED=0 keeps format 0; any of the kernel-choice knobs does as well.
+	c.row_fmt = alone && !score && k.tiled != '0' && !k.chooses_kernel() && (bw == 64u || bw == 128u || bw == 256u) && f.form == E_GRP32 && t.form == T_WAVE ? 1u : 0u;
+	f.tiled = t.tiled = c.row_fmt == 1u;
+	c.fwd_name = edit_fwd_name(f.form, f.tiled, score); c.trace_name = t.form != T_WAVE ? "k_edit_trace" : t.tiled ? "k_edit_trace_wave (rows tiled eight at a time)" : "k_edit_trace_wave";
+	return c;
+}
+bool bsa_edit_choice(uint32_t bw, uint32_t wide, uint32_t count, int mode, uint32_t bandwidth, bool score, bool alone, int cus, int occ_plain, int occ_coop,
+		uint64_t out[BSA_EDIT_CHOICE_WORDS], const char **fwd_name, const char **trace_name){
+	const EditChoice c = edit_choose(bw, wide, count, mode, bandwidth, score, alone, cus, occ_plain, occ_coop);
+	for(const auto &f : c.fwd){ const uint64_t v[7] = {f.form, f.n, f.tiled, f.track, f.lanes, f.grid, f.block}; out = std::copy(v, v + 7, out); }
+	const uint64_t v[5] = {c.trace.form, c.trace.tiled, c.trace.lanes, c.trace.grid, c.row_fmt}; std::copy(v, v + 5, out);
+	*fwd_name = c.fwd_name; *trace_name = c.trace_name;
+	return c.fwd[0].form != E_NONE;
+}
+template<bool COOP> static int edit_trace_occupancy(){          // resident blocks (= waves) of k_edit_trace<COOP> per CU; 32 where the runtime does not say
+	int v = 0;
+	return (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_edit_trace<COOP>, 64, 0) == hipSuccess && v > 0) ? v : ((void)hipGetLastError(), 32);
+}
+EditChoice bsa_edit_choose(const EditArgs &a, bool alone){
+	static const int occ_plain = edit_trace_occupancy<false>(), occ_coop = edit_trace_occupancy<true>();          // (asked once per process)
+	return edit_choose(a.bw, a.wide, a.count, a.mode, a.bandwidth, a.score != 0u, alone, bsa_cus(), occ_plain, occ_coop);
 }
 
-hipError_t bsa_launch_edit_fwd(const EditArgs &a, hipStream_t st){
+// The forward kernels: every instance the file builds is one row, keyed by the description that runs it (n: NW, G or WPL; TRACK: the register kernels outside global mode)
+constexpr uint32_t fwd_key(uint32_t form, uint32_t n, bool tiled, bool track, bool score){ return form | n << 3 | (uint32_t)tiled << 8 | (uint32_t)track << 9 | (uint32_t)score << 10; }
+#define E_REG_K1(N, TRACK, SCORE) case fwd_key(E_REG, N, false, TRACK, SCORE): hipLaunchKernelGGL((k_edit_fwd<N, TRACK, SCORE>), grid, block, 0, st, a, f.lanes); break;
+#define E_REG_K(N) E_REG_K1(N, false, false) E_REG_K1(N, true, false) E_REG_K1(N, false, true) E_REG_K1(N, true, true)
+#define E_GRP_K(G, SCORE) case fwd_key(E_GRP, G, false, false, SCORE): hipLaunchKernelGGL((k_edit_fwd_grp<G, SCORE>), grid, block, 0, st, a); break;
+#define E_GRP32_K(G, TILED, SCORE) case fwd_key(E_GRP32, G, TILED, false, SCORE): hipLaunchKernelGGL((k_edit_fwd_grp32<G, TILED, SCORE>), grid, block, 0, st, a); break;
+#define E_WIDE_K(WPL, SCORE) case fwd_key(E_WIDE, WPL, false, false, SCORE): hipLaunchKernelGGL((k_edit_fwd_wide<WPL, SCORE>), grid, block, 0, st, a); break;
+#define E_GEN_K(SCORE) case fwd_key(E_GEN, 0, false, false, SCORE): hipLaunchKernelGGL(k_edit_fwd_gen<SCORE>, grid, block, 0, st, a, f.lanes); break;
+hipError_t bsa_launch_edit_fwd(const EditArgs &a, const EditChoice &c, hipStream_t st){
 	if(a.count == 0) return hipSuccess;
-	return a.score ? launch_edit_fwd<true>(a, st) : launch_edit_fwd<false>(a, st);
+	for(const auto &f : c.fwd){
+		if(f.form == E_NONE && &f != c.fwd) break;          // (no second launch; a first one of no form has no row)
+		const dim3 grid(f.grid), block(f.block);
+		switch(fwd_key(f.form, f.n, f.tiled, f.track, c.score)){
+			E_REG_K(1) E_REG_K(2) E_REG_K(3) E_REG_K(4) E_REG_K(5) E_REG_K(6) E_REG_K(7) E_REG_K(8) E_REG_K(9) E_REG_K(10) E_REG_K(11) E_REG_K(12) E_REG_K(13) E_REG_K(14) E_REG_K(15) E_REG_K(16)
+			E_GRP_K(2, false) E_GRP_K(4, false) E_GRP_K(8, false) E_GRP_K(16, false) E_GRP_K(2, true) E_GRP_K(4, true) E_GRP_K(8, true) E_GRP_K(16, true)
+			E_GRP32_K(2, false, false) E_GRP32_K(4, false, false) E_GRP32_K(8, false, false) E_GRP32_K(16, false, false) E_GRP32_K(2, true, false) E_GRP32_K(4, true, false) E_GRP32_K(8, true, false)
+			E_GRP32_K(2, false, true) E_GRP32_K(4, false, true) E_GRP32_K(8, false, true) E_GRP32_K(16, false, true)
+			E_WIDE_K(1, false) E_WIDE_K(2, false) E_WIDE_K(4, false) E_WIDE_K(8, false) E_WIDE_K(1, true) E_WIDE_K(2, true) E_WIDE_K(4, true) E_WIDE_K(8, true)
+			E_GEN_K(false) E_GEN_K(true)
+			default: return hipErrorInvalidValue;          // (a description edit_choose does not make: no instance is built for it)
+		}
+	}
+	bsa_last_fwd_kernel = c.fwd_name;
+	return hipGetLastError();
 }
 
 hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st){
@@ -1617,46 +1635,16 @@ hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hi
 	return hipGetLastError();
 }
 
-hipError_t bsa_launch_edit_trace(const EditArgs &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
+constexpr uint32_t trace_key(uint32_t form, bool tiled){ return form | (uint32_t)tiled << 2; }          // the walkers
+#define E_WAVE_K(TILED) case trace_key(T_WAVE, TILED): hipLaunchKernelGGL(k_edit_trace_wave<TILED>, grid, dim3(64), 0, st, a, out, cig_cnt); break;
+#define E_TRACE_K(COOP) case trace_key(COOP ? T_COOP : T_PLAIN, false): hipLaunchKernelGGL(k_edit_trace<COOP>, grid, dim3(64), 0, st, a, out, cig_cnt, t.lanes); break;
+hipError_t bsa_launch_edit_trace(const EditArgs &a, const EditChoice &c, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
 	if(a.count == 0) return hipSuccess;
-	// fewest pairs per wave that keep every wave resident, a power of two in [2, 64]; up to 8 pairs per wave the idle
-	// lanes prefetch rows for the walking ones (COOP)
-	int dev = 0, cus = 256;
-	if(hipGetDevice(&dev) == hipSuccess){
-		int v = 0;
-		if(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
+	const auto &t = c.trace; const dim3 grid(t.grid);
+	switch(trace_key(t.form, t.tiled)){
+		E_WAVE_K(false) E_WAVE_K(true) E_TRACE_K(false) E_TRACE_K(true)
+		default: return hipErrorInvalidValue;
 	}
-	static int per_cu[2] = {0, 0};         // resident blocks (= waves) per CU of the two variants
-	if(per_cu[0] == 0){
-		int v = 0;
-		per_cu[0] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_edit_trace<false>, 64, 0) == hipSuccess && v > 0) ? v : 32;
-		per_cu[1] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_edit_trace<true>, 64, 0) == hipSuccess && v > 0) ? v : 32;
-		(void)hipGetLastError();
-	}
-	// few long walks: one walk per wave (k_edit_trace_wave); BSA_EDIT_TRACE_WAVE=0/1 overrides
-	{
-		// (measured, tools/edit_shapes.sh: 65536 x 20 kbp at bandwidth 256 16.9 ms against 23.5 pair-per-lane, at bandwidth 512 -- rows
-		// wider than the LDS window -- 43 against 22; 262144 x 3 kbp 10.1 against 8.5)
-		const bool narrow = a.bw != 0u && a.bw <= 64u * EW_WW;
-		bool wave = a.count <= (narrow ? 8u : 2u) * (uint32_t)cus * 32u;
-		if(const char *e = bsa_env("BSA_EDIT_TRACE_WAVE")) wave = e[0] == '1';
-		if(bsa_env("BSA_EDIT_TRACE_LANES") || bsa_env("BSA_EDIT_TRACE_COOP")) wave = false;
-		if(wave){
-			bsa_last_trace_kernel = a.row_fmt == 1u ? "k_edit_trace_wave (rows tiled eight at a time)" : "k_edit_trace_wave";
-			if(a.row_fmt == 1u) hipLaunchKernelGGL(k_edit_trace_wave<true>, dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			else hipLaunchKernelGGL(k_edit_trace_wave<false>, dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			return hipGetLastError();
-		}
-	}
-	const char *ce = bsa_env("BSA_EDIT_TRACE_COOP");
-	const bool coop_ok = !(ce && ce[0] == '0');
-	uint32_t lanes = 2;
-	const uint32_t slots_c = (uint32_t)cus * (uint32_t)per_cu[1], slots_p = (uint32_t)cus * (uint32_t)per_cu[0];
-	while(lanes < 64u && (a.count + lanes - 1) / lanes > (lanes <= 8u && coop_ok ? slots_c : slots_p)) lanes <<= 1;
-	if(const char *e = bsa_env("BSA_EDIT_TRACE_LANES")){ const int v = atoi(e); if(v >= 1 && v <= 64 && (v & (v - 1)) == 0) lanes = (uint32_t)v; }
-	const uint32_t blocks = (a.count + lanes - 1) / lanes;
-	bsa_last_trace_kernel = "k_edit_trace";
-	if(lanes <= 8u && lanes >= 2u && coop_ok) hipLaunchKernelGGL(k_edit_trace<true>, dim3(blocks), dim3(64), 0, st, a, out, cig_cnt, lanes);
-	else hipLaunchKernelGGL(k_edit_trace<false>, dim3(blocks), dim3(64), 0, st, a, out, cig_cnt, lanes);
+	bsa_last_trace_kernel = c.trace_name;
 	return hipGetLastError();
 }
