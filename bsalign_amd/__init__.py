@@ -26,6 +26,7 @@ ST_BAD_BASE, ST_EMPTY, ST_TRACE, ST_DEVICE = 1, 2, 4, 8
 KMER_CHAIN_DEVICE = 1                                                      # bsa_kmer_edit_batch2: the anchors come from the device chainer
 KMER_STRAND_AUTO = 2                                                       # bsa_kmer_chain_batch2 / bsa_kmer_edit_batch2: the call finds each pair's strand ...
 ST_REVCOMP = 16                                                            # ... and sets this status bit where it used the reverse complement of the stored query
+WINDOW_NONE = 0xFFFFFFFF                                                   # bsa_cigar_windows_*: all four fields of a window without an aligned column
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
            -5: "BSA_E_CIGAR_CAP", -6: "BSA_E_UNSUPPORTED"}
@@ -183,6 +184,10 @@ def lib():
         L.bsa_kmer_chain_words_bound.argtypes = [u32p, u32p, C.c_size_t]
         L.bsa_kmer_chain_words_bound.restype = C.c_uint64
         L.bsa_kmer_chain_run.argtypes = [vp, u8p, u64p, C.c_size_t, u64p, u32p]
+        L.bsa_cigar_windows_bound.argtypes = [u32p, C.c_size_t, C.c_uint32]
+        L.bsa_cigar_windows_bound.restype = C.c_uint64
+        L.bsa_cigar_windows_run.argtypes = [vp, vp, u32p, u64p, C.c_size_t, C.c_uint32, vp, C.c_size_t, u64p]
+        L.bsa_cigar_windows_batch.argtypes = [vp, vp, u32p, u64p, C.c_size_t, C.c_uint32, vp, C.c_size_t, u64p]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -667,6 +672,43 @@ class Context:
         ms, a, b = C.c_double(), C.c_long(), C.c_long()
         self._chk(lib().bsa_ctx_last_kmer_chain_ms(self.h, C.byref(ms), C.byref(a), C.byref(b)))
         return ms.value, a.value, b.value
+
+    def cigar_windows(self, results, cigars, window):
+        """bsa_cigar_windows_batch on what align_batch / edit_batch return (the record array and the list of CIGAR arrays): every alignment
+        cut at the borders of windows of `window` target bases.  Returns a list of (nw, 4) uint32 arrays, row r of pair k = (t_first, q_first,
+        t_last, q_last) of window results[k]["tb"] // window + r, all four WINDOW_NONE where the window holds no aligned column."""
+        n = len(cigars)
+        out = _np(results, RESULT_DTYPE)
+        if len(out) != n:
+            raise ValueError("cigar_windows: one CIGAR per record")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c) for c in cigars], dtype=np.uint64)
+        cig = _np(np.concatenate([np.zeros(0, np.uint32)] + [_np(c, np.uint32) for c in cigars]), np.uint32)
+        window = int(window)
+        # the records needed, from the definition: (te - 1) // w - tb // w + 1 for a pair with tb >= 0, te > tb and words
+        tb, te = out["tb"].astype(np.int64), out["te"].astype(np.int64)
+        has = (tb >= 0) & (te > tb) & (np.diff(off.astype(np.int64)) > 0)
+        cap = int(np.where(has, (te - 1) // max(window, 1) - tb // max(window, 1) + 1, 0).sum())
+        win = np.zeros((max(cap, 1), 4), dtype=np.uint32)
+        woff = np.zeros(n + 1, dtype=np.uint64)
+        self._chk(lib().bsa_cigar_windows_batch(self.h, _p(out), _p(cig) if len(cig) else None, _p(off), n, window, _p(win), cap, _p(woff)))
+        return [win[int(woff[k]):int(woff[k + 1])].copy() for k in range(n)]
+
+    def cigar_windows_run(self, d_out, d_cigar, d_cigar_off, n, window, d_win, win_cap, d_win_off):
+        """bsa_cigar_windows_run on torch tensors (plumbing only), asynchronous on the context's stream: d_out, d_cigar, d_cigar_off as a complete
+        AlignPlan.run / EditPlan.run left them; d_win: room for win_cap records of 16 bytes, or None with win_cap 0 for a count-only run;
+        d_win_off: n + 1 64-bit words.  Pair k's records are d_win[d_win_off[k] : d_win_off[k + 1]] where d_win_off[k + 1] <= win_cap;
+        d_win_off[n] is the number of records a complete run needs (cigar_windows_bound always suffices)."""
+        if d_win is not None and d_win.numel() * d_win.element_size() < 16 * win_cap:
+            raise ValueError("cigar_windows_run: d_win holds fewer than win_cap records")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_cigar_windows_run(self.h, ptr(d_out), ptr(d_cigar), ptr(d_cigar_off), n, int(window), ptr(d_win), win_cap, ptr(d_win_off)))
+
+
+def cigar_windows_bound(tlen, window):
+    """bsa_cigar_windows_bound: sum of ceil(tlen / window), a window arena (records) that always suffices; 0 for window == 0; host only"""
+    tlen = _np(tlen, np.uint32)
+    return int(lib().bsa_cigar_windows_bound(_p(tlen), len(tlen), int(window)))
 
 
 def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):

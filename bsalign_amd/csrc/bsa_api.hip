@@ -472,6 +472,11 @@ static hipError_t launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t
 	hipLaunchKernelGGL(k_scan_tile_apply, dim3(tiles), dim3(256), 0, st, cnt, off, n, (const uint64_t*)tmp, tiles);
 	return hipGetLastError();
 }
+// the same scan for the passes that live in files of their own (bsa_cigar_windows.hip): no carry, tmp of bsa_excl_scan_tmp_bytes(n)
+size_t bsa_excl_scan_tmp_bytes(uint32_t n){ return ((size_t)n / SCAN_TILE + 2u) * 8u; }
+hipError_t bsa_launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *tmp){
+	return launch_excl_scan(st, cnt, off, n, nullptr, tmp);
+}
 
 // one wave per pair: copy the CIGAR words a traceback kernel left at the tail of the pair's row slot
 __global__ void __launch_bounds__(256) k_cigar_collect(const uint8_t *rows, const uint64_t *slot_end,

@@ -504,6 +504,55 @@ uint64_t bsa_kmer_chain_words_bound(const uint32_t *qlen, const uint32_t *tlen, 
 int      bsa_kmer_chain_run(bsa_kmer_chain_plan_t *plan, const uint8_t *d_seqs,
                             uint64_t *d_maps, size_t maps_cap, uint64_t *d_maps_off /* n + 1 */, uint32_t *d_status /* n, may be NULL */);
 
+/* bsa_cigar_windows_* : every alignment cut at the borders of windows of `window` target bases -- what a windowed polisher needs between its read-to-draft
+ *                    alignment and its per-window POA: for every read, and for every window its alignment crosses, the read interval that belongs to that
+ *                    window, from the first to the last aligned column inside it.  A pass over the PUBLIC outputs of a run (records, CIGAR words, offsets:
+ *                    bsa_cigar_windows.hip) and nothing else, so it takes what bsa_align_run / bsa_align_batch and bsa_edit_run / bsa_edit_batch return in
+ *                    any mode and on any kernel route: plain and BSA_MODE_CIGAR_EQX words, BSA_MODE_QSTRAND pairs (query positions are then in q', as
+ *                    the record's are).  It touches no plan and changes no existing call.
+ * columns          : every position is 0-based.  The alignment of pair k starts at (t, q) = (out[k].tb, out[k].qb) and follows its words
+ *                    cigar[cigar_off[k] .. cigar_off[k + 1]).  A unit of an M, = or X word aligns target base t with query base q and then advances both: a
+ *                    DIAGONAL COLUMN (t, q).  A unit of I advances q, a unit of D advances t, any other op code takes no step.
+ * windows          : window m is the target positions [m w, (m + 1) w).  Pair k has nw_k = 0 windows when tb < 0 (score-only records), te <= tb or it has
+ *                    no words; otherwise m0 = tb / w, m1 = (te - 1) / w, nw_k = m1 - m0 + 1, and record r of the pair speaks of window m0 + r.
+ * a record         : bsa_window_t holds the first and the last diagonal column whose t lies in the window; all four fields are BSA_WINDOW_NONE when the
+ *                    window holds none (a deletion covers it whole).  The read's piece for the window is q[q_first, q_last + 1).
+ * Examples         : w = 10, tb = 7, qb = 3, words 5M 2I 4D 6M, te = 22: windows 0..2 --
+ *                      window 0 {7, 3, 9, 5}; window 1 {10, 6, 19, 13} (the deletion t 12..15 lies inside it, the query jumps from 7 to 10 over the
+ *                      insertion); window 2 {20, 14, 21, 15}.
+ *                    w = 10, tb = 0, qb = 0, words 3M 25D 3M, te = 31: windows 0..3 --
+ *                      window 0 {0, 0, 2, 2}; window 1 NONE; window 2 {28, 3, 29, 4}; window 3 {30, 5, 30, 5}.
+ * inconsistent     : the words are the caller's own arrays and may consume more or less target than te - tb.  Columns in a window above m1 are ignored
+ *                    (and, a record's positions being int32, so are columns at t >= 2^31); windows the words never reach are NONE; nothing is ever
+ *                    written outside the pair's nw_k records.  Query positions are summed modulo 2^32.
+ * _bound           : host only, no GPU.  The sum of ceil(tlen[k] / window) over the pairs: a win_cap that always suffices (0 for window == 0).
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation.  It may grow the context's scratch
+ *                    once (4 bytes a pair for the counts; a run that has to grow it may synchronise once).  window == 0 and a NULL d_win_off, a NULL d_out,
+ *                    d_cigar or d_cigar_off with n > 0, or a win_cap without a d_win are BSA_E_ARG.  n == 0 writes d_win_off[0] = 0.
+ *                    Precondition: the run that produced d_cigar was complete (its cigar_cap_words >= d_cigar_off[n]): the words of every pair are read.
+ * arena            : that of bsa_kmer_chain_run.  For ANY win_cap, 0 with a non-NULL d_win and a NULL d_win with win_cap 0 (a count-only run) included:
+ *                      - all n + 1 entries of d_win_off are those of a run with a large arena, and every run writes every one of them;
+ *                      - d_win_off[n] is the number of records needed;
+ *                      - pair k's records are written if and only if d_win_off[k + 1] <= win_cap, otherwise none of its range is touched;
+ *                      - no record at or above win_cap, nor at or above d_win_off[n], is touched;
+ *                      - every record of a written pair is written, NONE records included.
+ *                    A run leaves nothing behind that a later run reads.
+ * _batch           : all pointers are HOST memory: uploads the records and the words cigar[cigar_off[0] .. cigar_off[n]), runs, downloads, synchronises.
+ *                    win_off as from bsa_kmer_chain_batch: all n + 1 entries are written; win_cap too small: BSA_E_CIGAR_CAP, win_off[n] = the records
+ *                    needed, win untouched.  A cigar_off that decreases is BSA_E_ARG.
+ * Example          : a polisher's step on resident reads --
+ *                      bsa_align_run(plan, d_seqs, d_out, d_cigar, cigar_cap, d_cigar_off, d_status);
+ *                      cap = bsa_cigar_windows_bound(tlen, n, 500);                 (hipMalloc d_win: cap records, d_win_off: n + 1)
+ *                      bsa_cigar_windows_run(ctx, d_out, d_cigar, d_cigar_off, n, 500, d_win, cap, d_win_off); bsa_ctx_sync(ctx);
+ *                    then 16 bytes a window come down instead of the CIGAR arena. */
+#define BSA_WINDOW_NONE 0xFFFFFFFFu
+typedef struct { uint32_t t_first, q_first, t_last, q_last; } bsa_window_t;
+uint64_t bsa_cigar_windows_bound(const uint32_t *tlen, size_t n, uint32_t window);
+int      bsa_cigar_windows_run(bsa_ctx_t *ctx, const bsa_result_t *d_out, const uint32_t *d_cigar, const uint64_t *d_cigar_off,
+                               size_t n, uint32_t window, bsa_window_t *d_win, size_t win_cap, uint64_t *d_win_off /* n + 1 */);
+int      bsa_cigar_windows_batch(bsa_ctx_t *ctx, const bsa_result_t *out, const uint32_t *cigar, const uint64_t *cigar_off,
+                                 size_t n, uint32_t window, bsa_window_t *win, size_t win_cap, uint64_t *win_off /* n + 1 */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
