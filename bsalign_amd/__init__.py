@@ -140,6 +140,9 @@ def lib():
         L.bsa_align_plan_create.argtypes = [vp, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(AlignParams), C.POINTER(vp)]
         if hasattr(L, "bsa_align8_abs_form_internal"):          # (a BSA_LIB_PATH build from before it: everything else still runs)
             L.bsa_align8_abs_form_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
+        if hasattr(L, "bsa_align8_row_target_internal"):
+            L.bsa_align8_row_target_internal.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
         if hasattr(L, "bsa_align8_flag_span_internal"):
             L.bsa_align8_flag_span_internal.argtypes = [C.POINTER(AlignParams), C.POINTER(C.c_uint32)]
         if hasattr(L, "bsa_align8_x_choice_internal"):
@@ -246,6 +249,23 @@ def align8_abs_form(par):
     rows = C.c_uint32(0)
     form = lib().bsa_align8_abs_form_internal(C.byref(par), C.byref(rows))
     return int(form), int(rows.value)
+
+
+def align8_row_target(a, tlen, qlen, stride=4, steps=0):
+    """the row target of global steering as the absolute-score forward DP forms it in integers (bsa_align8_row_target_internal; host only), for uint32 arrays of
+    rows a < tlen: (value int32, fallback bool), fallback where the row asks the reference's double expression (a * qlen divides by tlen, or qlen * tlen >= 2**52 or
+    a length of 2**31 and more: outside the bound of the integer form's proof).  steps > 0: the state is
+    taken by division up to `steps` strides in front of the row and stepped to it, as the kernels do"""
+    import numpy as np
+    a, tlen, qlen = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, tlen, qlen))
+    assert a.shape == tlen.shape == qlen.shape and a.ndim == 1
+    value, fb = np.empty(len(a), np.int32), np.empty(len(a), np.uint8)
+    u32p = C.POINTER(C.c_uint32)
+    rc = lib().bsa_align8_row_target_internal(a.ctypes.data_as(u32p), tlen.ctypes.data_as(u32p), qlen.ctypes.data_as(u32p), len(a), stride, steps,
+                                              value.ctypes.data_as(C.POINTER(C.c_int32)), fb.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise ValueError("align8_row_target: a row outside its target or a target of length 0")
+    return value, fb.astype(bool)
 
 
 FLAG_SPAN_TERMS = ("M: f - d", "D: d - E", "D: f - E", "D: d - E, row -1", "D: f - E, row -1", "R, Od")

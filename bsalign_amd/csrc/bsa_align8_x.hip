@@ -29,6 +29,9 @@
 // sixteen cells a half, where it is 11 % faster).  The pair preamble, the LDS carving, the target-base window, the band steering, the code-row store, the band
 // offsets / end record and the hand-over between row segments are written in both, statement for statement: a fix to one of them goes into both.  (Moving any of
 // them into a force-inlined helper changes this compiler's output for the file's kernels, measurably so for some: HISTORY.md 11b.)
+// Two of these differ between the row bodies on purpose (HISTORY.md 19): x_forward_abs forms the row target of global steering in integers (x_rt_*, the double expression
+// where a row's product divides evenly) and shifts the slots of a row that does not move by one two to an instruction (x_slots_up / x_slots_down), and it forms
+// rbase behind a wave-level test of its two readers; x_forward keeps the double expression on every renewal, one v_cndmask_b32 a slot and rbase on every live row.
 #include "bsa_common.h"
 #include "bsa_dpp.h"
 #include <algorithm>
@@ -66,6 +69,77 @@ static __device__ __forceinline__ uint32_t x_ashr8(uint32_t a){ return __builtin
 static __device__ __forceinline__ uint32_t x_shl8(uint32_t a){ return __builtin_bit_cast(uint32_t, (xv2u)(__builtin_bit_cast(xv2u, a) << 8)); }
 // x = take ? y : x, in place (the band corrections: a plain C select makes the register allocator copy the whole band)
 static __device__ __forceinline__ void x_sel(uint32_t &x, uint32_t y, uint64_t take){ asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(x) : "v"(y), "s"(take)); }
+// Shift of a row's W slots by one slot in the lanes that execute it (the caller's divergent if sets the execution mask), two slots an instruction: slots 2j and 2j + 1
+// are handed over as one 64-bit operand, and v_pk_mov_b32 d, a, b op_sel:[x, y] writes d.lo = a[x], d.hi = b[y].
+//   x_slots_up:    X[k] <- X[k - 1], X[0] <- in        pair j = {high of pair j - 1, its own low}, from the top down
+//   x_slots_down:  X[k] <- X[k + 1], X[W - 1] <- in    pair j = {its own high, low of pair j + 1}, from the bottom up
+// The entering value is the low dword of a 64-bit operand of its own (written into the pair behind the shift instead, it made the register allocator rotate the
+// whole array by two registers and back).  The arrays stay uint32_t[W] in the source; the register coalescer keeps each in W / 2 aligned pairs.
+typedef uint32_t xv2w __attribute__((ext_vector_type(2)));
+template<int W> static __device__ __forceinline__ void x_slots_up(uint32_t *X, uint32_t in){
+	xv2w P[W / 2];
+#pragma unroll
+	for(int j = 0; j < W / 2; j++){ P[j].x = X[2 * j]; P[j].y = X[2 * j + 1]; }
+#pragma unroll
+	for(int j = W / 2 - 1; j >= 1; j--) asm("v_pk_mov_b32 %0, %1, %0 op_sel:[1,0]" : "+v"(P[j]) : "v"(P[j - 1]));
+	xv2w I;          // (the high dword is not selected by op_sel and stays unwritten: writing it costs a v_mov_b32 a shift)
+	I.x = in;
+	asm("v_pk_mov_b32 %0, %1, %0 op_sel:[0,0]" : "+v"(P[0]) : "v"(I));
+#pragma unroll
+	for(int j = 0; j < W / 2; j++){ X[2 * j] = P[j].x; X[2 * j + 1] = P[j].y; }
+}
+template<int W> static __device__ __forceinline__ void x_slots_down(uint32_t *X, uint32_t in){
+	xv2w P[W / 2];
+#pragma unroll
+	for(int j = 0; j < W / 2; j++){ P[j].x = X[2 * j]; P[j].y = X[2 * j + 1]; }
+#pragma unroll
+	for(int j = 0; j + 1 < W / 2; j++) asm("v_pk_mov_b32 %0, %0, %1 op_sel:[1,0]" : "+v"(P[j]) : "v"(P[j + 1]));
+	xv2w I;
+	I.x = in;
+	asm("v_pk_mov_b32 %0, %0, %1 op_sel:[1,0]" : "+v"(P[W / 2 - 1]) : "v"(I));
+#pragma unroll
+	for(int j = 0; j < W / 2; j++){ X[2 * j] = P[j].x; X[2 * j + 1] = P[j].y; }
+}
+// ROW TARGET of global steering (bsalign.h:4009) in integers, for x_forward_abs.  The reference's expression for row a of a pair (a < t = tlen, q = qlen):
+static __host__ __device__ inline int x_rt_double(uint32_t a, uint32_t t, uint32_t q){ return (int)((1.0 * (double)a / (double)t) * (double)q); }
+// Let v = a q / t exactly and a q = k t + r, 0 <= r < t.  The expression is y = fl(fl(a / t) q): two roundings, each within 2^-53 of its value, and a / t < 1, so
+// |y - v| < q 2^-52.  Where r != 0, v lies at least 1 / t from an integer, so trunc(y) = k whenever q 2^-52 < 1 / t, i.e. q t < 2^52.  Where r = 0, v = k is an
+// integer that y may miss from below, so those rows ask the expression itself (x_rt_set).
+// The state {k, r} of row a steps to row a + n by adding {dk, dr} of n q = dk t + dr with one carry (x_rt_step): integers throughout, a q < 2^52, r + dr < 2^32.
+// THE BOUND IS PER PAIR (x_rt_wide): the compact path bounds qlen (below 2^26), not tlen, so a pair with q t >= 2^52, or a length of 2^31 and more (r + dr could wrap),
+// is outside the proof and takes the double expression on EVERY renewal, as the kernels did before: whatever its state holds is never read.
+struct XRowTgt { uint32_t k, r; };
+static __host__ __device__ inline bool x_rt_wide(uint32_t t, uint32_t q){ return (uint64_t)t * q >= (1ull << 52) || ((t | q) >> 31) != 0u; }
+// {k, r} of a q by one division: the quotient of two exact doubles (a q < 2^52 when a < t and the pair is inside the bound) is within half an ulp of v, so its
+// truncation is k, or k + 1 where v rounded up to an integer: one correction.  t = 0 (a dead pair) has no target; rows past a short target (a >= t) and pairs
+// outside the bound get values nothing reads, and nothing here can fault.
+static __host__ __device__ inline XRowTgt x_rt_at(uint32_t a, uint32_t t, uint32_t q){
+	XRowTgt s = {0u, 0u};
+	if(t == 0u) return s;
+	const uint64_t p = (uint64_t)a * q;
+	const double y = (double)p / (double)t;
+	uint32_t k = y < 4294967295.0 ? (uint32_t)y : 0u;
+	int64_t r = (int64_t)(p - (uint64_t)k * t);
+	if(r < 0){ k--; r += t; }
+	s.k = k; s.r = (uint32_t)r;
+	return s;
+}
+static __host__ __device__ inline void x_rt_step(XRowTgt &s, const XRowTgt &d, uint32_t t){
+	s.k += d.k; s.r += d.r;
+	if(s.r >= t){ s.r -= t; s.k++; }
+}
+// one step back (k may wrap below zero in front of row 0: the step forward undoes it)
+static __host__ __device__ inline void x_rt_back(XRowTgt &s, const XRowTgt &d, uint32_t t){
+	s.k -= d.k;
+	if(s.r < d.r){ s.r += t; s.k--; }
+	s.r -= d.r;
+}
+// the row's target becomes y (the double expression's k or k - 1 where r = 0; k itself elsewhere): r takes up the difference, a q = y t + r still holds with r <= t,
+// and the next step's one carry brings r below t again because dr < t
+static __host__ __device__ inline void x_rt_set(XRowTgt &s, uint32_t y, uint32_t t){
+	s.r += (s.k - y) * t;
+	s.k = y;
+}
 static __device__ __forceinline__ uint32_t x_q8(int v){ return (((uint32_t)v & 0xffu) << 8) * 0x00010001u; }        // value << 8 in both halves
 static __device__ __forceinline__ uint32_t x_i16(int v){ return ((uint32_t)v & 0xffffu) * 0x00010001u; }            // plain int16 in both halves
 static __device__ __forceinline__ int x_lo8(uint32_t x){ return __builtin_amdgcn_sbfe((int)x, 8, 8); }              // value of the low half (value << 8 form)
@@ -963,6 +1037,8 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 // M3 = false keeps the integer recurrence above in the frame at 0, for the scorings whose bound does not fit the biased frame (bandwidth 256 only: bsa_align8_abs_rows).
 // ROWS THAT DO NOT MOVE BY ONE CELL are paid for by the whole wave, so their fix-ups have a constant form for the common cases (a move of two: one mask per flag in
 // the pair's last lane; a row that stays at rbeg > 0: the first cell's predecessor is fini's low half) and keep the general code for the wave that needs it.
+// Their slot shifts run in the lanes that need them, two slots an instruction (x_slots_up, x_slots_down).
+// ROW TARGET: {k, r} of (i + jl) qlen = k tlen + r, stepped every L rows (x_rt_double has the proof that k is what the reference's double expression gives where r != 0).
 template<int L, int NWV, int PW = 1, bool DO2 = true, bool EXT = false, bool M3 = true>
 static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const uint32_t first_pos, const uint32_t count, const uint32_t tid_base, const uint32_t rmask,
 		const uint32_t row0 = 0u, const uint32_t row1 = 0xFFFFFFF8u, uint32_t *st = nullptr, uint32_t *ext_stage = nullptr, uint32_t *ext_qwin = nullptr){
@@ -1059,14 +1135,29 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 	const int rbz = 2 * max((int)(tlen / max(qlen, 1u)), 1);
 	const bool rush32 = (unsigned long long)(uint32_t)rbz * tlen + qlen + (uint32_t)BW + (uint32_t)rbz < 0xFFFFFFFFull;
 	uint32_t rzl = rush32 ? (uint32_t)rbz * (tlen - min(row0, tlen) - 1u) : 0u;
-	int rby_tab = 0;
+	// the row target of row i + jl, renewed every L rows: held one step behind the segment's first row, the loop steps before it reads (row0 is a multiple of L)
+	XRowTgt rt = {0u, 0u}, rtd = {0u, 0u};
+	if(mode == BSA_MODE_GLOBAL){
+		rt = x_rt_at(row0 + (uint32_t)jl, tlen, qlen);
+		rtd = x_rt_at((uint32_t)L, tlen, qlen);
+		x_rt_back(rt, rtd, tlen);
+	}
+	const uint64_t rtwide = __builtin_amdgcn_ballot_w64(x_rt_wide(tlen, qlen));          // lanes of the pairs outside the proof's bound: the double expression on every renewal
 	const int rby_lane = (lt & (64 - L)) << 2;
 
 	uint64_t actm = 0;
 	while(i < row1 && (actm = __builtin_amdgcn_ballot_w64(i < tlen)) != 0ull){
 		const bool act = i < tlen;
-		if(mode == BSA_MODE_GLOBAL && (i & (uint32_t)(L - 1)) == 0u)
-			rby_tab = (int)((1.0 * (double)(i + (uint32_t)jl) / (double)tlen) * (double)qlen);
+		if(mode == BSA_MODE_GLOBAL && (i & (uint32_t)(L - 1)) == 0u){
+			// the row target of row i + jl in integers (x_rt_double has the proof); a wave with a live row whose product divides evenly, or with a live pair outside the
+			// proof's bound, asks the double expression
+			x_rt_step(rt, rtd, tlen);
+			// (one compare a ballot, joined on the scalar unit: the ballot of a conjunction is made 0 / 1 in a register and compared again)
+			if(__builtin_expect(((__builtin_amdgcn_ballot_w64(rt.r == 0u) & __builtin_amdgcn_ballot_w64(i + (uint32_t)jl < tlen)) | (rtwide & actm)) != 0ull, 0)){
+				const uint32_t y = (uint32_t)x_rt_double(i + (uint32_t)jl, tlen, qlen);
+				x_rt_set(rt, y, tlen);
+			}
+		}
 		// ---- rebase (i is uniform)
 		if((i & rmask) == 0u){
 			const uint32_t bc = x_bcast_first<L>(Hp[0]);
@@ -1096,23 +1187,17 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 			}
 			if(__any(act && mov == 0u)){
 				const bool d = act && mov == 0u;
-				const uint64_t dm = __ballot(d);
 				const uint32_t pu = x_shift_down<L>(Hp[W - 1], svH, first), pe = x_shift_down<L>(E[W - 1], svE, first);
-#pragma unroll
-				for(int k = W - 1; k >= 1; k--){ x_sel(Hp[k], Hp[k - 1], dm); x_sel(E[k], E[k - 1], dm); }
-				x_sel(Hp[0], pu, dm); x_sel(E[0], pe, dm);
+				if(d){ x_slots_up<W>(Hp, pu); x_slots_up<W>(E, pe); }
 			}
 			for(uint32_t s = 1; __any(act && mov < (uint32_t)BW && s < mov); s++){
 				const bool d = act && mov < (uint32_t)BW && s < mov;
-				const uint64_t dm = __ballot(d);
 				// the cells behind the band end: the first has H^ = last + cfirst - gape, the others repeat it; E^ of all of them is what the slide put in
 				uint32_t hfill = __builtin_amdgcn_perm(Hp[W - 1], Hp[W - 1], 0x03020302u);
 				if(s == 1u) hfill = x_add(hfill, ENT16);
 				const uint32_t efill = __builtin_amdgcn_perm(E[W - 1], E[W - 1], 0x03020302u);
 				const uint32_t inh = x_shift_up<L>(Hp[0], hfill, last), ine = x_shift_up<L>(E[0], efill, last);
-#pragma unroll
-				for(int k = 0; k + 1 < W; k++){ x_sel(Hp[k], Hp[k + 1], dm); x_sel(E[k], E[k + 1], dm); }
-				x_sel(Hp[W - 1], inh, dm); x_sel(E[W - 1], ine, dm);
+				if(d){ x_slots_down<W>(Hp, inh); x_slots_down<W>(E, ine); }
 			}
 		}
 		// ---- S~(x, y), sign-extended
@@ -1405,42 +1490,45 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 			const bool lastrow = i + 1u == tlen;
 			if((i & LM) == (uint32_t)jl) begq = (int)rbeg;
 			if(((i & LM) == LM || lastrow) && (uint32_t)jl <= (i & LM)) begs[(i & ~LM) + 1u + (uint32_t)jl] = begq;
-			const int rbase = base + GE * ((int)rbeg + (int)i);          // H at band position p = rbase + H^ + gape p
-			auto score_at = [&](uint32_t pos) -> int {
-				const uint32_t b = pos / W, kk = pos % W;
-				const bool hi = b >= (uint32_t)L;
-				uint32_t hh = Hp[0];
+			// rbase and qlen - 1 - rbeg are read by the end-of-query candidate (non-global modes) and by the last row alone: formed behind one wave-level test
+			if(__builtin_expect(__builtin_amdgcn_ballot_w64(lastrow || (mode != BSA_MODE_GLOBAL && rbeg + BW >= qlen)) != 0ull, 0)){
+				const int rbase = base + GE * ((int)rbeg + (int)i);          // H at band position p = rbase + H^ + gape p
+				auto score_at = [&](uint32_t pos) -> int {
+					const uint32_t b = pos / W, kk = pos % W;
+					const bool hi = b >= (uint32_t)L;
+					uint32_t hh = Hp[0];
 #pragma unroll
-				for(int k = 1; k < W; k++) x_sel(hh, Hp[k], __ballot((uint32_t)k == kk));          // (a plain select chain is turned into an indexed load of the row from scratch)
-				return rbase + (hi ? x_hi16(hh) : x_lo16(hh)) + GE * (int)pos;
-			};
-			if(mode != BSA_MODE_GLOBAL && rbeg + BW >= qlen){
-				const uint32_t pos = qlen - 1u - rbeg;
-				if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl){
-					const int sc = score_at(pos);
-					if(sc > cand_sc){ cand_sc = sc; cand_te = (int)i; }
+					for(int k = 1; k < W; k++) x_sel(hh, Hp[k], __ballot((uint32_t)k == kk));          // (a plain select chain is turned into an indexed load of the row from scratch)
+					return rbase + (hi ? x_hi16(hh) : x_lo16(hh)) + GE * (int)pos;
+				};
+				if(mode != BSA_MODE_GLOBAL && rbeg + BW >= qlen){
+					const uint32_t pos = qlen - 1u - rbeg;
+					if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl){
+						const int sc = score_at(pos);
+						if(sc > cand_sc){ cand_sc = sc; cand_te = (int)i; }
+					}
 				}
-			}
-			if(lastrow && mode == BSA_MODE_GLOBAL){
-				const uint32_t pos = qlen - 1u - rbeg;
-				int *const gs = begs + tlen + 1u;
-				if(pos >= (uint32_t)BW){ if(first) *gs = (int)0x80000000u; }
-				else if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl) *gs = score_at(pos);
-			} else if(lastrow){
-				bsa_code_end_t *er = (bsa_code_end_t*)(rowp + (size_t)bsa_code_rows(tlen) * (64u * CWD));
+				if(lastrow && mode == BSA_MODE_GLOBAL){
+					const uint32_t pos = qlen - 1u - rbeg;
+					int *const gs = begs + tlen + 1u;
+					if(pos >= (uint32_t)BW){ if(first) *gs = (int)0x80000000u; }
+					else if(((pos / W) & (uint32_t)(L - 1)) == (uint32_t)jl) *gs = score_at(pos);
+				} else if(lastrow){
+					bsa_code_end_t *er = (bsa_code_end_t*)(rowp + (size_t)bsa_code_rows(tlen) * (64u * CWD));
 #pragma unroll
-				for(int q = 0; q < 16 / L; q++){ er->cand_sc[jl + L * q] = q ? BSA_SCORE_MIN : cand_sc; er->cand_te[jl + L * q] = q ? 0 : cand_te; }
-				int8_t *ub = (int8_t*)(er + 1);
+					for(int q = 0; q < 16 / L; q++){ er->cand_sc[jl + L * q] = q ? BSA_SCORE_MIN : cand_sc; er->cand_te[jl + L * q] = q ? 0 : cand_te; }
+					int8_t *ub = (int8_t*)(er + 1);
 #pragma unroll
-				for(int hf = 0; hf < 2; hf++){
-					const int b = jl + L * hf;
-					auto half = [&](uint32_t x) -> int { return hf ? x_hi16(x) : x_lo16(x); };
-					er->ubegs[b * CR] = rbase + half(Hsh) + GE * (b * W - 1);
-					if constexpr (CR == 2) er->ubegs[b * CR + 1] = rbase + half(Hp[W / 2 - 1]) + GE * (b * W + W / 2 - 1);
+					for(int hf = 0; hf < 2; hf++){
+						const int b = jl + L * hf;
+						auto half = [&](uint32_t x) -> int { return hf ? x_hi16(x) : x_lo16(x); };
+						er->ubegs[b * CR] = rbase + half(Hsh) + GE * (b * W - 1);
+						if constexpr (CR == 2) er->ubegs[b * CR + 1] = rbase + half(Hp[W / 2 - 1]) + GE * (b * W + W / 2 - 1);
 #pragma unroll
-					for(int k = 0; k < W; k++) ub[b * W + k] = (int8_t)(half(Hp[k]) - half((k == 0) ? Hsh : Hp[k - 1]) + GE);
+						for(int k = 0; k < W; k++) ub[b * W + k] = (int8_t)(half(Hp[k]) - half((k == 0) ? Hsh : Hp[k - 1]) + GE);
+					}
+					if(last){ er->ubegs[16] = rbase + x_hi16(Hp[W - 1]) + GE * (BW - 1); er->rbeg_last = (int)rbeg; }
 				}
-				if(last){ er->ubegs[16] = rbase + x_hi16(Hp[W - 1]) + GE * (BW - 1); er->rbeg_last = (int)rbeg; }
 			}
 		}
 		// ---- adaptive band + global steering (x_forward's, the block differences read from H^)
@@ -1468,7 +1556,7 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 			else if(d16 < -noisy) rbx = 0;
 			else rbx = 1;
 			if(mode == BSA_MODE_GLOBAL){
-				const int rby = __builtin_amdgcn_ds_bpermute(rby_lane + (int)((i & (uint32_t)(L - 1)) << 2), rby_tab);
+				const int rby = __builtin_amdgcn_ds_bpermute(rby_lane + (int)((i & (uint32_t)(L - 1)) << 2), (int)rt.k);
 				const uint32_t left = tlen - i - 1u;
 				bool rush;
 				if(rush32) rush = act && rbeg + rzl + (uint32_t)BW <= qlen + (uint32_t)rbz - 1u;
@@ -1926,3 +2014,30 @@ static hipError_t x_launch(const Align8Args &a, int pw, bool score, hipStream_t 
 hipError_t bsa_launch_align8_fwd_x(const Align8Args &a, int pw, hipStream_t st){ return x_launch(a, pw, false, st); }
 // BSA_MODE_SCORE_ONLY (bsa_api.hip): the SCORE forms of the one-piece and linear kernels at bandwidth 64, 128 and 256, each pair leaving its record (bsa_score_rec_bytes)
 hipError_t bsa_launch_align8_fwd_x_score(const Align8Args &a, int pw, hipStream_t st){ return x_launch(a, pw, true, st); }
+
+// The row target that x_forward_abs uses for rows a[n] of pairs (tlen[n], qlen[n]), a[n] < tlen[n], for tests of x_rt_double's proof; needs no device.  The state is
+// taken by division at row a - stride * min(steps, a / stride) and stepped from there to row a (steps = 0: the division alone; the kernels step by L = 4 or 8 rows).
+// value[n]: the target; fallback[n]: 1 where the row asks the double expression (a qlen mod tlen = 0, or a pair outside the bound of the proof: x_rt_wide).
+// Returns 0, or -1 for an argument outside that.
+extern "C" int bsa_align8_row_target_internal(const uint32_t *a, const uint32_t *tlen, const uint32_t *qlen, size_t n, uint32_t stride, uint32_t steps, int32_t *value, uint8_t *fallback){
+	if(!a || !tlen || !qlen || !value || !fallback || (steps != 0u && stride == 0u)) return -1;
+	for(size_t j = 0; j < n; j++){
+		const uint32_t t = tlen[j], q = qlen[j];
+		if(t == 0u || a[j] >= t) return -1;
+		if(x_rt_wide(t, q)){ fallback[j] = 1; value[j] = x_rt_double(a[j], t, q); continue; }          // (every renewal: the state is never read)
+		const uint32_t back = steps ? std::min(steps, a[j] / stride) : 0u;
+		XRowTgt s = x_rt_at(a[j] - back * stride, t, q);
+		if(back){
+			const XRowTgt d = x_rt_at(stride, t, q);
+			x_rt_back(s, d, t);          // as the kernel starts: one step behind
+			for(uint32_t m = 0; m <= back; m++){
+				x_rt_step(s, d, t);
+				// a row on the way that divides evenly hands its state on through the double expression, as in the kernel
+				if(s.r == 0u && m < back) x_rt_set(s, (uint32_t)x_rt_double(a[j] - (back - m) * stride, t, q), t);
+			}
+		}
+		fallback[j] = s.r == 0u;
+		value[j] = s.r == 0u ? x_rt_double(a[j], t, q) : (int32_t)s.k;
+	}
+	return 0;
+}
