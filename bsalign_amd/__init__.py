@@ -88,6 +88,9 @@ class KmerParams(C.Structure):
 
 
 RESULT_DTYPE = np.dtype([(n, np.int32) for n in ("score", "qb", "qe", "tb", "te", "mat", "mis", "ins", "del", "aln")])
+# bsa_piece_t (bsa_window_pieces_*): a read's piece in one window of the draft
+PIECE_DTYPE = np.dtype([("pair", np.uint32), ("q_first", np.uint32), ("len", np.uint32), ("t_first", np.uint32), ("t_last", np.uint32), ("reserved", np.uint32),
+                        ("base_off", np.uint64)])
 
 _lib = None
 
@@ -191,6 +194,11 @@ def lib():
         L.bsa_cigar_windows_bound.restype = C.c_uint64
         L.bsa_cigar_windows_run.argtypes = [vp, vp, u32p, u64p, C.c_size_t, C.c_uint32, vp, C.c_size_t, u64p]
         L.bsa_cigar_windows_batch.argtypes = [vp, vp, u32p, u64p, C.c_size_t, C.c_uint32, vp, C.c_size_t, u64p]
+        if hasattr(L, "bsa_window_pieces_run"):                 # (a BSA_LIB_PATH build from before it: everything else still runs)
+            L.bsa_window_pieces_run.argtypes = [vp, u8p, u64p, u32p, vp, u64p, C.c_size_t, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
+                                                vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
+            L.bsa_window_pieces_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, vp, u64p, C.c_size_t, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
+                                                  vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -723,6 +731,70 @@ class Context:
             raise ValueError("cigar_windows_run: d_win holds fewer than win_cap records")
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
         self._chk(lib().bsa_cigar_windows_run(self.h, ptr(d_out), ptr(d_cigar), ptr(d_cigar_off), n, int(window), ptr(d_win), win_cap, ptr(d_win_off)))
+
+    def window_pieces(self, pairs, windows, window, gbase, nwin, seq2bit=False, strands=None):
+        """bsa_window_pieces_batch on the pairs an align_batch / edit_batch call took and what Context.cigar_windows made of its results (the
+        per-pair (nw, 4) arrays): the window records turned window-major, with the reads' bases.  The blob is packed exactly as align_batch packs
+        it (pack_pairs; seq2bit / strands as there), gbase and nwin as from window_gbase.  Returns a list over the nwin windows of
+        (pieces, codes): pieces a PIECE_DTYPE array in ascending record order, codes a list of uint8 arrays, codes[j] = q'[q_first : q_first + len)
+        of pieces[j] -- the strand that was aligned, one base a byte."""
+        n = len(pairs)
+        if len(windows) != n:
+            raise ValueError("window_pieces: one window array per pair")
+        seqs, qoff, qlen, _, _ = pack_pairs(pairs, seq2bit, strands)
+        flags = (MODE_SEQ2BIT if seq2bit else 0) | (MODE_QSTRAND if strands is not None else 0)
+        gbase = _np(gbase, np.uint64)
+        if len(gbase) != n:
+            raise ValueError("window_pieces: one gbase per pair")
+        window, nwin = int(window), int(nwin)
+        woff = np.zeros(n + 1, dtype=np.uint64)
+        woff[1:] = np.cumsum([len(x) for x in windows], dtype=np.uint64)
+        win = _np(np.concatenate([np.zeros((0, 4), np.uint32)] + [_np(x, np.uint32).reshape(-1, 4) for x in windows]), np.uint32)
+        # exact caps, from the definition
+        k = np.repeat(np.arange(n), np.diff(woff.astype(np.int64)))
+        tf, qf, tl, ql = (win[:, c].astype(np.uint64) for c in range(4))
+        gb = gbase[k] if n else np.zeros(0, np.uint64)
+        ok = (tf != WINDOW_NONE) & (tf <= tl) & (qf <= ql) & (ql < qlen[k]) & (gb < np.uint64(max(nwin, 0)))
+        ok &= np.where(ok, gb, np.uint64(0)) + tf // np.uint64(max(window, 1)) < np.uint64(max(nwin, 0))
+        pcap, bcap = int(ok.sum()), int((ql - qf + np.uint64(1))[ok].sum())
+        piece = np.zeros(max(pcap, 1), dtype=PIECE_DTYPE)
+        bases = np.zeros(max(bcap, 1), dtype=np.uint8)
+        poff, boff = np.zeros(nwin + 1, dtype=np.uint64), np.zeros(nwin + 1, dtype=np.uint64)
+        self._chk(lib().bsa_window_pieces_batch(self.h, _p(seqs), seqs.nbytes, _p(qoff), _p(qlen), _p(win) if len(win) else None, _p(woff), n, window,
+                                                _p(gbase), nwin, flags, _p(piece), pcap, _p(poff), _p(bases), bcap, _p(boff)))
+        res = []
+        for g in range(nwin):
+            ps = piece[int(poff[g]):int(poff[g + 1])].copy()
+            res.append((ps, [bases[int(x["base_off"]):int(x["base_off"]) + int(x["len"])].copy() for x in ps]))
+        return res
+
+    def window_pieces_run(self, d_seqs, d_qoff, d_qlen, d_win, d_win_off, n, window, d_gbase, nwin, flags, d_piece, piece_cap, d_piece_off,
+                          d_bases, bases_cap, d_base_off):
+        """bsa_window_pieces_run on torch tensors (plumbing only), asynchronous on the context's stream: d_seqs, d_qoff, d_qlen as the aligner's
+        plan took them, d_win, d_win_off as a complete cigar_windows_run left them, d_gbase n 64-bit words; flags: MODE_SEQ2BIT | MODE_QSTRAND as
+        in the plan's mode.  d_piece: room for piece_cap records of 32 bytes, d_bases: bases_cap bytes (either None with cap 0: a count-only run);
+        d_piece_off, d_base_off: nwin + 1 64-bit words each.  Window g is written where d_piece_off[g + 1] <= piece_cap and
+        d_base_off[g + 1] <= bases_cap; the last entries are what a complete run needs."""
+        if d_piece is not None and d_piece.numel() * d_piece.element_size() < 32 * piece_cap:
+            raise ValueError("window_pieces_run: d_piece holds fewer than piece_cap records")
+        if d_bases is not None and d_bases.numel() * d_bases.element_size() < bases_cap:
+            raise ValueError("window_pieces_run: d_bases holds fewer than bases_cap bytes")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_pieces_run(self.h, ptr(d_seqs), ptr(d_qoff), ptr(d_qlen), ptr(d_win), ptr(d_win_off), n, int(window), ptr(d_gbase),
+                                              nwin, int(flags), ptr(d_piece), piece_cap, ptr(d_piece_off), ptr(d_bases), bases_cap, ptr(d_base_off)))
+
+
+def window_gbase(target_id, target_len, window):
+    """gbase for bsa_window_pieces_*: the drafts' windows numbered through -- target j's first window is the exclusive sum of ceil(target_len / window)
+    over the targets in front of it.  target_id: for every pair the index of its target; -> (gbase per pair as uint64, nwin).  Host only."""
+    window = int(window)
+    if window <= 0:
+        raise ValueError("window_gbase: window must be positive")
+    tl = _np(target_len, np.uint64)
+    per = (tl + np.uint64(window - 1)) // np.uint64(window)
+    first = np.zeros(len(tl) + 1, dtype=np.uint64)
+    first[1:] = np.cumsum(per, dtype=np.uint64)
+    return first[_np(target_id, np.int64)].astype(np.uint64), int(first[-1])
 
 
 def cigar_windows_bound(tlen, window):

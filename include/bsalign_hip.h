@@ -553,6 +553,94 @@ int      bsa_cigar_windows_run(bsa_ctx_t *ctx, const bsa_result_t *d_out, const 
 int      bsa_cigar_windows_batch(bsa_ctx_t *ctx, const bsa_result_t *out, const uint32_t *cigar, const uint64_t *cigar_off,
                                  size_t n, uint32_t window, bsa_window_t *win, size_t win_cap, uint64_t *win_off /* n + 1 */);
 
+/* bsa_window_pieces_* : the window records turned window-major, with the reads' bases -- what a windowed polisher's POA wants: for every window of the draft, the
+ *                    pieces of the reads that cross it, as 1 B/base codes in the strand that was aligned.  bsa_cigar_windows_* leaves, for every read, the
+ *                    windows it crosses; this pass buckets those records by window and gathers q'[q_first, q_last + 1) of every one of them from the resident
+ *                    blob, so that neither the blob nor the window records have to come down and no host code slices, reverse-complements or unpacks a read.
+ *                    A pass over public outputs (bsa_window_pieces.hip): it touches no plan and changes no existing call.
+ * inputs           : d_seqs, d_qoff, d_qlen are the blob and the queries as the aligner's plan took them (BSA_MODE_SEQ2BIT and BSA_MODE_QSTRAND in `flags` as
+ *                    in that plan's mode); d_win, d_win_off are what a COMPLETE bsa_cigar_windows_run left for the same n pairs (win_cap >= d_win_off[n]).
+ * global windows   : gbase[k] is the global index of the window that holds target position 0 of pair k's target sequence.  The caller makes it: an exclusive
+ *                    sum of ceil(target length / window) over its targets, looked up per pair -- so a pair's target slice must start on a window border
+ *                    of its draft.  Windows are numbered 0 .. nwin - 1.
+ * pieces           : record i of d_win, belonging to pair k (d_win_off[k] <= i < d_win_off[k + 1]), is a PIECE if and only if
+ *                      t_first != BSA_WINDOW_NONE,  t_first <= t_last,  q_first <= q_last < qlen[k]  and  g = gbase[k] + t_first / window < nwin
+ *                    (g formed without wrapping: a gbase[k] >= nwin has no piece).  The piece belongs to window g.  Every other record is ignored: NONE
+ *                    records, and anything inconsistent in arrays that are the caller's own.  Nothing is ever read outside a read's qlen bases because of
+ *                    a record.
+ * order            : the pieces of window g are piece[piece_off[g] .. piece_off[g + 1]), in ascending order of their record index i (on what
+ *                    bsa_cigar_windows_run writes a pair has one record a window, so this is ascending pair index).  The order is part of the contract: the
+ *                    output of a call is a function of its inputs alone and identical from run to run.
+ * a piece          : bsa_piece_t: pair = k; q_first = the record's, a position in q' (the strand that was aligned: the record's coordinates); len = q_last -
+ *                    q_first + 1; t_first, t_last = the record's; reserved = 0; base_off: the piece's codes are bases[base_off .. base_off + len).
+ * bases            : the bases of window g are bases[base_off[g] .. base_off[g + 1]): its pieces one after another in that order, no padding.  A piece's
+ *                    base_off is absolute (an index into bases, not into the window's range).
+ * codes            : one base a byte, q'[q_first .. q_first + len), q' the query as the aligner saw it through its staging kernels.  With s the stored query of
+ *                    qlen[k] bases: an unmarked pair gives s[j] & 3; a pair marked with BSA_QOFF_REVCOMP (only with BSA_MODE_QSTRAND in flags) gives
+ *                    (s[qlen - 1 - j] & 3) ^ 3; with BSA_MODE_SEQ2BIT the blob is BaseBank.bits words and qoff are base offsets, layout and rules as for
+ *                    the align calls (d_seqs 8-byte aligned, bsa_window_pieces_run: BSA_E_ARG otherwise).  Nothing is read in front of the word (byte)
+ *                    that holds a read's first base nor behind the one that holds its last.
+ * flags            : a subset of BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND; any other bit is BSA_E_ARG.  Without BSA_MODE_QSTRAND bit 63 of qoff is part of the
+ *                    offset (bsa_window_pieces_batch: BSA_E_ARG, offset outside the blob; bsa_window_pieces_run: a broken precondition).
+ * Example          : window = 4, one target of 12 bases (windows 0..2, nwin = 3), two pairs on it, gbase = {0, 0}, flags = BSA_MODE_QSTRAND.
+ *                      pair 0: stored ACGTACGTAC (0 1 2 3 0 1 2 3 0 1), qlen 10, unmarked: q' = the stored bases.
+ *                              records 0..2: {1, 0, 3, 2}  {4, 3, 7, 6}  {8, 7, 10, 9}                     (t_first, q_first, t_last, q_last; windows 0, 1, 2)
+ *                      pair 1: stored AACCGGT (0 0 1 1 2 2 3), qlen 7, marked: q' = ACCGGTT (0 1 1 2 2 3 3).
+ *                              records 3..4: {5, 0, 7, 2}  {8, 3, 11, 6}                                    (windows 1, 2);  d_win_off = {0, 3, 5}
+ *                    gives piece_off = {0, 1, 3, 5}, base_off = {0, 3, 10, 17} and
+ *                      window 0: {pair 0, q_first 0, len 3, t 1..3,  base_off 0}   codes 0 1 2
+ *                      window 1: {pair 0, q_first 3, len 4, t 4..7,  base_off 3}   codes 3 0 1 2        (record 1)
+ *                                {pair 1, q_first 0, len 3, t 5..7,  base_off 7}   codes 0 1 1          (record 3: q'[0, 3), stored bases 6, 5, 4 complemented)
+ *                      window 2: {pair 0, q_first 7, len 3, t 8..10, base_off 10}  codes 3 0 1          (record 2)
+ *                                {pair 1, q_first 3, len 4, t 8..11, base_off 13}  codes 2 2 3 3        (record 4)
+ *                    bases = 0 1 2 | 3 0 1 2 0 1 1 | 3 0 1 2 2 3 3.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (16 bytes a window for the counters, 16 bytes for every piece of piece_cap while both caps are non-zero; a run that has to
+ *                    grow it may synchronise once; BSA_E_NOMEM when it cannot).
+ * arenas (_run)    : the contract of bsa_kmer_chain_run and bsa_cigar_windows_run with the window as the unit and two arenas.  For ANY piece_cap and bases_cap,
+ *                    0 with a non-NULL arena and a NULL arena with cap 0 (a count-only run) included:
+ *                      - all nwin + 1 entries of d_piece_off and of d_base_off are those of a run with large arenas, and every run writes every one of them;
+ *                      - d_piece_off[nwin] and d_base_off[nwin] are the pieces and the bytes a complete run needs;
+ *                      - window g is written if and only if d_piece_off[g + 1] <= piece_cap and d_base_off[g + 1] <= bases_cap;
+ *                      - a written window is written whole: every field of every piece record (reserved = 0) and every base;
+ *                      - a window that is not written has no byte of either of its ranges touched;
+ *                      - nothing at or above either cap, nor at or above either total, is touched;
+ *                      - the caller's arenas are never used as scratch for windows that do not fit.
+ *                    A run leaves nothing behind that a later run reads.  Caps that always suffice: d_win_off[n] pieces (bsa_cigar_windows_bound bounds
+ *                    them) and the sum of qlen bytes when, as on what bsa_cigar_windows_run writes, a pair's pieces do not overlap.
+ * _batch           : all pointers are HOST memory: checks every (qoff & ~strand bit) + qlen against seqs_bytes (4 * seqs_bytes bases with BSA_MODE_SEQ2BIT,
+ *                    seqs_bytes then a multiple of 8) -- a read outside the blob is BSA_E_ARG, as is a win_off that decreases -- uploads the blob, the queries
+ *                    and the records win[win_off[0] .. win_off[n]), runs, downloads, synchronises.  Both offset arrays are always written whole; if either cap
+ *                    is too small: BSA_E_CIGAR_CAP, piece_off[nwin] and base_off[nwin] say what is needed, piece and bases are untouched.
+ * errors (both)    : window == 0; a NULL piece_off or base_off; NULL inputs with n > 0; a cap without its arena; n or nwin above 0xFFFFFFF0: BSA_E_ARG.
+ *                    n == 0 or nwin == 0 is fine: the offsets are all 0.
+ * Example          : a polisher's step on resident reads --
+ *                      bsa_align_run(plan, d_seqs, d_out, d_cigar, cigar_cap, d_cigar_off, d_status);
+ *                      bsa_cigar_windows_run(ctx, d_out, d_cigar, d_cigar_off, n, 500, d_win, cap, d_win_off);
+ *                      bsa_window_pieces_run(ctx, d_seqs, d_qoff, d_qlen, d_win, d_win_off, n, 500, d_gbase, nwin, plan_mode & (BSA_MODE_SEQ2BIT | BSA_MODE_QSTRAND),
+ *                                            d_piece, cap, d_piece_off, d_bases, sum_qlen, d_base_off); bsa_ctx_sync(ctx);
+ *                    then 32 bytes a piece and the pieces' codes come down, window by window, instead of the window records and the blob. */
+typedef struct {
+	uint32_t pair;             /* k: the pair the piece comes from */
+	uint32_t q_first;          /* first base of the piece, a position in q' (the strand that was aligned: the record's coordinates) */
+	uint32_t len;              /* q_last - q_first + 1 */
+	uint32_t t_first, t_last;  /* the window record's first and last aligned target position */
+	uint32_t reserved;         /* 0 */
+	uint64_t base_off;         /* the piece's codes are bases[base_off .. base_off + len) */
+} bsa_piece_t;                 /* 32 bytes */
+int      bsa_window_pieces_run(bsa_ctx_t *ctx,
+                               const uint8_t *d_seqs, const uint64_t *d_qoff, const uint32_t *d_qlen,
+                               const bsa_window_t *d_win, const uint64_t *d_win_off, size_t n,
+                               uint32_t window, const uint64_t *d_gbase /* n */, size_t nwin, uint32_t flags,
+                               bsa_piece_t *d_piece, size_t piece_cap, uint64_t *d_piece_off /* nwin + 1 */,
+                               uint8_t *d_bases, size_t bases_cap, uint64_t *d_base_off /* nwin + 1 */);
+int      bsa_window_pieces_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seqs_bytes,
+                                 const uint64_t *qoff, const uint32_t *qlen,
+                                 const bsa_window_t *win, const uint64_t *win_off, size_t n,
+                                 uint32_t window, const uint64_t *gbase, size_t nwin, uint32_t flags,
+                                 bsa_piece_t *piece, size_t piece_cap, uint64_t *piece_off,
+                                 uint8_t *bases, size_t bases_cap, uint64_t *base_off);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
