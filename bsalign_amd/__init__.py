@@ -27,6 +27,7 @@ KMER_CHAIN_DEVICE = 1                                                      # bsa
 KMER_STRAND_AUTO = 2                                                       # bsa_kmer_chain_batch2 / bsa_kmer_edit_batch2: the call finds each pair's strand ...
 ST_REVCOMP = 16                                                            # ... and sets this status bit where it used the reverse complement of the stored query
 WINDOW_NONE = 0xFFFFFFFF                                                   # bsa_cigar_windows_*: all four fields of a window without an aligned column
+PIECE_ST_NOT_ON_PATH = 1                                                   # bsa_piece_cigars_*: a piece whose ends are not aligned columns of its pair
 
 E_NAMES = {0: "OK", -1: "BSA_E_NODEVICE", -2: "BSA_E_ARG", -3: "BSA_E_NOMEM", -4: "BSA_E_HIP",
            -5: "BSA_E_CIGAR_CAP", -6: "BSA_E_UNSUPPORTED"}
@@ -199,6 +200,11 @@ def lib():
                                                 vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
             L.bsa_window_pieces_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, vp, u64p, C.c_size_t, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
                                                   vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
+        if hasattr(L, "bsa_piece_cigars_run"):
+            L.bsa_piece_cigars_bound.argtypes = [u64p, C.c_size_t, C.c_size_t]
+            L.bsa_piece_cigars_bound.restype = C.c_uint64
+            L.bsa_piece_cigars_run.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+            L.bsa_piece_cigars_batch.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -783,6 +789,52 @@ class Context:
         self._chk(lib().bsa_window_pieces_run(self.h, ptr(d_seqs), ptr(d_qoff), ptr(d_qlen), ptr(d_win), ptr(d_win_off), n, int(window), ptr(d_gbase),
                                               nwin, int(flags), ptr(d_piece), piece_cap, ptr(d_piece_off), ptr(d_bases), bases_cap, ptr(d_base_off)))
 
+    def piece_cigars(self, results, cigars, windows_out):
+        """bsa_piece_cigars_batch on what align_batch / edit_batch returned (the record array and the list of CIGAR arrays) and what
+        Context.window_pieces made of them (the list over the windows of (pieces, codes)): every piece's own CIGAR words, the stretch of its pair's
+        words from the piece's first to its last aligned column.  Returns a list over the windows of lists of (words, status), one for each piece
+        of the window in its order: words a uint32 array, status 0, or PIECE_ST_NOT_ON_PATH and no words for a piece whose ends are not aligned
+        columns of its pair (none on what cigar_windows and window_pieces return)."""
+        n = len(cigars)
+        out = _np(results, RESULT_DTYPE)
+        if len(out) != n:
+            raise ValueError("piece_cigars: one CIGAR per record")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(c) for c in cigars], dtype=np.uint64)
+        cig = _np(np.concatenate([np.zeros(0, np.uint32)] + [_np(c, np.uint32) for c in cigars]), np.uint32)
+        piece = _np(np.concatenate([np.zeros(0, PIECE_DTYPE)] + [_np(ps, PIECE_DTYPE) for ps, _ in windows_out]), PIECE_DTYPE)
+        npiece = len(piece)
+        poff = np.zeros(npiece + 1, dtype=np.uint64)
+        status = np.zeros(max(npiece, 1), dtype=np.uint32)
+        cap = piece_cigars_bound(off, npiece)                  # enough for pieces that do not overlap; any others say what they need
+        for _ in range(2):
+            pcig = np.zeros(max(cap, 1), dtype=np.uint32)
+            rc = lib().bsa_piece_cigars_batch(self.h, _p(out), _p(cig) if len(cig) else None, _p(off), n, _p(piece) if npiece else None, npiece,
+                                              _p(pcig), cap, _p(poff), _p(status))
+            if rc != -5 or int(poff[npiece]) <= cap:
+                break
+            cap = int(poff[npiece])
+        self._chk(rc)
+        res, j = [], 0
+        for ps, _ in windows_out:
+            res.append([(pcig[int(poff[i]):int(poff[i + 1])].copy(), int(status[i])) for i in range(j, j + len(ps))])
+            j += len(ps)
+        return res
+
+    def piece_cigars_run(self, d_out, d_cigar, d_cigar_off, n, d_piece, d_npiece, piece_cap, d_pcig, pcig_cap, d_pcig_off, d_pstatus=None):
+        """bsa_piece_cigars_run on torch tensors (plumbing only), asynchronous on the context's stream: d_out, d_cigar, d_cigar_off as a complete
+        AlignPlan.run / EditPlan.run left them; d_piece as a complete window_pieces_run left it, with room for piece_cap records; d_npiece: one
+        64-bit word on the device, the pieces there are (d_piece_off[nwin:]); d_pcig: room for pcig_cap words, or None with pcig_cap 0 for a
+        count-only run; d_pcig_off: piece_cap + 1 64-bit words; d_pstatus: piece_cap 32-bit words or None.  Piece j's words are
+        d_pcig[d_pcig_off[j] : d_pcig_off[j + 1]] where d_pcig_off[j + 1] <= pcig_cap; d_pcig_off[piece_cap] is what a complete run needs."""
+        if d_pcig is not None and d_pcig.numel() * d_pcig.element_size() < 4 * pcig_cap:
+            raise ValueError("piece_cigars_run: d_pcig holds fewer than pcig_cap words")
+        if d_pcig_off is not None and d_pcig_off.numel() * d_pcig_off.element_size() < 8 * (piece_cap + 1):
+            raise ValueError("piece_cigars_run: d_pcig_off holds fewer than piece_cap + 1 offsets")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_piece_cigars_run(self.h, ptr(d_out), ptr(d_cigar), ptr(d_cigar_off), n, ptr(d_piece), ptr(d_npiece), piece_cap,
+                                             ptr(d_pcig), pcig_cap, ptr(d_pcig_off), ptr(d_pstatus)))
+
 
 def window_gbase(target_id, target_len, window):
     """gbase for bsa_window_pieces_*: the drafts' windows numbered through -- target j's first window is the exclusive sum of ceil(target_len / window)
@@ -801,6 +853,13 @@ def cigar_windows_bound(tlen, window):
     """bsa_cigar_windows_bound: sum of ceil(tlen / window), a window arena (records) that always suffices; 0 for window == 0; host only"""
     tlen = _np(tlen, np.uint32)
     return int(lib().bsa_cigar_windows_bound(_p(tlen), len(tlen), int(window)))
+
+
+def piece_cigars_bound(cigar_off, npiece):
+    """bsa_piece_cigars_bound: the words the n + 1 offsets speak of plus npiece, a word arena that always suffices for pieces of which no two
+    of a pair share a column (those of one cigar_windows call); host only"""
+    off = _np(cigar_off, np.uint64)
+    return int(lib().bsa_piece_cigars_bound(_p(off) if len(off) else None, max(len(off) - 1, 0), int(npiece)))
 
 
 def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):

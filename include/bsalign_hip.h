@@ -641,6 +641,77 @@ int      bsa_window_pieces_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
                                  bsa_piece_t *piece, size_t piece_cap, uint64_t *piece_off,
                                  uint8_t *bases, size_t bases_cap, uint64_t *base_off);
 
+/* bsa_piece_cigars_* : every piece's own CIGAR words -- how the piece aligns to its window of the draft, which is what the POA's band placement takes as a
+ *                    read's guide (bsa_pog_guide_t::sam, bsalign_poa.h).  bsa_window_pieces_* leaves, for every window, the reads' pieces and their codes;
+ *                    the piece's alignment against the draft already exists: it is the stretch of its pair's CIGAR from the piece's first to its last
+ *                    aligned column.  This pass cuts that stretch out for every piece, window by window, so that the CIGAR arena never has to come down.
+ *                    A pass over public outputs (bsa_piece_cigars.hip): it touches no plan and changes no existing call, uses neither the window records
+ *                    nor the window size, and so serves both aligners, plain and BSA_MODE_CIGAR_EQX words and BSA_MODE_QSTRAND pairs (positions in q').
+ * inputs           : d_out, d_cigar, d_cigar_off are what a COMPLETE bsa_align_run / bsa_edit_run left for n pairs; d_piece and d_npiece = d_piece_off + nwin
+ *                    are what a COMPLETE bsa_window_pieces_run left (its piece_cap >= d_piece_off[nwin]); piece_cap is the room of d_piece.
+ * columns          : as in bsa_cigar_windows_*.  The alignment of pair k starts at (t, q) = (out[k].tb, out[k].qb); a unit of an M, = or X word is a DIAGONAL
+ *                    COLUMN (t, q) and then advances both; a unit of I advances q, a unit of D advances t; any other op code takes no step.  t is summed in 64
+ *                    bits, q modulo 2^32.  ALL of the pair's words count, also where they run on behind out[k].te.
+ * a piece is cut   : piece j, with k = piece[j].pair, is CUT if and only if  k < n,  out[k].tb >= 0,  pair k has words (cigar_off[k + 1] > cigar_off[k]; a pair of
+ *                    2^32 words or more counts as having none),  t_first <= t_last,  len >= 1,  and both (t_first, q_first) and (t_last, q_first + len - 1) are
+ *                    diagonal columns of pair k's alignment (q_first + len - 1 modulo 2^32).  A cut piece has status 0.  Every other piece has no words and
+ *                    status BSA_PIECE_ST_NOT_ON_PATH.  The pieces are the caller's own arrays: nothing inconsistent in them makes the pass read outside
+ *                    pair k's words or write outside piece j's range.  On what bsa_cigar_windows_run and bsa_window_pieces_run write every piece is cut.
+ * its words        : pair k's words in order, clipped to the units from the first of the two columns to the last, both included: a word that lies partly
+ *                    outside keeps its op and the length that lies inside; words (or clippings) of length 0 and words of an op that takes no step are
+ *                    dropped; nothing is merged (two adjacent M words stay two words); = and X stay = and X.  So the first and the last word are diagonal,
+ *                    the lengths of the words that advance q sum to len (modulo 2^32) and those of the words that advance t to t_last - t_first + 1.
+ * order            : piece j's words are pcig[pcig_off[j] .. pcig_off[j + 1]); j is the index bsa_window_pieces_run gave the piece (by window, then ascending
+ *                    record), so window g's words are the contiguous range pcig[pcig_off[piece_off[g]] .. pcig_off[piece_off[g + 1]]).  The output is a
+ *                    function of the inputs alone.
+ * Example          : the first example of bsa_cigar_windows_*: tb = 7, qb = 3, words 5M 2I 4D 6M, cut at w = 10 into the pieces
+ *                      {q_first 3, len 3, t 7..9}    -> 3M                 (the first three units of 5M)
+ *                      {q_first 6, len 8, t 10..19}  -> 2M 2I 4D 4M        (the last two units of 5M, the whole gap words, the first four units of 6M)
+ *                      {q_first 14, len 2, t 20..21} -> 2M                 (the last two units of 6M)
+ *                    pcig_off = {0, 1, 5, 6}, status 0 0 0.  A piece {q_first 6, len 3, t 10..12} is not on the path (t 12 is deleted), nor is
+ *                    {q_first 7, len 7, t 10..19} (t 10 aligns with q 6): no words, status 1.
+ *                    For bsa_pog_place in refmode, with the window's slice of the draft as the backbone, the caller puts the piece's words between two D words
+ *                    of its own: (t_first % w) D in front and (window's end - 1 - t_last) D behind (zero lengths left out) -- window [0, 10): 7D 3M;
+ *                    window [10, 20): 2M 2I 4D 4M; window [20, 30): 2M 8D.
+ * _bound           : host only, no GPU.  (cigar_off[n] - cigar_off[0]) + npiece: a pcig_cap that always suffices IF no two pieces of a pair share a column,
+ *                    as is the case for the pieces of ONE bsa_cigar_windows_run (each of a pair's words then lands in at most one piece, plus one more
+ *                    piece for every cut that falls inside it, and there are fewer cuts than pieces).  Pieces that overlap can need more: count first.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (512 bytes a pair for the index, 36 bytes for every piece of piece_cap; a run that has to grow it may synchronise once;
+ *                    BSA_E_NOMEM when it cannot).  P = min(*d_npiece, piece_cap) is read on the device; launches are sized by piece_cap.  All piece_cap + 1
+ *                    entries of d_pcig_off are written by every run, the entries above P equal the total d_pcig_off[P]; d_pstatus[j] (if not NULL) is
+ *                    written for j < P.
+ * arena (_run)     : that of bsa_kmer_chain_run, with the piece as the unit.  For ANY pcig_cap, 0 with a non-NULL d_pcig and a NULL d_pcig with cap 0 (a
+ *                    count-only run) included:
+ *                      - all entries of d_pcig_off are those of a run with a large arena;
+ *                      - d_pcig_off[P] is the number of words needed;
+ *                      - piece j's words are written, all of them, if and only if d_pcig_off[j + 1] <= pcig_cap, otherwise none of its range is touched;
+ *                      - no word at or above pcig_cap, nor at or above the total, is touched;
+ *                      - the caller's arena is never used as scratch.
+ *                    A run leaves nothing behind that a later run reads.
+ * _batch           : all pointers are HOST memory: uploads the records, the words cigar[cigar_off[0] .. cigar_off[n]) and the npiece pieces, runs, downloads,
+ *                    synchronises.  pcig_off: all npiece + 1 entries are written; pstatus (npiece, may be NULL) likewise.  A cigar_off that decreases is
+ *                    BSA_E_ARG.  pcig_cap too small: BSA_E_CIGAR_CAP, pcig_off[npiece] = the words needed, pcig untouched.  n == 0 or npiece == 0 is
+ *                    fine: the offsets are 0 and every piece is not on a path.
+ * errors (both)    : a NULL pcig_off; NULL d_out, d_cigar (_batch: only if the offsets speak of words) or d_cigar_off with n > 0; a NULL d_piece or
+ *                    d_npiece with piece_cap > 0; a cap without its arena; n or the piece count (piece_cap, npiece) above 0xFFFFFFF0: BSA_E_ARG.
+ * Example          : a polisher's step on resident reads --
+ *                      bsa_align_run(plan, d_seqs, d_out, d_cigar, cigar_cap, d_cigar_off, d_status);
+ *                      bsa_cigar_windows_run(ctx, d_out, d_cigar, d_cigar_off, n, 500, d_win, cap, d_win_off);
+ *                      bsa_window_pieces_run(ctx, d_seqs, d_qoff, d_qlen, d_win, d_win_off, n, 500, d_gbase, nwin, flags, d_piece, cap, d_piece_off, ...);
+ *                      bsa_piece_cigars_run(ctx, d_out, d_cigar, d_cigar_off, n, d_piece, d_piece_off + nwin, cap, d_pcig, cigar_cap + cap, d_pcig_off, NULL);
+ *                    then codes and guides of every window come down window by window; blob, window records and CIGAR arena stay on the device. */
+#define BSA_PIECE_ST_NOT_ON_PATH 1u
+uint64_t bsa_piece_cigars_bound(const uint64_t *cigar_off, size_t n, size_t npiece);
+int      bsa_piece_cigars_run(bsa_ctx_t *ctx,
+                              const bsa_result_t *d_out, const uint32_t *d_cigar, const uint64_t *d_cigar_off, size_t n,
+                              const bsa_piece_t *d_piece, const uint64_t *d_npiece, size_t piece_cap,
+                              uint32_t *d_pcig, size_t pcig_cap, uint64_t *d_pcig_off /* piece_cap + 1 */, uint32_t *d_pstatus /* piece_cap, may be NULL */);
+int      bsa_piece_cigars_batch(bsa_ctx_t *ctx,
+                                const bsa_result_t *out, const uint32_t *cigar, const uint64_t *cigar_off, size_t n,
+                                const bsa_piece_t *piece, size_t npiece,
+                                uint32_t *pcig, size_t pcig_cap, uint64_t *pcig_off /* npiece + 1 */, uint32_t *pstatus /* npiece, may be NULL */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
