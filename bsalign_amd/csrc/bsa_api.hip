@@ -6,7 +6,7 @@
 // two HIP streams: forward DP of chunk k+1 (compute / HBM-write bound) runs on the context stream while
 // traceback + CIGAR compaction of chunk k (latency bound, few waves) runs on an auxiliary stream, the two
 // halves of the workspace alternating.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 #include <algorithm>
 #include <atomic>
 #include <memory>
@@ -375,109 +375,6 @@ extern "C" int bsa_seq_pack2bit(bsa_ctx_t *c, const uint8_t *d_codes, uint64_t n
 	return BSA_OK;
 }
 
-// single-block exclusive scan of cnt[0..n) into off[0..n], off[n] = total; *carry (optional) is a running base
-__global__ void __launch_bounds__(1024) k_excl_scan(const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *carry){
-	__shared__ uint64_t part[1024];
-	__shared__ uint64_t base;
-	const uint32_t t = threadIdx.x;
-	if(t == 0) base = carry ? *carry : 0ull;
-	__syncthreads();
-	for(uint32_t s = 0; s < n; s += 1024u * 8u){
-		uint64_t loc[8]; uint64_t sum = 0;
-		for(int k = 0; k < 8; k++){
-			uint32_t idx = s + t * 8u + k;
-			loc[k] = sum;
-			sum += (idx < n) ? cnt[idx] : 0u;
-		}
-		part[t] = sum;
-		__syncthreads();
-		for(uint32_t d = 1; d < 1024; d <<= 1){   // Hillis-Steele inclusive scan of the per-thread sums
-			uint64_t v = (t >= d) ? part[t - d] : 0ull;
-			__syncthreads();
-			part[t] += v;
-			__syncthreads();
-		}
-		const uint64_t excl = part[t] - sum + base;
-		for(int k = 0; k < 8; k++){
-			uint32_t idx = s + t * 8u + k;
-			if(idx < n) off[idx] = excl + loc[k];
-		}
-		__syncthreads();
-		if(t == 1023) base += part[1023];
-		__syncthreads();
-	}
-	if(t == 0){ off[n] = base; if(carry) *carry = base; }
-}
-
-// The same scan over many blocks for batches of millions of pairs (one block reads 4 bytes per pair at the speed of one CU: 2 ms
-// for 2 M pairs, twice per step): sums of tiles of SCAN_TILE counts, a scan of the sums by one block, then every tile scanned with
-// its base.  tmp: (tiles + 1) uint64.
-#define SCAN_TILE 4096u
-__global__ void __launch_bounds__(256) k_scan_tile_sums(const uint32_t *cnt, uint32_t n, uint64_t *tmp){
-	__shared__ uint64_t red[4];
-	const uint32_t b = blockIdx.x, t = threadIdx.x;
-	uint64_t s = 0;
-	for(uint32_t i = t; i < SCAN_TILE; i += 256u){ const uint32_t idx = b * SCAN_TILE + i; s += (idx < n) ? cnt[idx] : 0u; }
-	for(int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
-	if((t & 63u) == 0u) red[t >> 6] = s;
-	__syncthreads();
-	if(t == 0) tmp[b] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ void __launch_bounds__(1024) k_scan_tile_bases(uint64_t *tmp, uint32_t tiles, uint64_t *carry){
-	__shared__ uint64_t part[1024];
-	__shared__ uint64_t base;
-	const uint32_t t = threadIdx.x;
-	if(t == 0) base = carry ? *carry : 0ull;
-	__syncthreads();
-	for(uint32_t s = 0; s < tiles; s += 1024u){
-		const uint64_t v = (s + t < tiles) ? tmp[s + t] : 0ull;
-		part[t] = v;
-		__syncthreads();
-		for(uint32_t d = 1; d < 1024; d <<= 1){
-			const uint64_t w = (t >= d) ? part[t - d] : 0ull;
-			__syncthreads();
-			part[t] += w;
-			__syncthreads();
-		}
-		if(s + t < tiles) tmp[s + t] = part[t] - v + base;
-		__syncthreads();
-		if(t == 1023) base += part[1023];
-		__syncthreads();
-	}
-	if(t == 0){ tmp[tiles] = base; if(carry) *carry = base; }
-}
-__global__ void __launch_bounds__(256) k_scan_tile_apply(const uint32_t *cnt, uint64_t *off, uint32_t n, const uint64_t *tmp, uint32_t tiles){
-	__shared__ uint64_t wsum[4];
-	const uint32_t b = blockIdx.x, t = threadIdx.x;
-	const uint32_t i0 = b * SCAN_TILE + t * 16u;            // 16 consecutive counts per thread
-	uint32_t loc[16]; uint64_t s = 0;
-	for(int k = 0; k < 16; k++){ const uint32_t idx = i0 + k; loc[k] = (uint32_t)s; s += (idx < n) ? cnt[idx] : 0u; }
-	uint64_t inc = s;                                       // inclusive scan of the thread sums inside the wave, then across the four waves
-	for(int d = 1; d < 64; d <<= 1){ const uint64_t v = __shfl_up(inc, d); if((t & 63u) >= (uint32_t)d) inc += v; }
-	if((t & 63u) == 63u) wsum[t >> 6] = inc;
-	__syncthreads();
-	uint64_t wb = 0;
-	for(uint32_t w = 0; w < (t >> 6); w++) wb += wsum[w];
-	const uint64_t excl = tmp[b] + wb + inc - s;
-	for(int k = 0; k < 16; k++){ const uint32_t idx = i0 + k; if(idx < n) off[idx] = excl + loc[k]; }
-	if(b == tiles - 1u && t == 0) off[n] = tmp[tiles];
-}
-
-static hipError_t launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *carry, uint64_t *tmp){
-	// (one block takes 111 us for the 100 000 counts of C2, twice a step; in tiles 3 x 5 us)
-	if(n <= 16384u || !tmp){ hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, st, cnt, off, n, carry); return hipGetLastError(); }
-	const uint32_t tiles = (n + SCAN_TILE - 1u) / SCAN_TILE;
-	hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles), dim3(256), 0, st, cnt, n, tmp);
-	hipLaunchKernelGGL(k_scan_tile_bases, dim3(1), dim3(1024), 0, st, tmp, tiles, carry);
-	hipLaunchKernelGGL(k_scan_tile_apply, dim3(tiles), dim3(256), 0, st, cnt, off, n, (const uint64_t*)tmp, tiles);
-	return hipGetLastError();
-}
-// the same scan for the passes that live in files of their own (bsa_cigar_windows.hip): no carry, tmp of bsa_excl_scan_tmp_bytes(n)
-size_t bsa_excl_scan_tmp_bytes(uint32_t n){ return ((size_t)n / SCAN_TILE + 2u) * 8u; }
-hipError_t bsa_launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *tmp){
-	return launch_excl_scan(st, cnt, off, n, nullptr, tmp);
-}
-
 // one wave per pair: copy the CIGAR words a traceback kernel left at the tail of the pair's row slot
 __global__ void __launch_bounds__(256) k_cigar_collect(const uint8_t *rows, const uint64_t *slot_end,
 		uint32_t first, uint32_t count, const uint32_t *cnt, const uint64_t *off, uint32_t *tmp, uint64_t cap){
@@ -697,7 +594,7 @@ static int plan_common_alloc(PlanBase *p, const uint64_t *qoff, const uint32_t *
 		{(void**)&p->d_qst, nullptr, std::max<size_t>(qst_bytes, 1), 0}, {(void**)&p->d_tst, nullptr, std::max<size_t>(tst_bytes, 1), 0},
 		{(void**)&p->d_cnt_pos, nullptr, m * 4, 0}, {(void**)&p->d_cnt_pair, nullptr, m * 4, 0}, {(void**)&p->d_status_own, nullptr, m * 4, 0},
 		{(void**)&p->d_off_pos, nullptr, (m + 1) * 8, 0}, {(void**)&p->d_src_pair, nullptr, m * 8, 0}, {(void**)&p->d_carry, nullptr, 8, 0},
-		{(void**)&p->d_scan_tmp, nullptr, (m / SCAN_TILE + 2) * 8, 0}, {(void**)&p->d_cnt_plain, nullptr, p->eqx ? m * 4 : 0, 0},
+		{(void**)&p->d_scan_tmp, nullptr, bsa_excl_scan_tmp_bytes((uint32_t)m), 0}, {(void**)&p->d_cnt_plain, nullptr, p->eqx ? m * 4 : 0, 0},
 	};
 	size_t total = 0, upload = 0;
 	for(Part &q : parts){ q.off = total; total += (std::max<size_t>(q.bytes, 8) + 255) & ~(size_t)255; if(q.src) upload = total; }
@@ -759,7 +656,7 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 		}
 		if(eqx) HIPCHK(c, bsa_launch_cigar_eqx_count(half, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_cnt_plain, es, stt));
 		if(want_cig && !direct){
-			HIPCHK(c, launch_excl_scan(stt, p->d_cnt_pos + ch.first, p->d_off_pos + ch.first, ch.count, p->d_carry, p->d_scan_tmp));
+			HIPCHK(c, bsa_launch_excl_scan(stt, p->d_cnt_pos + ch.first, p->d_off_pos + ch.first, ch.count, p->d_carry, p->d_scan_tmp));
 			if(eqx) HIPCHK(c, bsa_launch_cigar_collect_eqx(half, p->d_slot_end, ch.first, ch.count, p->d_cnt_pos, p->d_cnt_plain, p->d_off_pos, p->d_tmp, (uint64_t)cigar_cap_words, es, stt));
 			else hipLaunchKernelGGL(k_cigar_collect, dim3((ch.count + 3) / 4), dim3(256), 0, stt, half, p->d_slot_end,
 				ch.first, ch.count, p->d_cnt_pos, p->d_off_pos, p->d_tmp, (uint64_t)cigar_cap_words);
@@ -778,7 +675,7 @@ static int run_pipeline(PlanBase *p, bool want_cig, uint32_t *d_cigar, size_t ci
 	if(want_cig){
 		hipLaunchKernelGGL(k_cnt_by_pair, dim3((n + 255) / 256), dim3(256), 0, sf, p->d_order, p->d_cnt_pos, direct ? (const uint64_t*)nullptr : p->d_off_pos, p->d_cnt_pair, p->d_src_pair, n);
 		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, launch_excl_scan(sf, p->d_cnt_pair, d_cigar_off, n, (uint64_t*)nullptr, p->d_scan_tmp));
+		HIPCHK(c, bsa_launch_excl_scan(sf, p->d_cnt_pair, d_cigar_off, n, (uint64_t*)nullptr, p->d_scan_tmp));
 		if(direct && eqx) HIPCHK(c, bsa_launch_cigar_final_direct_eqx(c->ws, p->d_slot_end, p->d_cnt_pair, p->d_src_pair, p->d_cnt_plain, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n, es, sf));
 		else if(direct) hipLaunchKernelGGL(k_cigar_final_direct, dim3((n + 3) / 4), dim3(256), 0, sf, c->ws, p->d_slot_end, p->d_cnt_pair, p->d_src_pair, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n);
 		else hipLaunchKernelGGL(k_cigar_final, dim3((n + 3) / 4), dim3(256), 0, sf, p->d_tmp, p->d_cnt_pair, p->d_src_pair, d_cigar_off, d_cigar, (uint64_t)cigar_cap_words, n);

@@ -11,20 +11,14 @@
 // T = (target bases its words consume) steps from row to row; step s, inside word k at offset d = s - (target bases in front of k),
 // gives  enter of row tb + s  =  qs_k + d (M) or qs_k (D)  and  leave of row tb + s - 1  =  qs_k + d - 1 (M) or qs_k (D),  qs_k the query
 // position at which word k starts.  Words are taken in tiles of 64, a lane a word, with wave prefix sums of the bases they consume
-// (as in bsa_cigar_eqx.hip); the steps of a tile are then taken 64 at a time, a lane a step: a binary search over the tile's
+// (bsa_pass.h: bsa_wave_iscan and the rules of a CIGAR word, as in bsa_cigar_eqx.hip); the steps of a tile are then taken 64 at a time, a lane a step: a binary search over the tile's
 // inclusive target sums (six lane-indexed shuffles) finds the step's word -- two identical 10 kbp reads are ONE word and 157 such
 // trips, never one lane's loop -- and the lane reads begs[i] and begs[i - 1], coalesced over the wave.  The start vertex's row and
 // the last row's leave are added once a pair.  O(tlen + words) a pair; 4 bytes a row and the words are read once.
 //
 // No LDS allocation, no scratch; plain C++ with vector loads and stores only.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 
-static __device__ __forceinline__ uint32_t bm_iscan(uint32_t v, uint32_t lane){           // inclusive prefix sum over the wave
-#pragma unroll
-	for(uint32_t d = 1; d < 64u; d <<= 1){ const uint32_t u = __shfl_up(v, d); if(lane >= d) v += u; }
-	return v;
-}
-static __device__ __forceinline__ bool bm_diag(uint32_t op){ return op == BSA_CIGAR_M || op == BSA_CIGAR_EQ || op == BSA_CIGAR_X; }
 static __device__ __forceinline__ bool bm_is_ins(uint32_t w){ return (w & 15u) == BSA_CIGAR_I && (w >> 4) != 0u; }
 
 #define BM_NOTHING 0x7FFFFFFF
@@ -40,8 +34,8 @@ static __device__ __forceinline__ uint32_t bm_pair(const int *begs, const uint32
 		const uint32_t idx = w0 + lane;
 		const uint32_t w = idx < c ? src[idx] : 0u, nx = idx + 1u < c ? src[idx + 1u] : 0u;
 		const uint32_t op = w & 15u, len = w >> 4;
-		const uint32_t qa = (bm_diag(op) || op == BSA_CIGAR_I) ? len : 0u, ta = (bm_diag(op) || op == BSA_CIGAR_D) ? len : 0u;
-		const uint32_t qi = bm_iscan(qa, lane), ti = bm_iscan(ta, lane);
+		const uint32_t qa = bsa_cig_qadd(op, len), ta = bsa_cig_tadd(op, len);
+		const uint32_t qi = bsa_wave_iscan(qa, lane), ti = bsa_wave_iscan(ta, lane);
 		const uint32_t qs = qp + qi - qa, te = ti - ta;                                     // the word's query position / the tile's target steps in front of it
 		const uint32_t tile_t = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl(ti, 63));
 		for(uint32_t s0 = 0; s0 < tile_t; s0 += 64u){
@@ -53,7 +47,7 @@ static __device__ __forceinline__ uint32_t bm_pair(const int *begs, const uint32
 			const uint32_t i = tb + tp + sl;                                                // vertex row the step enters
 			if(sl <= tile_t && i <= tl){
 				const uint32_t d = sl - kt, klen = kw >> 4;
-				const bool dg = bm_diag(kw & 15u);
+				const bool dg = bsa_cig_diag(kw & 15u);
 				const uint32_t enter = dg ? kq + d : kq, leave = dg ? kq + d - 1u : kq;
 				const int bi = begs[i], bp = begs[i - 1u];
 				if(bi > 0){

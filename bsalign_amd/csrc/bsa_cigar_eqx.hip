@@ -1,15 +1,15 @@
 // bsa_cigar_eqx.hip -- BSA_MODE_CIGAR_EQX (include/bsalign_hip.h): every M word of a CIGAR split into the maximal runs of = and X.
 //
 // A pass over the words the traceback kernels left at the tails of their slots, not part of any walker: without the flag none of
-// these kernels is launched.  One wave a pair, in tiles of 64 words: lane i takes word i, a wave prefix sum of the bases the words
-// consume (seeded with the record's qb / tb) gives it its start positions in the staged 1 B/base copies, and it compares its M
+// these kernels is launched.  One wave a pair, in tiles of 64 words: lane i takes word i, a wave prefix sum (bsa_pass.h) of the bases the
+// words consume (seeded with the record's qb / tb; the input holds M, I and D words only, so the test here is op == M, not the wider bsa_cig_diag) gives it its start positions in the staged 1 B/base copies, and it compares its M
 // word's columns eight at a time.  k_cigar_eqx_count counts the expanded words (run_pipeline scans them into offsets); the EQX
 // forms of k_cigar_collect and k_cigar_final_direct repeat the walk and write each word's runs at the pair's offset plus an
 // exclusive prefix of the per-word counts.  The two walks are one function (eqx_walk<EMIT>), so they cannot disagree; the emitting
 // form still checks every index against the pair's counted total before it stores.
 //
 // No LDS, no scratch; plain C++ with vector loads and stores only.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 
 // An M word of up to EQX_LANE_COLS columns stays on its lane: its mismatch bits are one 64-bit mask, its runs a popcount.  A longer
 // word (two identical 10 kbp sequences are ONE word of 10 000 columns) is taken by the whole wave, EQX_TRIP_COLS columns a trip,
@@ -27,12 +27,6 @@ static __device__ __forceinline__ uint32_t eqx_mis8(const uint8_t *q, const uint
 	uint64_t x = a ^ b;
 	x = (x | (x >> 1)) & 0x0101010101010101ull;
 	return (((uint32_t)x * 0x01020408u) >> 24) | ((((uint32_t)(x >> 32) * 0x01020408u) >> 24) << 4);
-}
-
-static __device__ __forceinline__ uint32_t eqx_iscan(uint32_t v, uint32_t lane){         // inclusive prefix sum over the wave
-#pragma unroll
-	for(uint32_t d = 1; d < 64u; d <<= 1){ const uint32_t u = __shfl_up(v, d); if(lane >= d) v += u; }
-	return v;
 }
 
 static __device__ __forceinline__ uint32_t eqx_op(uint32_t mis){ return mis & 1u ? (uint32_t)BSA_CIGAR_X : (uint32_t)BSA_CIGAR_EQ; }
@@ -56,7 +50,7 @@ static __device__ __forceinline__ uint32_t eqx_long(const uint8_t *q, const uint
 		if(b == 0){ m0 = __shfl(bits, 0) & 1u; if(lane == 0) pb = bits & 1u; }        // (column 0 starts the first run and closes none)
 		uint32_t st = (bits ^ ((bits << 1) | pb)) & vm;
 		const uint32_t ns = __popc(st);
-		const uint32_t inc = eqx_iscan(ns, lane);
+		const uint32_t inc = bsa_wave_iscan(ns, lane);
 		const uint32_t tot = __shfl(inc, 63);
 		if(EMIT){
 			// the run a lane's first start closes began at the last start on a lower lane, or at rs (start columns grow with the lane: a running maximum)
@@ -96,7 +90,7 @@ static __device__ __forceinline__ uint32_t eqx_walk(const uint32_t *src, uint32_
 		const uint32_t w = have ? src[i] : 0u;
 		const uint32_t op = w & 15u, len = w >> 4;
 		const uint32_t qa = (op == BSA_CIGAR_M || op == BSA_CIGAR_I) ? len : 0u, ta = (op == BSA_CIGAR_M || op == BSA_CIGAR_D) ? len : 0u;
-		const uint32_t qi = eqx_iscan(qa, lane), ti = eqx_iscan(ta, lane);
+		const uint32_t qi = bsa_wave_iscan(qa, lane), ti = bsa_wave_iscan(ta, lane);
 		const uint32_t qs = qp + qi - qa, ts = tp + ti - ta;          // where this lane's word starts
 		qp += (uint32_t)__shfl(qi, 63); tp += (uint32_t)__shfl(ti, 63);
 		const bool isM = have && op == BSA_CIGAR_M && len != 0u && qs <= ql && ts <= tl && len <= ql - qs && len <= tl - ts;
@@ -111,7 +105,7 @@ static __device__ __forceinline__ uint32_t eqx_walk(const uint32_t *src, uint32_
 			nrun = 1u + (uint32_t)__popcll(st);
 		}
 		if(lng) nrun = 0u;                                            // (counted below, by the wave)
-		const uint32_t inc = eqx_iscan(nrun, lane);
+		const uint32_t inc = bsa_wave_iscan(nrun, lane);
 		const uint32_t eo = inc - nrun, tile_short = __shfl(inc, 63);
 		uint32_t extra = 0, long_total = 0;                           // runs of long words on lower lanes / in this tile
 		uint64_t lm = __ballot(lng);

@@ -4,9 +4,9 @@
 // A pass over the PUBLIC outputs of a run -- the records, the CIGAR arena and its offsets -- and nothing else: it knows no plan, no slot and
 // no walker, so it serves both aligners, plain and = / X words, stranded pairs and every kernel route.  Three steps on the context stream:
 //   count : one thread a pair reads the record and its two offsets, cnt[k] = the pair's windows (k_cigar_windows_count);
-//   scan  : the 64-bit exclusive scan of bsa_api.hip into the caller's d_win_off;
+//   scan  : the 64-bit exclusive scan of bsa_scan.hip into the caller's d_win_off;
 //   fill  : one wave a pair (k_cigar_windows_fill).  Words in tiles of 64, a lane a word, wave prefix sums give every lane the target and
-//           query position at its word (as in bsa_cigar_eqx.hip and bsa_band_margin.hip).  `pe`, the last diagonal column seen so far, is
+//           query position at its word (bsa_pass.h, as in bsa_cigar_eqx.hip and bsa_band_margin.hip).  `pe`, the last diagonal column seen so far, is
 //           carried from tile to tile; inside a tile a diagonal word finds its predecessor's last column with one ballot and two lane-indexed
 //           shuffles.  A diagonal word that starts in a later window than its predecessor ends writes `last` of that window, NONE into
 //           the windows in between and `first` of its own; the pair's first diagonal word writes NONE into the windows in front of it;
@@ -16,29 +16,11 @@
 // Target positions are summed in 64 bits (64 words of 2^28 bases overflow 32), query positions wrap in 32: they are never compared.
 //
 // No LDS in the count and fill kernels, no scratch; plain C++ with vector loads and stores only.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 #include <algorithm>
 #include <vector>
 
-extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
-extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
-extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *ctx, const char *msg);
-hipError_t bsa_launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *tmp);      // bsa_api.hip; tmp: bsa_excl_scan_tmp_bytes(n)
-size_t bsa_excl_scan_tmp_bytes(uint32_t n);
-
 #define CW_T_LIMIT 0x80000000ull     // a record's target positions are int32: a column at or above 2^31 belongs to no window
-
-static __device__ __forceinline__ uint32_t cw_iscan(uint32_t v, uint32_t lane){           // inclusive prefix sums over the wave
-#pragma unroll
-	for(uint32_t d = 1; d < 64u; d <<= 1){ const uint32_t u = __shfl_up(v, d); if(lane >= d) v += u; }
-	return v;
-}
-static __device__ __forceinline__ uint64_t cw_iscan64(uint64_t v, uint32_t lane){
-#pragma unroll
-	for(uint32_t d = 1; d < 64u; d <<= 1){ const uint64_t u = __shfl_up(v, d); if(lane >= d) v += u; }
-	return v;
-}
-static __device__ __forceinline__ bool cw_diag(uint32_t op){ return op == BSA_CIGAR_M || op == BSA_CIGAR_EQ || op == BSA_CIGAR_X; }
 
 // the windows of one pair (the definition's "window count"); c: its words
 static __device__ __forceinline__ uint32_t cw_count(int32_t tb, int32_t te, uint64_t c, uint32_t w){
@@ -89,11 +71,11 @@ __global__ void __launch_bounds__(256) k_cigar_windows_fill(const bsa_result_t *
 		const uint64_t idx = w0 + lane;
 		const uint32_t word = idx < c ? src[idx] : 0u;
 		const uint32_t op = word & 15u, len = word >> 4;
-		const bool dg = cw_diag(op);
-		const uint32_t qa = (dg || op == BSA_CIGAR_I) ? len : 0u;
-		const uint64_t ta = (dg || op == BSA_CIGAR_D) ? len : 0u;
-		const uint32_t qi = cw_iscan(qa, lane);
-		const uint64_t ti = cw_iscan64(ta, lane);
+		const bool dg = bsa_cig_diag(op);
+		const uint32_t qa = bsa_cig_qadd(op, len);
+		const uint64_t ta = bsa_cig_tadd<uint64_t>(op, len);
+		const uint32_t qi = bsa_wave_iscan(qa, lane);
+		const uint64_t ti = bsa_wave_iscan(ta, lane);
 		const uint64_t ts64 = tp + ti - ta;                    // where this lane's word starts
 		const uint32_t qs = qp + qi - qa;
 		const bool act = dg && len != 0u && ts64 < lim;        // a word with a column that counts
@@ -149,13 +131,13 @@ extern "C" uint64_t bsa_cigar_windows_bound(const uint32_t *tlen, size_t n, uint
 
 // count and scan: d_win_off[0 .. n] on the stream; *cnt_out: the counts in the context's scratch
 static int cw_offsets(bsa_ctx_t *ctx, hipStream_t stream, const bsa_result_t *d_out, const uint64_t *d_cigar_off, size_t n, uint32_t window, uint64_t *d_win_off){
-	const size_t o_tmp = ((n * 4u) + 255u) & ~(size_t)255u;
+	const size_t o_tmp = bsa_up256(n * 4u);
 	void *bufv = nullptr;
 	int rc = bsa_ctx_scratch_internal(ctx, 1, o_tmp + bsa_excl_scan_tmp_bytes((uint32_t)n), &bufv);      // (waits for the stream only when it has to grow)
 	if(rc != BSA_OK) return rc;
 	uint32_t *cnt = (uint32_t*)bufv;
 	if(n) hipLaunchKernelGGL(k_cigar_windows_count, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, d_out, d_cigar_off, (uint32_t)n, window, cnt);
-	if(hipGetLastError() != hipSuccess || bsa_launch_excl_scan(stream, cnt, d_win_off, (uint32_t)n, (uint64_t*)((uint8_t*)bufv + o_tmp)) != hipSuccess){
+	if(hipGetLastError() != hipSuccess || bsa_launch_excl_scan(stream, cnt, d_win_off, (uint32_t)n, nullptr, (uint64_t*)((uint8_t*)bufv + o_tmp)) != hipSuccess){
 		(void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_cigar_windows: launch failed"); return BSA_E_HIP;
 	}
 	return BSA_OK;
@@ -188,38 +170,28 @@ extern "C" int bsa_cigar_windows_batch(bsa_ctx_t *ctx, const bsa_result_t *out, 
 	if(!win_off || (n && (!out || !cigar_off)) || (win_cap && !win)){ bsa_ctx_set_error_internal(ctx, "bsa_cigar_windows_batch: null argument"); return BSA_E_ARG; }
 	if(n > 0xFFFFFFF0ull){ bsa_ctx_set_error_internal(ctx, "too many pairs"); return BSA_E_ARG; }
 	if(n == 0){ win_off[0] = 0; return BSA_OK; }
-	for(size_t k = 0; k < n; k++) if(cigar_off[k + 1] < cigar_off[k]){ bsa_ctx_set_error_internal(ctx, "bsa_cigar_windows_batch: cigar_off decreases"); return BSA_E_ARG; }
-	const uint64_t w0 = cigar_off[0], words = cigar_off[n] - w0;          // only the words the offsets speak of go up
+	std::vector<uint64_t> coff;
+	int rc = bsa_rebase_offsets(ctx, cigar_off, n, coff, "bsa_cigar_windows_batch: cigar_off decreases");
+	if(rc != BSA_OK) return rc;
+	const uint64_t w0 = cigar_off[0], words = coff[n];                    // only the words the offsets speak of go up
 	if(words && !cigar){ bsa_ctx_set_error_internal(ctx, "bsa_cigar_windows_batch: null argument"); return BSA_E_ARG; }
 	hipStream_t stream;
-	int rc = bsa_ctx_get_stream_internal(ctx, &stream);
-	if(rc != BSA_OK) return rc;
-	auto up = [](size_t b){ return (b + 255u) & ~(size_t)255u; };
-	const size_t o_out = 0, o_coff = o_out + up(n * sizeof(bsa_result_t)), o_woff = o_coff + up((n + 1) * 8), o_cig = o_woff + up((n + 1) * 8), total = o_cig + up(words * 4 + 4);
-	uint8_t *buf = nullptr, *d_win = nullptr;
-	auto fail = [&](const char *what, int code){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, what); rc = code; };
-	std::vector<uint64_t> coff;
-	try { coff.resize(n + 1); } catch(...){ return BSA_E_NOMEM; }
-	for(size_t k = 0; k <= n; k++) coff[k] = cigar_off[k] - w0;
-	do {
-		if(hipMalloc((void**)&buf, total) != hipSuccess){ buf = nullptr; fail("bsa_cigar_windows_batch: no device memory for the records and words", BSA_E_NOMEM); break; }
-		if(hipMemcpyAsync(buf + o_out, out, n * sizeof(bsa_result_t), hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_coff, coff.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| (words && hipMemcpyAsync(buf + o_cig, cigar + w0, words * 4, hipMemcpyHostToDevice, stream) != hipSuccess)){ fail("bsa_cigar_windows_batch: upload failed", BSA_E_HIP); break; }
-		const bsa_result_t *d_out = (const bsa_result_t*)(buf + o_out);
-		const uint64_t *d_coff = (const uint64_t*)(buf + o_coff);
-		uint64_t *d_woff = (uint64_t*)(buf + o_woff);
-		if((rc = cw_offsets(ctx, stream, d_out, d_coff, n, window, d_woff)) != BSA_OK) break;
-		if(hipMemcpyAsync(win_off, d_woff, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_cigar_windows_batch: download of the offsets failed", BSA_E_HIP); break; }
-		const uint64_t need = win_off[n];
-		if(need > win_cap){ bsa_ctx_set_error_internal(ctx, "bsa_cigar_windows_batch: win_cap too small, win_off[n] holds the records needed"); rc = BSA_E_CIGAR_CAP; break; }
-		if(need == 0) break;
-		if(hipMalloc((void**)&d_win, need * sizeof(bsa_window_t)) != hipSuccess){ d_win = nullptr; fail("bsa_cigar_windows_batch: no device memory for the windows", BSA_E_NOMEM); break; }
-		if((rc = cw_fill(ctx, stream, d_out, (const uint32_t*)(buf + o_cig), d_coff, n, window, (bsa_window_t*)d_win, need, d_woff)) != BSA_OK) break;
-		if(hipMemcpyAsync(win, d_win, need * sizeof(bsa_window_t), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_cigar_windows_batch: download of the windows failed", BSA_E_HIP); break; }
-	} while(0);
-	if(rc != BSA_OK && rc != BSA_E_CIGAR_CAP) (void)hipStreamSynchronize(stream);      // nothing of the call is in flight when its buffers go
-	if(d_win) (void)hipFree(d_win);
-	if(buf) (void)hipFree(buf);
-	return rc;
+	if((rc = bsa_ctx_get_stream_internal(ctx, &stream)) != BSA_OK) return rc;
+	bsa_stage_t in(ctx, stream), res(ctx, stream);
+	const size_t o_out = in.part(n * sizeof(bsa_result_t)), o_coff = in.part((n + 1) * 8), o_woff = in.part((n + 1) * 8), o_cig = in.part(words * 4 + 4);
+	if((rc = in.alloc("bsa_cigar_windows_batch: no device memory for the records and words")) != BSA_OK) return rc;
+	if(!in.up(o_out, out, n * sizeof(bsa_result_t)) || !in.up(o_coff, coff.data(), (n + 1) * 8) || !in.up(o_cig, words ? cigar + w0 : nullptr, words * 4)) return in.fail("bsa_cigar_windows_batch: upload failed");
+	const bsa_result_t *d_out = in.at<bsa_result_t>(o_out);
+	const uint64_t *d_coff = in.at<uint64_t>(o_coff);
+	uint64_t *d_woff = in.at<uint64_t>(o_woff);
+	if((rc = cw_offsets(ctx, stream, d_out, d_coff, n, window, d_woff)) != BSA_OK) return rc;
+	if(!in.down(win_off, o_woff, (n + 1) * 8) || !in.sync()) return in.fail("bsa_cigar_windows_batch: download of the offsets failed");
+	const uint64_t need = win_off[n];                                     // (the offsets are down before the capacity is judged)
+	if(need > win_cap) return in.fail("bsa_cigar_windows_batch: win_cap too small, win_off[n] holds the records needed", BSA_E_CIGAR_CAP);
+	if(need == 0) return BSA_OK;
+	const size_t o_win = res.part(need * sizeof(bsa_window_t));
+	if((rc = res.alloc("bsa_cigar_windows_batch: no device memory for the windows")) != BSA_OK) return rc;
+	if((rc = cw_fill(ctx, stream, d_out, in.at<uint32_t>(o_cig), d_coff, n, window, res.at<bsa_window_t>(o_win), need, d_woff)) != BSA_OK) return rc;
+	if(!res.down(win, o_win, need * sizeof(bsa_window_t)) || !res.sync()) return res.fail("bsa_cigar_windows_batch: download of the windows failed");
+	return BSA_OK;
 }

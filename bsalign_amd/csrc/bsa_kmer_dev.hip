@@ -35,7 +35,7 @@
 // called once per strand: the forward pass keeps its hits in the 8 min(qlen, tlen) extra bytes behind the slice's halves so that the sorted records
 // survive it, its anchors then move there, and the reverse pass runs with the layout of the other kernels.  Reverse exactly when it has MORE anchors;
 // a pair with a base code above 3 is chained forward only.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -44,9 +44,6 @@
 #include <thread>
 #include <vector>
 
-extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
-extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
-extern "C" size_t bsa_ctx_workspace_limit_internal(bsa_ctx_t *ctx);
 
 #define KC_THREADS   256
 #define KC_BITS      5u                  // radix digit
@@ -405,7 +402,6 @@ __global__ __launch_bounds__(KC_THREADS) void k_kmer_gather(const uint8_t *__res
 // the largest pair the device route takes (qlen + tlen); longer pairs are chained by the host code in the same call
 extern "C" uint32_t bsa_kmer_dev_max_internal(void){ return 1u << 18; }
 
-static inline size_t kc_up(size_t x){ return (x + 255u) & ~(size_t)255u; }
 static uint32_t kc_min_cover(uint32_t qlen, uint32_t tlen, uint32_t ksz){       // bsa_kmer.cpp: min_cover (double arithmetic on the host, as there)
 	uint32_t c = (uint32_t)(std::min(qlen, tlen) * 0.05 + 1);
 	return std::min(c, 2 * ksz);
@@ -506,14 +502,14 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 		}
 		// carve the scratch
 		size_t o = 0;
-		const size_t o_seq = o;  o += kc_up(seqb + 16);
-		const size_t o_meta = o; o += kc_up(c * sizeof(KcPair));
-		const size_t o_cnt = o;  o += kc_up(c * 4);
-		const size_t o_off = o;  o += kc_up((c + 1) * 4);
-		const size_t o_st = o;   o += kc_up(c * 4);
-		const size_t o_res = o;  o += kc_up(c * 8);
-		const size_t o_ar = o;   o += kc_up((acap + 1) * 8);
-		const size_t o_ws = o;   o += kc_up(slots + 16);
+		const size_t o_seq = o;  o += bsa_up256(seqb + 16);
+		const size_t o_meta = o; o += bsa_up256(c * sizeof(KcPair));
+		const size_t o_cnt = o;  o += bsa_up256(c * 4);
+		const size_t o_off = o;  o += bsa_up256((c + 1) * 4);
+		const size_t o_st = o;   o += bsa_up256(c * 4);
+		const size_t o_res = o;  o += bsa_up256(c * 8);
+		const size_t o_ar = o;   o += bsa_up256((acap + 1) * 8);
+		const size_t o_ws = o;   o += bsa_up256(slots + 16);
 		void *bufv = nullptr;
 		if((rc = bsa_ctx_scratch_internal(ctx, 1, o, &bufv)) != BSA_OK) break;
 		uint8_t *buf = (uint8_t*)bufv;
@@ -554,8 +550,6 @@ extern "C" int bsa_kmer_chain_dev_internal(bsa_ctx_t *ctx, const uint8_t *seqs, 
 // The same k_kmer_chain kernels read the CALLER's device blob in place (KcPair.qoff / toff are the caller's offsets), the pair tables go up once when the
 // plan is made, and a run is launches on the context stream and nothing else: per workspace chunk the chain kernel, k_kmer_scan_carry and
 // k_kmer_gather_whole, which writes straight into the caller's arena.  Stream order is all that keeps chunk c + 1 from the slices chunk c still gathers from.
-extern "C" int bsa_ctx_kmer_chain_events_internal(bsa_ctx_t *ctx, size_t chunks, long on_device, hipEvent_t **ev);
-extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *ctx, const char *msg);
 
 // (f) for a chunk of a plan: the exclusive scan of its counts in 64 bits, carried from chunk to chunk through the caller's array.  `off` points at the chunk's
 // first entry: off[0] is what the chunk before wrote there as its total (the first chunk writes the 0 itself), off[i + 1] = off[0] + cnt[0] + .. + cnt[i].
@@ -599,8 +593,8 @@ struct bsa_kmer_chain_plan {
 	size_t scratch = 0;                                       // bytes of the context's scratch the largest chunk asks for
 };
 // a chunk's carve of the scratch: counts, result offsets, slices
-static inline size_t kc_plan_o_res(size_t c){ return kc_up(c * 4); }
-static inline size_t kc_plan_o_ws(size_t c){ return kc_plan_o_res(c) + kc_up(c * 8); }
+static inline size_t kc_plan_o_res(size_t c){ return bsa_up256(c * 4); }
+static inline size_t kc_plan_o_ws(size_t c){ return kc_plan_o_res(c) + bsa_up256(c * 8); }
 
 extern "C" uint64_t bsa_kmer_chain_words_bound(const uint32_t *qlen, const uint32_t *tlen, size_t n){
 	uint64_t w = 0;
@@ -662,7 +656,7 @@ static int kc_plan_create(bsa_ctx_t *ctx, const uint64_t *qoff, const uint32_t *
 			j1 ++;
 		}
 		p->chunks.push_back(KcChunk{ j0, j1, slots });
-		p->scratch = std::max(p->scratch, kc_plan_o_ws(j1 - j0) + kc_up(slots + 16));
+		p->scratch = std::max(p->scratch, kc_plan_o_ws(j1 - j0) + bsa_up256(slots + 16));
 		j0 = j1;
 	}
 	if(n){

@@ -12,7 +12,7 @@
 //           t_first, tests q there, goes on to the word that holds t_last counting the words kept with a ballot and a popcount a step, and tests q
 //           again.  It leaves the count, the first and the last word, the two in-word offsets and where the pair's words are (32 bytes) and the
 //           status.  Groups at or above P = min(*d_npiece, piece_cap) leave a count of 0, so that
-//   scan  : the 64-bit exclusive scan of bsa_api.hip over all piece_cap counts writes every offset, those above P included;
+//   scan  : the 64-bit exclusive scan of bsa_scan.hip over all piece_cap counts writes every offset, those above P included;
 //   fill  : 16 lanes a piece whose range ends inside the arena (k_piece_cigars_fill) copy from the first word to the last, clip both, and compact
 //           dropped words away with a ballot prefix.
 // A piece of a polisher's window is a few hundred bytes of work, and whoever does it mostly waits for loads.  So count and fill put four pieces into
@@ -22,15 +22,9 @@
 // first word lies in to its last word, twice (count and fill).  Where the piece lies inside its pair does not matter while stride is 1.
 // Target positions are summed in 64 bits, query positions wrap in 32.  No LDS, no atomics; plain C++ with vector loads and stores, DPP row moves
 // (bsa_dpp.h) and wave intrinsics only.
-#include "bsa_common.h"
+#include "bsa_pass.h"
 #include "bsa_dpp.h"
 #include <vector>
-
-extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
-extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
-extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *ctx, const char *msg);
-hipError_t bsa_launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *tmp);      // bsa_api.hip; tmp: bsa_excl_scan_tmp_bytes(n)
-size_t bsa_excl_scan_tmp_bytes(uint32_t n);
 
 #define PCG_SAMPLES 32u            // index places a pair (32: a lane of a group of 16 reads two)
 #ifndef PCG_INDEX_TILES
@@ -44,20 +38,15 @@ size_t bsa_excl_scan_tmp_bytes(uint32_t n);
 struct pcg_info_t { uint32_t x, a, b, cnt; uint64_t c0; uint32_t c, y; };
 static_assert(sizeof(pcg_info_t) == 32 && sizeof(bsa_piece_t) == 32, "32 bytes of scratch a piece; bsa_piece_t is 32 bytes");
 
-// Sums without the LDS crossbar: prefix sums inside a DPP row of 16 lanes with four DPP moves; a row's total is its lane 15.  A word's length is below
-// 2^28, so 64 of them sum to less than 2^34: where target lengths are summed, the low 20 and the high 8 bits are summed apart, each in 32 bits.
-static __device__ __forceinline__ uint32_t pcg_row_iscan(uint32_t x){                      // (all lanes of the row active)
-	x += (uint32_t)DPP_SHR(0, (int)x, 1); x += (uint32_t)DPP_SHR(0, (int)x, 2); x += (uint32_t)DPP_SHR(0, (int)x, 4); x += (uint32_t)DPP_SHR(0, (int)x, 8);
-	return x;
-}
+// Sums without the LDS crossbar: prefix sums inside a DPP row of 16 lanes with four DPP moves (row_iscan16 of bsa_dpp.h, all lanes of the row active);
+// a row's total is its lane 15.  A word's length is below 2^28, so 64 of them sum to less than 2^34: where target lengths are summed, the low 20 and
+// the high 8 bits are summed apart, each in 32 bits.
 static __device__ __forceinline__ uint32_t pcg_lane(uint32_t v, int l){ return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 static __device__ __forceinline__ uint32_t pcg_sum(uint32_t v){                            // the sum over the wave, modulo 2^32, in scalar registers (all 64 lanes active)
-	const uint32_t x = pcg_row_iscan(v);
+	const uint32_t x = (uint32_t)row_iscan16((int)v);
 	return pcg_lane(x, 15) + pcg_lane(x, 31) + pcg_lane(x, 47) + pcg_lane(x, 63);
 }
 static __device__ __forceinline__ uint64_t pcg_sum_len(uint32_t v){ return (uint64_t)pcg_sum(v & 0xFFFFFu) + ((uint64_t)pcg_sum(v >> 20) << 20); }
-static __device__ __forceinline__ bool pcg_diag(uint32_t op){ return op == BSA_CIGAR_M || op == BSA_CIGAR_EQ || op == BSA_CIGAR_X; }
-static __device__ __forceinline__ bool pcg_steps(uint32_t op){ return pcg_diag(op) || op == BSA_CIGAR_I || op == BSA_CIGAR_D; }
 
 // the words of pair k, 0 where it has no alignment to cut: tb < 0, no words, offsets that decrease, too many words
 static __device__ __forceinline__ uint64_t pcg_words(const bsa_result_t *out, const uint64_t *coff, uint32_t k){
@@ -93,9 +82,8 @@ __global__ void __launch_bounds__(256) k_piece_cigars_index(const bsa_result_t *
 				next += stride; s++;
 			}
 			const uint32_t op = word[u] & 15u, len = word[u] >> 4;
-			const bool dg = pcg_diag(op);
-			qp += pcg_sum((dg || op == BSA_CIGAR_I) ? len : 0u);
-			tp += pcg_sum_len((dg || op == BSA_CIGAR_D) ? len : 0u);
+			qp += pcg_sum(bsa_cig_qadd(op, len));
+			tp += pcg_sum_len(bsa_cig_tadd(op, len));
 		}
 	}
 }
@@ -146,9 +134,9 @@ __global__ void __launch_bounds__(256) k_piece_cigars_count(const bsa_result_t *
 						if(tp > tl){ stop = true; break; }                     // behind the last column
 						const uint64_t i = w0 + 16u * u + gl;
 						const uint32_t op = word[u] & 15u, len = word[u] >> 4;
-						const bool dg = pcg_diag(op);
-						const uint32_t qa = (dg || op == BSA_CIGAR_I) ? len : 0u, ta = (dg || op == BSA_CIGAR_D) ? len : 0u;
-						const uint32_t qi = pcg_row_iscan(qa), tlo = pcg_row_iscan(ta & 0xFFFFFu), thi = pcg_row_iscan(ta >> 20);
+						const bool dg = bsa_cig_diag(op);
+						const uint32_t qa = bsa_cig_qadd(op, len), ta = bsa_cig_tadd(op, len);
+						const uint32_t qi = (uint32_t)row_iscan16((int)qa), tlo = (uint32_t)row_iscan16((int)(ta & 0xFFFFFu)), thi = (uint32_t)row_iscan16((int)(ta >> 20));
 						const uint64_t ti = (uint64_t)tlo + ((uint64_t)thi << 20);
 						const uint64_t tn = tp + (uint64_t)pcg_row_total(tlo) + ((uint64_t)pcg_row_total(thi) << 20);      // behind the 16 words
 						const uint64_t ts = tp + ti - ta;                      // where this lane's word starts
@@ -166,7 +154,7 @@ __global__ void __launch_bounds__(256) k_piece_cigars_count(const bsa_result_t *
 						if(havex){
 							const uint32_t hit = pcg_grp(__ballot(col && ts <= tl && tl - ts < len), sh);
 							const int ly = hit != 0u ? __ffs((int)hit) - 1 : 15;
-							kept += (uint32_t)__popc(pcg_grp(__ballot(pcg_steps(op) && len != 0u && i >= x && gl <= (uint32_t)ly), sh));
+							kept += (uint32_t)__popc(pcg_grp(__ballot(bsa_cig_steps(op) && len != 0u && i >= x && gl <= (uint32_t)ly), sh));
 							if(hit != 0u){
 								const uint32_t d = (uint32_t)(tl - ts);
 								if(__shfl(qs + d, (int)sh + ly) == ql){
@@ -211,7 +199,7 @@ __global__ void __launch_bounds__(256) k_piece_cigars_fill(const uint32_t *cigar
 #pragma unroll
 			for(int u = 0; u < 4; u++){
 				const uint32_t op = word[u] & 15u, len = word[u] >> 4;
-				const bool keep = pcg_steps(op) && len != 0u;
+				const bool keep = bsa_cig_steps(op) && len != 0u;
 				const uint32_t m = (uint32_t)(__ballot(keep) >> sh) & 0xFFFFu;
 				const uint32_t at = done + (uint32_t)__popc(m & ((1u << gl) - 1u));
 				if(keep && at < r.cnt){
@@ -234,9 +222,8 @@ extern "C" uint64_t bsa_piece_cigars_bound(const uint64_t *cigar_off, size_t n, 
 // the pass's part of the context's scratch: cnt | the scan's tiles | info | idx
 struct pcg_scratch_t { uint32_t *cnt; uint64_t *tmp; pcg_info_t *info; uint4 *idx; };
 static int pcg_scratch(bsa_ctx_t *ctx, size_t n, size_t piece_cap, pcg_scratch_t *s){
-	auto up = [](size_t b){ return (b + 255u) & ~(size_t)255u; };
-	const size_t o_cnt = 0, o_tmp = o_cnt + up(piece_cap * 4u), o_info = o_tmp + up(bsa_excl_scan_tmp_bytes((uint32_t)piece_cap)), o_idx = o_info + up(piece_cap * sizeof(pcg_info_t)),
-		total = o_idx + up(n * PCG_SAMPLES * sizeof(uint4));
+	const size_t o_cnt = 0, o_tmp = o_cnt + bsa_up256(piece_cap * 4u), o_info = o_tmp + bsa_up256(bsa_excl_scan_tmp_bytes((uint32_t)piece_cap)),
+		o_idx = o_info + bsa_up256(piece_cap * sizeof(pcg_info_t)), total = o_idx + bsa_up256(n * PCG_SAMPLES * sizeof(uint4));
 	void *bufv = nullptr;
 	const int rc = bsa_ctx_scratch_internal(ctx, 1, total, &bufv);      // (waits for the stream only when it has to grow)
 	if(rc != BSA_OK) return rc;
@@ -256,13 +243,12 @@ static int pcg_launch(bsa_ctx_t *ctx, hipStream_t st, const pcg_in_t &a, const p
 		hipLaunchKernelGGL(k_piece_cigars_index, pairs, block, 0, st, a.out, a.cigar, a.coff, a.n, s.idx);
 		e = hipGetLastError();
 	}
-	const uint64_t want = ((uint64_t)a.piece_cap + 15u) / 16u, most = (uint64_t)bsa_cus() * 16u;          // count and fill: 16 pieces a block and trip
-	const dim3 pieces((uint32_t)(want < most ? want : most));
+	const dim3 pieces = bsa_grid16(a.piece_cap);               // count and fill
 	if(e == hipSuccess && (steps & PCG_COUNT) && a.piece_cap){
 		hipLaunchKernelGGL(k_piece_cigars_count, pieces, block, 0, st, a.out, a.cigar, a.coff, a.n, a.piece, a.npiece, a.piece_cap, (const uint4*)s.idx, s.cnt, s.info, d_pstatus);
 		e = hipGetLastError();
 	}
-	if(e == hipSuccess && (steps & PCG_SCAN)) e = bsa_launch_excl_scan(st, s.cnt, d_pcig_off, a.piece_cap, s.tmp);
+	if(e == hipSuccess && (steps & PCG_SCAN)) e = bsa_launch_excl_scan(st, s.cnt, d_pcig_off, a.piece_cap, nullptr, s.tmp);
 	if(e == hipSuccess && (steps & PCG_FILL) && a.n && a.piece_cap && pcig_cap){
 		hipLaunchKernelGGL(k_piece_cigars_fill, pieces, block, 0, st, a.cigar, a.npiece, a.piece_cap, (const pcg_info_t*)s.info, (const uint64_t*)d_pcig_off, d_pcig, (uint64_t)pcig_cap);
 		e = hipGetLastError();
@@ -313,8 +299,9 @@ extern "C" int bsa_piece_cigars_batch(bsa_ctx_t *ctx, const bsa_result_t *out, c
 	if(!ctx) return BSA_E_ARG;
 	int rc = pcg_check(ctx, out, cigar_off, n, piece, npiece, pcig, pcig_cap, pcig_off);
 	if(rc != BSA_OK) return rc;
-	for(size_t k = 0; k < n; k++) if(cigar_off[k + 1] < cigar_off[k]){ bsa_ctx_set_error_internal(ctx, "bsa_piece_cigars_batch: cigar_off decreases"); return BSA_E_ARG; }
-	const uint64_t w0 = n ? cigar_off[0] : 0ull, words = n ? cigar_off[n] - w0 : 0ull;          // only the words the offsets speak of go up
+	std::vector<uint64_t> coff;
+	if((rc = bsa_rebase_offsets(ctx, cigar_off, n, coff, "bsa_piece_cigars_batch: cigar_off decreases")) != BSA_OK) return rc;
+	const uint64_t w0 = n ? cigar_off[0] : 0ull, words = coff[n], np64 = npiece;          // only the words the offsets speak of go up
 	if(words && !cigar){ bsa_ctx_set_error_internal(ctx, "bsa_piece_cigars_batch: null argument"); return BSA_E_ARG; }
 	if(n == 0 || npiece == 0){                                 // no alignment, or nothing to cut
 		for(size_t j = 0; j <= npiece; j++) pcig_off[j] = 0;
@@ -323,41 +310,24 @@ extern "C" int bsa_piece_cigars_batch(bsa_ctx_t *ctx, const bsa_result_t *out, c
 	}
 	hipStream_t stream;
 	if((rc = bsa_ctx_get_stream_internal(ctx, &stream)) != BSA_OK) return rc;
-	auto up = [](size_t b){ return (b + 255u) & ~(size_t)255u; };
-	const size_t o_out = 0, o_coff = o_out + up(n * sizeof(bsa_result_t)), o_np = o_coff + up((n + 1) * 8), o_poff = o_np + 256u, o_st = o_poff + up((npiece + 1) * 8),
-		o_piece = o_st + up(npiece * 4), o_cig = o_piece + up(npiece * sizeof(bsa_piece_t)), total = o_cig + up(words * 4 + 4);
-	uint8_t *buf = nullptr, *d_pcig = nullptr;
-	auto fail = [&](const char *what, int code){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, what); rc = code; };
-	std::vector<uint64_t> coff;
-	try { coff.resize(n + 2); } catch(...){ return BSA_E_NOMEM; }
-	for(size_t k = 0; k <= n; k++) coff[k] = cigar_off[k] - w0;
-	coff[n + 1] = npiece;                                      // (the piece count goes up behind the offsets; it lives at o_np on the device)
-	do {
-		if(hipMalloc((void**)&buf, total) != hipSuccess){ buf = nullptr; fail("bsa_piece_cigars_batch: no device memory for the records, words and pieces", BSA_E_NOMEM); break; }
-		if(hipMemcpyAsync(buf + o_out, out, n * sizeof(bsa_result_t), hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_coff, coff.data(), (n + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_np, coff.data() + n + 1, 8, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_piece, piece, npiece * sizeof(bsa_piece_t), hipMemcpyHostToDevice, stream) != hipSuccess
-				|| (words && hipMemcpyAsync(buf + o_cig, cigar + w0, words * 4, hipMemcpyHostToDevice, stream) != hipSuccess)){ fail("bsa_piece_cigars_batch: upload failed", BSA_E_HIP); break; }
-		const pcg_in_t a = { (const bsa_result_t*)(buf + o_out), (const uint32_t*)(buf + o_cig), (const uint64_t*)(buf + o_coff), (uint32_t)n,
-			(const bsa_piece_t*)(buf + o_piece), (const uint64_t*)(buf + o_np), (uint32_t)npiece };
-		uint64_t *d_poff = (uint64_t*)(buf + o_poff);
-		uint32_t *d_st = (uint32_t*)(buf + o_st);
-		pcg_scratch_t s;
-		if((rc = pcg_scratch(ctx, n, npiece, &s)) != BSA_OK) break;
-		if((rc = pcg_launch(ctx, stream, a, s, PCG_INDEX | PCG_COUNT | PCG_SCAN, nullptr, 0, d_poff, d_st)) != BSA_OK) break;
-		if(hipMemcpyAsync(pcig_off, d_poff, (npiece + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| (pstatus && hipMemcpyAsync(pstatus, d_st, npiece * 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
-				|| hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_piece_cigars_batch: download of the offsets failed", BSA_E_HIP); break; }
-		const uint64_t need = pcig_off[npiece];
-		if(need > pcig_cap){ bsa_ctx_set_error_internal(ctx, "bsa_piece_cigars_batch: pcig_cap too small, pcig_off[npiece] holds the words needed"); rc = BSA_E_CIGAR_CAP; break; }
-		if(need == 0) break;
-		if(hipMalloc((void**)&d_pcig, need * 4) != hipSuccess){ d_pcig = nullptr; fail("bsa_piece_cigars_batch: no device memory for the words", BSA_E_NOMEM); break; }
-		if((rc = pcg_launch(ctx, stream, a, s, PCG_FILL, (uint32_t*)d_pcig, need, d_poff, nullptr)) != BSA_OK) break;
-		if(hipMemcpyAsync(pcig, d_pcig, need * 4, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_piece_cigars_batch: download of the words failed", BSA_E_HIP); break; }
-	} while(0);
-	if(rc != BSA_OK && rc != BSA_E_CIGAR_CAP) (void)hipStreamSynchronize(stream);      // nothing of the call is in flight when its buffers go
-	if(d_pcig) (void)hipFree(d_pcig);
-	if(buf) (void)hipFree(buf);
-	return rc;
+	bsa_stage_t in(ctx, stream), res(ctx, stream);
+	const size_t o_out = in.part(n * sizeof(bsa_result_t)), o_coff = in.part((n + 1) * 8), o_np = in.part(8), o_poff = in.part((npiece + 1) * 8), o_st = in.part(npiece * 4),
+		o_piece = in.part(npiece * sizeof(bsa_piece_t)), o_cig = in.part(words * 4 + 4);
+	if((rc = in.alloc("bsa_piece_cigars_batch: no device memory for the records, words and pieces")) != BSA_OK) return rc;
+	if(!in.up(o_out, out, n * sizeof(bsa_result_t)) || !in.up(o_coff, coff.data(), (n + 1) * 8) || !in.up(o_np, &np64, 8) || !in.up(o_piece, piece, npiece * sizeof(bsa_piece_t))
+			|| !in.up(o_cig, words ? cigar + w0 : nullptr, words * 4)) return in.fail("bsa_piece_cigars_batch: upload failed");
+	const pcg_in_t a = { in.at<bsa_result_t>(o_out), in.at<uint32_t>(o_cig), in.at<uint64_t>(o_coff), (uint32_t)n, in.at<bsa_piece_t>(o_piece), in.at<uint64_t>(o_np), (uint32_t)npiece };
+	uint64_t *d_poff = in.at<uint64_t>(o_poff);
+	pcg_scratch_t s;
+	if((rc = pcg_scratch(ctx, n, npiece, &s)) != BSA_OK) return rc;
+	if((rc = pcg_launch(ctx, stream, a, s, PCG_INDEX | PCG_COUNT | PCG_SCAN, nullptr, 0, d_poff, in.at<uint32_t>(o_st))) != BSA_OK) return rc;
+	if(!in.down(pcig_off, o_poff, (npiece + 1) * 8) || (pstatus && !in.down(pstatus, o_st, npiece * 4)) || !in.sync()) return in.fail("bsa_piece_cigars_batch: download of the offsets failed");
+	const uint64_t need = pcig_off[npiece];                    // (the offsets are down before the capacity is judged)
+	if(need > pcig_cap) return in.fail("bsa_piece_cigars_batch: pcig_cap too small, pcig_off[npiece] holds the words needed", BSA_E_CIGAR_CAP);
+	if(need == 0) return BSA_OK;
+	const size_t o_pcig = res.part(need * 4);
+	if((rc = res.alloc("bsa_piece_cigars_batch: no device memory for the words")) != BSA_OK) return rc;
+	if((rc = pcg_launch(ctx, stream, a, s, PCG_FILL, res.at<uint32_t>(o_pcig), need, d_poff, nullptr)) != BSA_OK) return rc;
+	if(!res.down(pcig, o_pcig, need * 4) || !res.sync()) return res.fail("bsa_piece_cigars_batch: download of the words failed");
+	return BSA_OK;
 }

@@ -6,8 +6,8 @@
 //   clear  : the per-window counters in the context's scratch (hipMemsetAsync: a run leaves nothing behind that a later run reads);
 //   count  : one wave a pair over its records (k_window_pieces_count): a record that is a piece adds 1 to cnt[g] and its length to bsum[g] with
 //            vector atomics.  Integer sums do not depend on the order of the adds, so the offsets are a function of the inputs alone;
-//   scan   : cnt -> d_piece_off with the 64-bit exclusive scan of bsa_api.hip, bsum (64-bit values) -> d_base_off with the same scan in tiles
-//            for 64-bit input (k_wp_scan_*);
+//   scan   : cnt -> d_piece_off and bsum (64-bit values) -> d_base_off, both with the 64-bit exclusive scan of bsa_scan.hip (its tile kernels
+//            take either value type; 64-bit values always go to tiles);
 //   place  : the count kernel's loop again (k_window_pieces_place): a piece of a window that FITS (both of its ranges end inside the caps) takes a
 //            slot from the window's cursor and leaves (record index, pair, length) in ent[piece_off[g] + slot], in scratch.  The slot order is
 //            whatever the atomics made it;
@@ -21,15 +21,9 @@
 //            of the first 16-byte border of the destination one a lane, then 16 codes a lane and trip -- two unaligned 8-byte loads (byte-reversed
 //            and ^ 3 for a marked read, as k_stage<.., true> does) or bsa_bits16 / bsa_bits16_rc from packed words -- into one aligned 16-byte
 //            store, then the bytes behind the last border one a lane.  Every load lies inside the piece, so inside the read.
-// No LDS, plain C++ with vector loads, stores and atomics only.
-#include "bsa_common.h"
+// No LDS in this file's kernels, plain C++ with vector loads, stores and atomics only.
+#include "bsa_pass.h"
 #include <vector>
-
-extern "C" int bsa_ctx_get_stream_internal(bsa_ctx_t *ctx, hipStream_t *st);
-extern "C" int bsa_ctx_scratch_internal(bsa_ctx_t *ctx, int slot, size_t bytes, void **out);
-extern "C" void bsa_ctx_set_error_internal(bsa_ctx_t *ctx, const char *msg);
-hipError_t bsa_launch_excl_scan(hipStream_t st, const uint32_t *cnt, uint64_t *off, uint32_t n, uint64_t *tmp);      // bsa_api.hip; tmp: bsa_excl_scan_tmp_bytes(n)
-size_t bsa_excl_scan_tmp_bytes(uint32_t n);
 
 static_assert(sizeof(bsa_piece_t) == 32, "bsa_piece_t is 32 bytes");
 
@@ -160,73 +154,12 @@ __global__ void __launch_bounds__(256) k_window_pieces_gather(const uint8_t *seq
 	}
 }
 
-// the exclusive scan of bsa_api.hip for 64-bit values: sums of tiles, a scan of the sums by one block, every tile scanned with its base.
-// tmp: tiles + 1 words, tiles = max(1, ceil(n / WP_SCAN_TILE)); off[n] = the total
-#define WP_SCAN_TILE 4096u
-__global__ void __launch_bounds__(256) k_wp_scan_sums(const uint64_t *v, uint32_t n, uint64_t *tmp){
-	__shared__ uint64_t red[4];
-	const uint32_t t = threadIdx.x;
-	uint64_t s = 0;
-	for(uint32_t i = t; i < WP_SCAN_TILE; i += 256u){ const uint64_t idx = (uint64_t)blockIdx.x * WP_SCAN_TILE + i; s += idx < n ? v[idx] : 0ull; }
-	for(int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
-	if((t & 63u) == 0u) red[t >> 6] = s;
-	__syncthreads();
-	if(t == 0) tmp[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ void __launch_bounds__(1024) k_wp_scan_bases(uint64_t *tmp, uint32_t tiles){
-	__shared__ uint64_t part[1024];
-	__shared__ uint64_t base;
-	const uint32_t t = threadIdx.x;
-	if(t == 0) base = 0ull;
-	__syncthreads();
-	for(uint32_t s = 0; s < tiles; s += 1024u){
-		const uint64_t v = (s + t < tiles) ? tmp[s + t] : 0ull;
-		part[t] = v;
-		__syncthreads();
-		for(uint32_t d = 1; d < 1024; d <<= 1){
-			const uint64_t u = (t >= d) ? part[t - d] : 0ull;
-			__syncthreads();
-			part[t] += u;
-			__syncthreads();
-		}
-		if(s + t < tiles) tmp[s + t] = part[t] - v + base;
-		__syncthreads();
-		if(t == 1023) base += part[1023];
-		__syncthreads();
-	}
-	if(t == 0) tmp[tiles] = base;
-}
-__global__ void __launch_bounds__(256) k_wp_scan_apply(const uint64_t *v, uint64_t *off, uint32_t n, const uint64_t *tmp, uint32_t tiles){
-	__shared__ uint64_t wsum[4];
-	const uint32_t b = blockIdx.x, t = threadIdx.x;
-	const uint64_t i0 = (uint64_t)b * WP_SCAN_TILE + t * 16u;          // 16 consecutive values per thread
-	uint64_t loc[16], s = 0;
-	for(int k = 0; k < 16; k++){ loc[k] = s; s += (i0 + k < n) ? v[i0 + k] : 0ull; }
-	uint64_t inc = s;
-	for(int d = 1; d < 64; d <<= 1){ const uint64_t u = __shfl_up(inc, d); if((t & 63u) >= (uint32_t)d) inc += u; }
-	if((t & 63u) == 63u) wsum[t >> 6] = inc;
-	__syncthreads();
-	uint64_t wb = 0;
-	for(uint32_t x = 0; x < (t >> 6); x++) wb += wsum[x];
-	const uint64_t excl = tmp[b] + wb + inc - s;
-	for(int k = 0; k < 16; k++) if(i0 + k < n) off[i0 + k] = excl + loc[k];
-	if(b == tiles - 1u && t == 0) off[n] = tmp[tiles];
-}
-static uint32_t wp_scan_tiles(uint32_t n){ const uint32_t t = (uint32_t)(((uint64_t)n + WP_SCAN_TILE - 1u) / WP_SCAN_TILE); return t ? t : 1u; }
-static hipError_t wp_launch_scan64(hipStream_t st, const uint64_t *v, uint64_t *off, uint32_t n, uint64_t *tmp){
-	const uint32_t tiles = wp_scan_tiles(n);
-	hipLaunchKernelGGL(k_wp_scan_sums, dim3(tiles), dim3(256), 0, st, v, n, tmp);
-	hipLaunchKernelGGL(k_wp_scan_bases, dim3(1), dim3(1024), 0, st, tmp, tiles);
-	hipLaunchKernelGGL(k_wp_scan_apply, dim3(tiles), dim3(256), 0, st, v, off, n, (const uint64_t*)tmp, tiles);
-	return hipGetLastError();
-}
-
 // the pass's part of the context's scratch: cnt | bsum (cleared by the offsets) | cur | written (cleared by the fill) | the scans' tiles | ent
 struct wp_scratch_t { uint32_t *cnt; unsigned long long *bsum; uint32_t *cur; uint64_t *written, *tmp32, *tmp64; wp_ent_t *ent; };
 static int wp_scratch(bsa_ctx_t *ctx, size_t nwin, size_t ent_cap, wp_scratch_t *s){
-	auto up = [](size_t b){ return (b + 255u) & ~(size_t)255u; };
-	const size_t o_cnt = 0, o_bsum = o_cnt + up(nwin * 4u), o_cur = o_bsum + up(nwin * 8u), o_wr = o_cur + up(nwin * 4u), o_t32 = o_wr + 256u,
-		o_t64 = o_t32 + up(bsa_excl_scan_tmp_bytes((uint32_t)nwin)), o_ent = o_t64 + up(((size_t)wp_scan_tiles((uint32_t)nwin) + 1u) * 8u);
+	const size_t tmp = bsa_up256(bsa_excl_scan_tmp_bytes((uint32_t)nwin));
+	const size_t o_cnt = 0, o_bsum = o_cnt + bsa_up256(nwin * 4u), o_cur = o_bsum + bsa_up256(nwin * 8u), o_wr = o_cur + bsa_up256(nwin * 4u), o_t32 = o_wr + 256u,
+		o_t64 = o_t32 + tmp, o_ent = o_t64 + tmp;
 	if(ent_cap > (((size_t)1 << 62) - o_ent) / sizeof(wp_ent_t)){ bsa_ctx_set_error_internal(ctx, "bsa_window_pieces: piece_cap too large for the scratch it needs"); return BSA_E_NOMEM; }
 	void *bufv = nullptr;
 	const int rc = bsa_ctx_scratch_internal(ctx, 1, o_ent + ent_cap * sizeof(wp_ent_t), &bufv);      // (waits for the stream only when it has to grow)
@@ -247,15 +180,14 @@ static int wp_offsets(bsa_ctx_t *ctx, hipStream_t st, const wp_in_t &a, const wp
 		hipLaunchKernelGGL(k_window_pieces_count, dim3((a.n + 3u) / 4u), dim3(256), 0, st, a.win, a.woff, a.qlen, a.gbase, a.n, a.window, a.nwin, s.cnt, s.bsum);
 		e = hipGetLastError();
 	}
-	if(e == hipSuccess) e = bsa_launch_excl_scan(st, s.cnt, d_piece_off, a.nwin, s.tmp32);
-	if(e == hipSuccess) e = wp_launch_scan64(st, (const uint64_t*)s.bsum, d_base_off, a.nwin, s.tmp64);
+	if(e == hipSuccess) e = bsa_launch_excl_scan(st, s.cnt, d_piece_off, a.nwin, nullptr, s.tmp32);
+	if(e == hipSuccess) e = bsa_launch_excl_scan(st, (const uint64_t*)s.bsum, d_base_off, a.nwin, nullptr, s.tmp64);
 	if(e != hipSuccess){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, "bsa_window_pieces: launch failed"); return BSA_E_HIP; }
 	return BSA_OK;
 }
 // the gather launch of wp_fill; s.written: the records the order kernel left
 static hipError_t wp_launch_gather(hipStream_t st, const wp_in_t &a, const wp_scratch_t &s, const bsa_piece_t *d_piece, size_t piece_cap, uint8_t *d_bases, size_t bases_cap){
-	const size_t want = (piece_cap + 15u) / 16u, most = (size_t)bsa_cus() * 16u;          // 16 pieces a block and trip
-	const dim3 grid((uint32_t)(want < most ? want : most)), block(256);
+	const dim3 grid = bsa_grid16(piece_cap), block(256);
 	const bool pk = (a.flags & BSA_MODE_SEQ2BIT) != 0, qs = (a.flags & BSA_MODE_QSTRAND) != 0;
 #define WP_GATHER(PK, QS) hipLaunchKernelGGL((k_window_pieces_gather<PK, QS>), grid, block, 0, st, a.seqs, a.qoff, a.qlen, d_piece, (const uint64_t*)s.written, d_bases, (uint64_t)bases_cap)
 	if(pk){ if(qs) WP_GATHER(true, true); else WP_GATHER(true, false); }
@@ -343,52 +275,34 @@ extern "C" int bsa_window_pieces_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size
 	for(size_t k = 0; k < n; k++){
 		const uint64_t o = qoff[k] & mask;
 		if(o > have || qlen[k] > have - o){ bsa_ctx_set_error_internal(ctx, "bsa_window_pieces_batch: a read lies outside the blob"); return BSA_E_ARG; }
-		if(win_off[k + 1] < win_off[k]){ bsa_ctx_set_error_internal(ctx, "bsa_window_pieces_batch: win_off decreases"); return BSA_E_ARG; }
 	}
-	const uint64_t r0 = win_off[0], recs = win_off[n] - r0;          // only the records the offsets speak of go up
+	std::vector<uint64_t> woff;
+	if((rc = bsa_rebase_offsets(ctx, win_off, n, woff, "bsa_window_pieces_batch: win_off decreases")) != BSA_OK) return rc;
+	const uint64_t r0 = win_off[0], recs = woff[n];                       // only the records the offsets speak of go up
 	if(recs && !win){ bsa_ctx_set_error_internal(ctx, "bsa_window_pieces_batch: null argument"); return BSA_E_ARG; }
 	hipStream_t stream;
 	if((rc = bsa_ctx_get_stream_internal(ctx, &stream)) != BSA_OK) return rc;
-	auto up = [](size_t b){ return (b + 255u) & ~(size_t)255u; };
-	const size_t o_seq = 0, o_qoff = o_seq + up(seqs_bytes + 8u), o_qlen = o_qoff + up(n * 8u), o_woff = o_qlen + up(n * 4u), o_gb = o_woff + up((n + 1u) * 8u),
-		o_poff = o_gb + up(n * 8u), o_boff = o_poff + up((nwin + 1u) * 8u), o_win = o_boff + up((nwin + 1u) * 8u), total = o_win + up(recs * sizeof(bsa_window_t) + 16u);
-	uint8_t *buf = nullptr, *d_out = nullptr;
-	auto fail = [&](const char *what, int code){ (void)hipGetLastError(); bsa_ctx_set_error_internal(ctx, what); rc = code; };
-	std::vector<uint64_t> woff;
-	try { woff.resize(n + 1); } catch(...){ return BSA_E_NOMEM; }
-	for(size_t k = 0; k <= n; k++) woff[k] = win_off[k] - r0;
-	do {
-		if(hipMalloc((void**)&buf, total) != hipSuccess){ buf = nullptr; fail("bsa_window_pieces_batch: no device memory for the blob and the records", BSA_E_NOMEM); break; }
-		if((seqs_bytes && hipMemcpyAsync(buf + o_seq, seqs, seqs_bytes, hipMemcpyHostToDevice, stream) != hipSuccess)
-				|| hipMemcpyAsync(buf + o_qoff, qoff, n * 8u, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_qlen, qlen, n * 4u, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_woff, woff.data(), (n + 1u) * 8u, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| hipMemcpyAsync(buf + o_gb, gbase, n * 8u, hipMemcpyHostToDevice, stream) != hipSuccess
-				|| (recs && hipMemcpyAsync(buf + o_win, win + r0, recs * sizeof(bsa_window_t), hipMemcpyHostToDevice, stream) != hipSuccess)){ fail("bsa_window_pieces_batch: upload failed", BSA_E_HIP); break; }
-		const wp_in_t a = { buf + o_seq, (const uint64_t*)(buf + o_qoff), (const uint32_t*)(buf + o_qlen), (const bsa_window_t*)(buf + o_win), (const uint64_t*)(buf + o_woff),
-			(const uint64_t*)(buf + o_gb), (uint32_t)n, window, (uint32_t)nwin, flags };
-		uint64_t *d_poff = (uint64_t*)(buf + o_poff), *d_boff = (uint64_t*)(buf + o_boff);
-		wp_scratch_t s;
-		if((rc = wp_scratch(ctx, nwin, 0u, &s)) != BSA_OK) break;
-		if((rc = wp_offsets(ctx, stream, a, s, d_poff, d_boff)) != BSA_OK) break;
-		if(hipMemcpyAsync(piece_off, d_poff, (nwin + 1u) * 8u, hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| hipMemcpyAsync(base_off, d_boff, (nwin + 1u) * 8u, hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_window_pieces_batch: download of the offsets failed", BSA_E_HIP); break; }
-		const uint64_t np = piece_off[nwin], nb = base_off[nwin];
-		if(np > piece_cap || nb > bases_cap){
-			bsa_ctx_set_error_internal(ctx, "bsa_window_pieces_batch: piece_cap or bases_cap too small, piece_off[nwin] and base_off[nwin] hold what is needed"); rc = BSA_E_CIGAR_CAP; break;
-		}
-		if(np == 0) break;
-		const size_t o_b = up(np * sizeof(bsa_piece_t));
-		if(hipMalloc((void**)&d_out, o_b + up(nb)) != hipSuccess){ d_out = nullptr; fail("bsa_window_pieces_batch: no device memory for the pieces", BSA_E_NOMEM); break; }
-		if((rc = wp_scratch(ctx, nwin, np, &s)) != BSA_OK) break;
-		if((rc = wp_fill(ctx, stream, a, s, d_poff, d_boff, (bsa_piece_t*)d_out, np, d_out + o_b, nb)) != BSA_OK) break;
-		if(hipMemcpyAsync(piece, d_out, np * sizeof(bsa_piece_t), hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| hipMemcpyAsync(bases, d_out + o_b, nb, hipMemcpyDeviceToHost, stream) != hipSuccess
-				|| hipStreamSynchronize(stream) != hipSuccess){ fail("bsa_window_pieces_batch: download of the pieces failed", BSA_E_HIP); break; }
-	} while(0);
-	if(rc != BSA_OK && rc != BSA_E_CIGAR_CAP) (void)hipStreamSynchronize(stream);      // nothing of the call is in flight when its buffers go
-	if(d_out) (void)hipFree(d_out);
-	if(buf) (void)hipFree(buf);
-	return rc;
+	bsa_stage_t in(ctx, stream), res(ctx, stream);
+	const size_t o_seq = in.part(seqs_bytes + 8u), o_qoff = in.part(n * 8u), o_qlen = in.part(n * 4u), o_woff = in.part((n + 1u) * 8u), o_gb = in.part(n * 8u),
+		o_poff = in.part((nwin + 1u) * 8u), o_boff = in.part((nwin + 1u) * 8u), o_win = in.part(recs * sizeof(bsa_window_t) + 16u);
+	if((rc = in.alloc("bsa_window_pieces_batch: no device memory for the blob and the records")) != BSA_OK) return rc;
+	if(!in.up(o_seq, seqs, seqs_bytes) || !in.up(o_qoff, qoff, n * 8u) || !in.up(o_qlen, qlen, n * 4u) || !in.up(o_woff, woff.data(), (n + 1u) * 8u) || !in.up(o_gb, gbase, n * 8u)
+			|| !in.up(o_win, recs ? win + r0 : nullptr, recs * sizeof(bsa_window_t))) return in.fail("bsa_window_pieces_batch: upload failed");
+	const wp_in_t a = { in.at<uint8_t>(o_seq), in.at<uint64_t>(o_qoff), in.at<uint32_t>(o_qlen), in.at<bsa_window_t>(o_win), in.at<uint64_t>(o_woff), in.at<uint64_t>(o_gb),
+		(uint32_t)n, window, (uint32_t)nwin, flags };
+	uint64_t *d_poff = in.at<uint64_t>(o_poff), *d_boff = in.at<uint64_t>(o_boff);
+	wp_scratch_t s;
+	if((rc = wp_scratch(ctx, nwin, 0u, &s)) != BSA_OK) return rc;
+	if((rc = wp_offsets(ctx, stream, a, s, d_poff, d_boff)) != BSA_OK) return rc;
+	if(!in.down(piece_off, o_poff, (nwin + 1u) * 8u) || !in.down(base_off, o_boff, (nwin + 1u) * 8u) || !in.sync()) return in.fail("bsa_window_pieces_batch: download of the offsets failed");
+	const uint64_t np = piece_off[nwin], nb = base_off[nwin];             // (the offsets are down before the capacities are judged)
+	if(np > piece_cap || nb > bases_cap)
+		return in.fail("bsa_window_pieces_batch: piece_cap or bases_cap too small, piece_off[nwin] and base_off[nwin] hold what is needed", BSA_E_CIGAR_CAP);
+	if(np == 0) return BSA_OK;
+	const size_t o_p = res.part(np * sizeof(bsa_piece_t)), o_b = res.part(nb);
+	if((rc = res.alloc("bsa_window_pieces_batch: no device memory for the pieces")) != BSA_OK) return rc;
+	if((rc = wp_scratch(ctx, nwin, np, &s)) != BSA_OK) return rc;
+	if((rc = wp_fill(ctx, stream, a, s, d_poff, d_boff, res.at<bsa_piece_t>(o_p), np, res.at<uint8_t>(o_b), nb)) != BSA_OK) return rc;
+	if(!res.down(piece, o_p, np * sizeof(bsa_piece_t)) || !res.down(bases, o_b, nb) || !res.sync()) return res.fail("bsa_window_pieces_batch: download of the pieces failed");
+	return BSA_OK;
 }

@@ -137,6 +137,37 @@ def test_one_pair_after_another(ctx):
         assert rc == 0 and list(off) == [0, len(per[k])] and np.array_equal(win[:len(per[k])], per[k]) and np.all(win[len(per[k]):] == SENT), k
 
 
+N_TILED = 16400                    # above 16 384 counts the scan goes from one block to tiles of 4096
+
+
+def test_more_pairs_than_one_scan_block(ctx):
+    """16 400 pairs of one 30M word at w = 10: three or four records a pair, offsets across the borders of the scan's tiles"""
+    cig = W.words((30, W.M))
+    recs, cigs = [W.record(k % 7, k % 5, cig) for k in range(N_TILED)], [cig] * N_TILED
+    per, woff = W.expected(10, recs, cigs)
+    need = int(woff[-1])
+    assert need > 3 * N_TILED and {len(p) for p in per} == {3, 4}
+    dev = _Dev(10, recs, cigs, need + GUARD)
+    off, win = dev.run(ctx, need + GUARD)
+    assert _check(off, win, per, woff, need + GUARD, "16 400 pairs") == N_TILED
+
+
+def test_window_counts_that_sum_above_2_pow_32_inside_a_thread(ctx):
+    """count-only run at w = 1: every pair has one window, but pairs 4146 .. 4148 -- three of the sixteen counts of one thread of the tiled scan --
+    have 2^31 - 1 each, so the prefix inside that thread passes 2^32"""
+    cig = W.words((1, W.M))
+    big = (4146, 4147, 4148)
+    recs, cigs = [W.record(0, 0, cig, te=0x7FFFFFFF if k in big else 1) for k in range(N_TILED)], [cig] * N_TILED
+    cnt = np.ones(N_TILED, dtype=np.uint64)
+    cnt[list(big)] = 0x7FFFFFFF
+    woff = np.zeros(N_TILED + 1, dtype=np.uint64)
+    woff[1:] = np.cumsum(cnt, dtype=np.uint64)
+    assert int(woff[4149]) - int(woff[4144]) > 1 << 32
+    off, win = _Dev(1, recs, cigs, 0).run(ctx, 0, null_win=True)
+    bad = np.flatnonzero(off != woff)
+    assert len(bad) == 0, ("win_off", len(bad), int(bad[0]), int(off[bad[0]]), int(woff[bad[0]]))
+
+
 # ---- 2. what the aligners return -----------------------------------------------------------------------------------------------------------
 def _real_pairs():
     """64 pairs of 300 .. 2000 bases; every other one with a burst: a deleted or an inserted block of 10 .. 50 bases"""

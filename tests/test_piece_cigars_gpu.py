@@ -190,6 +190,17 @@ def test_more_pieces_announced_than_there_is_room_for(ctx):
         assert _check(dev.run(ctx, int(want[0][-1]) + 7), want, int(want[0][-1]) + 7, "announced %d" % announced) == cap_p
 
 
+def test_more_room_than_one_scan_block_takes(ctx):
+    """piece_cap = 16 400 with the batch's own piece count in *d_npiece: the scan of all piece_cap counts runs in tiles (above 16 384), and every
+    offset above P is the total"""
+    args, ref = _named("tile_sizes")
+    np_, total = len(ref[2]), int(ref[0][-1])
+    assert 0 < np_ < 4096 and total > 0
+    dev = _Dev(args, 16400, total + GUARD)
+    assert dev.npiece == np_
+    assert _check(dev.run(ctx, total + GUARD), ref, total + GUARD, "piece_cap 16 400") == np_
+
+
 def test_through_the_python_calls(ctx):
     """Context.piece_cigars on host arrays, Context.piece_cigars_run on torch tensors"""
     import torch

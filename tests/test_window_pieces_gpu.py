@@ -22,7 +22,7 @@ _CASES, _REFS = {}, {}
 CASE_NAMES = ["depths", "deep_5000", "lengths_at_every_residue", "stored_at_every_offset", "marked_read_of_length_1", "codes_above_3", "none_records",
               "pairs_without_records", "q_last_at_qlen", "q_last_far_above_qlen", "q_first_above_q_last", "t_first_above_t_last", "window_at_nwin",
               "window_far_above_nwin", "gbase_pushes_a_pair_out", "gbase_2_pow_40", "gbase_near_2_pow_64", "two_records_in_one_window", "no_pairs", "no_windows",
-              "one_window", "window_1", "window_max", "thousand_pairs", "arena_batch"]
+              "one_window", "window_1", "window_max", "thousand_pairs", "arena_batch", "many_windows"]
 RAW_CASES = ("codes_above_3",)     # codes above 3 have no packed form: built for 1 B/base only
 
 
@@ -181,6 +181,9 @@ def test_hand_made_cases_hold_what_they_are_for():
                  "gbase_near_2_pow_64"):
         args, ref = _case(name, 0)
         assert len(args[3]) == 7 and len(ref[2]) in (4, 5), name          # the two broken records, or a whole pair of two, are ignored
+    args, (poff, boff, recs, codes) = _case("many_windows", P.QSTRAND)
+    d = np.diff(poff.astype(np.int64))
+    assert args[7] == 16400 and len(args[2]) == 40 and int(poff[-1]) == 40 and all(1 <= d[g] <= 4 for g in P.MANY_WINDOWS) and max(d[g] for g in P.MANY_WINDOWS) >= 3
 
 
 # ---- 2. what the aligners return -------------------------------------------------------------------------------------------------------
@@ -280,6 +283,22 @@ def test_real_outputs_resident(ctx):
     with pytest.raises(ValueError):
         ctx.window_pieces_run(dev.d_seqs, dev.d_qoff, dev.d_qlen, dev.d_win, dev.d_woff, dev.n, W_REAL, dev.d_gbase, nwin, args[8], d_piece, pcap + 1, dev.d_poff, d_bases, bcap,
                               dev.d_boff)
+
+
+def test_base_sums_above_2_pow_32(ctx):
+    """count-only run (no arenas: the blob is never read): three pieces of 2^32 - 1 bases, two in window 0 and one in window 4096, the first window of the
+    scan's second tile.  base_off is summed in 64 bits inside a thread, across a tile and across the tiles.  (_batch rightly refuses such reads.)"""
+    n, nwin, big = 3, 4100, 0xFFFFFFFF
+    args = (np.zeros(16, np.uint8), np.zeros(n, np.uint64), np.full(n, big, np.uint32), np.array([[0, 0, 5, big - 1]] * n, np.uint32),
+            np.arange(n + 1, dtype=np.uint64), 10, np.array([0, 0, 4096], np.uint64), nwin, 0)
+    cnt = np.zeros(nwin, np.uint64)
+    cnt[0], cnt[4096] = 2, 1
+    rpoff, rboff = np.zeros(nwin + 1, np.uint64), np.zeros(nwin + 1, np.uint64)
+    rpoff[1:], rboff[1:] = np.cumsum(cnt, dtype=np.uint64), np.cumsum(cnt * np.uint64(big), dtype=np.uint64)
+    assert int(rboff[1]) == 2 * big > 1 << 32 and int(rboff[-1]) == 3 * big
+    poff, boff, piece, bases = _Dev(args, 0, 0).run(ctx, 0, 0, null=True)
+    assert np.array_equal(poff, rpoff), ("piece_off", poff[[0, 1, 4096, 4097, nwin]])
+    assert np.array_equal(boff, rboff), ("base_off", boff[[0, 1, 4096, 4097, nwin]])
 
 
 # ---- 3. the arena contract -------------------------------------------------------------------------------------------------------------

@@ -105,6 +105,8 @@ def _reads(rng, lens, raw=False):
 
 LENGTHS = (1, 3, 4, 5, 15, 16, 17, 31, 32, 33, 63, 64, 65, 1000)
 DEPTHS = (0, 1, 2, 63, 64, 65, 129, 200)
+MANY_NWIN = 16400
+MANY_WINDOWS = (0, 4095, 4096, 4097, 8191, 8192, 12288, 16383, 16384, 16399)
 
 
 def hand_cases():
@@ -207,4 +209,15 @@ def hand_cases():
     reads = _reads(rng, rng.integers(20, 200, 100))
     recs = [[(int(t), 0, int(t) + 5, int(rng.integers(0, len(r)))) for t in sorted(rng.choice(30, 3, replace=False) * 10)] for r in reads]
     c["arena_batch"] = Case(reads, [k % 2 == 0 for k in range(100)], recs, 10, [0] * 100, 30)
+    # 16 400 windows, nearly all empty: pieces on both sides of the borders of the scans' tiles of 4096 counts and of the 16 384 counts up to which
+    # 32-bit counts are scanned by one block, and in the last window; one to three pieces a window, a pair and a record each, placed by gbase
+    depth = dict(zip(MANY_WINDOWS, (3, 1, 2, 3, 2, 3, 1, 2, 3, 2)))
+    gb = [g for g in MANY_WINDOWS for _ in range(depth[g])]
+    gb = [gb[i] for i in rng.permutation(len(gb))] + [int(g) for g in rng.integers(0, MANY_NWIN, 40 - len(gb))]
+    reads = _reads(rng, rng.integers(20, 61, len(gb)))
+    recs = []
+    for r in reads:
+        a = int(rng.integers(0, len(r)))
+        recs.append([(int(rng.integers(0, 10)), a, 9, int(rng.integers(a, len(r))))])
+    c["many_windows"] = Case(reads, [k % 3 == 1 for k in range(len(gb))], recs, 10, gb, MANY_NWIN)
     return c
