@@ -96,6 +96,9 @@ PIECE_DTYPE = np.dtype([("pair", np.uint32), ("q_first", np.uint32), ("len", np.
 _lib = None
 
 
+# bsa_cns_window_t (include/bsalign_msa.h): what bsa_window_msa_* writes and bsa_msa_call_consensus_batch takes
+CNS_WINDOW_DTYPE = np.dtype([("cols_off", np.uint64), ("idxs_off", np.uint64), ("out_off", np.uint64),
+                             ("nall", np.uint32), ("nseq", np.uint32), ("nmax", np.uint32), ("mlen", np.uint32)])
 DIAGDP_PROB_DTYPE = np.dtype([("seq0", np.uint64), ("seq1", np.uint64), ("mats0", np.uint64, (4,)), ("mats1", np.uint64, (4,)),
                               ("out0", np.uint64), ("out1", np.uint64), ("mlen", np.uint32), ("mbeg", np.uint32), ("mend", np.uint32), ("W", np.uint32)])
 
@@ -205,6 +208,12 @@ def lib():
             L.bsa_piece_cigars_bound.restype = C.c_uint64
             L.bsa_piece_cigars_run.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
             L.bsa_piece_cigars_batch.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        if hasattr(L, "bsa_window_msa_run"):
+            L.bsa_window_msa_bound.argtypes = [u64p, C.c_size_t, C.c_uint32, C.c_uint64]
+            L.bsa_window_msa_bound.restype = C.c_uint64
+            L.bsa_window_msa_run.argtypes = [vp, vp, u64p, C.c_size_t, C.c_size_t, u8p, C.c_size_t, u32p, C.c_size_t, u64p, u8p, u64p, u32p,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t, u64p, vp]
+            L.bsa_window_msa_batch.argtypes = L.bsa_window_msa_run.argtypes
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -835,6 +844,75 @@ class Context:
         self._chk(lib().bsa_piece_cigars_run(self.h, ptr(d_out), ptr(d_cigar), ptr(d_cigar_off), n, ptr(d_piece), ptr(d_npiece), piece_cap,
                                              ptr(d_pcig), pcig_cap, ptr(d_pcig_off), ptr(d_pstatus)))
 
+    def window_msa(self, windows_out, guides, drafts, window, vote=False, seq2bit=False):
+        """bsa_window_msa_batch on what Context.window_pieces returned (the list over the windows of (pieces, codes)), what Context.piece_cigars
+        made of it (the list over the windows of lists of (words, status)) and one code array a window, the window's slice of the draft (at most
+        `window` bases of it count): every window's draft-anchored MSA.  Returns a list over the windows of (cols, cwin): cols an (mlen, depth + 4)
+        uint8 array -- a row of it is one column of the MSA: the depth piece rows, the draft row, the three consensus bytes 4 0 0 -- and cwin the
+        window's CNS_WINDOW_DTYPE record, cols_off and out_off counted over the whole call.  vote: the draft row votes too (nseq = depth + 1);
+        seq2bit: the drafts go to the device 2-bit packed (the same columns)."""
+        nwin = len(windows_out)
+        if len(guides) != nwin or len(drafts) != nwin:
+            raise ValueError("window_msa: one list of guides and one draft per window")
+        piece = _np(np.concatenate([np.zeros(0, PIECE_DTYPE)] + [_np(ps, PIECE_DTYPE) for ps, _ in windows_out]), PIECE_DTYPE).copy()
+        poff = np.zeros(nwin + 1, dtype=np.uint64)
+        poff[1:] = np.cumsum([len(ps) for ps, _ in windows_out], dtype=np.uint64)
+        codes = [_np(c, np.uint8) for _, cs in windows_out for c in cs]
+        words = [_np(ws, np.uint32) for gs in guides for ws, _ in gs]
+        if len(codes) != len(piece) or len(words) != len(piece):
+            raise ValueError("window_msa: one code array and one guide per piece")
+        boff = np.zeros(len(piece) + 1, dtype=np.uint64)
+        boff[1:] = np.cumsum([len(c) for c in codes], dtype=np.uint64)
+        piece["base_off"] = boff[:-1]                           # the codes as they are laid out here
+        bases = _np(np.concatenate([np.zeros(0, np.uint8)] + codes), np.uint8)
+        pcoff = np.zeros(len(piece) + 1, dtype=np.uint64)
+        pcoff[1:] = np.cumsum([len(w) for w in words], dtype=np.uint64)
+        pcig = _np(np.concatenate([np.zeros(0, np.uint32)] + words), np.uint32)
+        dl = [_np(d, np.uint8) for d in drafts]
+        dlen = np.array([len(d) for d in dl], dtype=np.uint32)
+        doff = np.zeros(nwin, dtype=np.uint64)
+        doff[1:] = np.cumsum(dlen[:-1], dtype=np.uint64)
+        draft = _np(np.concatenate([np.zeros(1, np.uint8)] + dl)[1:], np.uint8) if nwin else np.zeros(0, np.uint8)
+        if seq2bit:
+            draft = pack2bit(draft)
+        draft = draft if draft.size else np.zeros(1, np.uint64 if seq2bit else np.uint8)
+        coff = np.zeros(nwin + 1, dtype=np.uint64)
+        cwin = np.zeros(max(nwin, 1), dtype=CNS_WINDOW_DTYPE)
+        cols, cap = np.zeros(1, dtype=np.uint8), 0
+        for _ in range(2):                                     # a count-only call says what is needed
+            rc = lib().bsa_window_msa_batch(self.h, _p(piece) if len(piece) else None, _p(poff), nwin, len(piece), _p(bases) if len(bases) else None, len(bases),
+                                            _p(pcig) if len(pcig) else None, len(pcig), _p(pcoff), _p(draft), _p(doff), _p(dlen), int(window),
+                                            MODE_SEQ2BIT if seq2bit else 0, 1 if vote else 0, _p(cols) if cap else None, cap, _p(coff), _p(cwin))
+            if rc != -5 or int(coff[nwin]) <= cap:
+                break
+            cap = int(coff[nwin])
+            cols = np.zeros(cap, dtype=np.uint8)
+        self._chk(rc)
+        res = []
+        for g in range(nwin):
+            w = cwin[g]
+            res.append((cols[int(coff[g]):int(coff[g + 1])].reshape(int(w["mlen"]), int(w["nall"]) + 3).copy(), w.copy()))
+        return res
+
+    def window_msa_run(self, d_piece, d_piece_off, nwin, piece_cap, d_bases, bases_cap, d_pcig, pcig_cap, d_pcig_off, d_draft, d_doff, d_dlen,
+                       window, flags, vote, d_cols, cols_cap, d_cols_off, d_cwin):
+        """bsa_window_msa_run on torch tensors (plumbing only), asynchronous on the context's stream: d_piece, d_piece_off, d_bases as a complete
+        window_pieces_run left them, d_pcig, d_pcig_off as a complete piece_cigars_run left them for the same piece_cap; d_draft the draft (1 B/base,
+        or 2-bit packed words with MODE_SEQ2BIT in flags), d_doff (64-bit) and d_dlen (32-bit) one entry a window (window_drafts); vote 0 or 1.
+        d_cols: room for cols_cap bytes, or None with cols_cap 0 for a count-only run; d_cols_off: nwin + 1 64-bit words; d_cwin: nwin records of
+        40 bytes (CNS_WINDOW_DTYPE).  Window g's columns are d_cols[d_cols_off[g] : d_cols_off[g + 1]] where d_cols_off[g + 1] <= cols_cap;
+        d_cols_off[nwin] is what a complete run needs."""
+        if d_cols is not None and d_cols.numel() * d_cols.element_size() < cols_cap:
+            raise ValueError("window_msa_run: d_cols holds fewer than cols_cap bytes")
+        if d_cols_off is not None and d_cols_off.numel() * d_cols_off.element_size() < 8 * (nwin + 1):
+            raise ValueError("window_msa_run: d_cols_off holds fewer than nwin + 1 offsets")
+        if d_cwin is not None and d_cwin.numel() * d_cwin.element_size() < 40 * nwin:
+            raise ValueError("window_msa_run: d_cwin holds fewer than nwin records")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_msa_run(self.h, ptr(d_piece), ptr(d_piece_off), nwin, piece_cap, ptr(d_bases), bases_cap, ptr(d_pcig), pcig_cap,
+                                           ptr(d_pcig_off), ptr(d_draft), ptr(d_doff), ptr(d_dlen), int(window), int(flags), int(vote),
+                                           ptr(d_cols), cols_cap, ptr(d_cols_off), ptr(d_cwin)))
+
 
 def window_gbase(target_id, target_len, window):
     """gbase for bsa_window_pieces_*: the drafts' windows numbered through -- target j's first window is the exclusive sum of ceil(target_len / window)
@@ -849,6 +927,25 @@ def window_gbase(target_id, target_len, window):
     return first[_np(target_id, np.int64)].astype(np.uint64), int(first[-1])
 
 
+def window_drafts(target_off, target_len, window):
+    """doff, dlen for bsa_window_msa_*, the sibling of window_gbase: the drafts' windows numbered through as there, window m of target j is the
+    slice that starts at target_off[j] + m * window and has target_len[j] - m * window bases left (the pass takes min(dlen, window) of them).
+    target_off: where each target starts in the draft array (bytes, or bases of a packed one); -> (doff as uint64, dlen as uint32), one entry a
+    window.  Host only."""
+    window = int(window)
+    if window <= 0:
+        raise ValueError("window_drafts: window must be positive")
+    to, tl = _np(target_off, np.uint64), _np(target_len, np.uint64)
+    if len(to) != len(tl):
+        raise ValueError("window_drafts: one offset per target")
+    per = ((tl + np.uint64(window - 1)) // np.uint64(window)).astype(np.int64)
+    j = np.repeat(np.arange(len(tl)), per)
+    first = np.zeros(len(tl) + 1, dtype=np.int64)
+    first[1:] = np.cumsum(per)
+    m = (np.arange(int(first[-1]), dtype=np.int64) - first[j]).astype(np.uint64) * np.uint64(window)
+    return (to[j] + m).astype(np.uint64), np.minimum(tl[j] - m, np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
 def cigar_windows_bound(tlen, window):
     """bsa_cigar_windows_bound: sum of ceil(tlen / window), a window arena (records) that always suffices; 0 for window == 0; host only"""
     tlen = _np(tlen, np.uint32)
@@ -860,6 +957,13 @@ def piece_cigars_bound(cigar_off, npiece):
     of a pair share a column (those of one cigar_windows call); host only"""
     off = _np(cigar_off, np.uint64)
     return int(lib().bsa_piece_cigars_bound(_p(off) if len(off) else None, max(len(off) - 1, 0), int(npiece)))
+
+
+def window_msa_bound(piece_off, window, ins_units):
+    """bsa_window_msa_bound: a column arena (bytes) that always suffices for the pieces of one chain -- window * (depth + 4) summed over the windows
+    plus ins_units * (the largest depth + 4), ins_units the I units of all the alignments' words; host only"""
+    off = _np(piece_off, np.uint64)
+    return int(lib().bsa_window_msa_bound(_p(off) if len(off) else None, max(len(off) - 1, 0), int(window), int(ins_units)))
 
 
 def synth_pairs_host(n, L, eps=0.10, seed=20240611, first_pair=0):

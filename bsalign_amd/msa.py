@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import LIB_PATH, BsaError
+from . import LIB_PATH, BsaError, CNS_WINDOW_DTYPE      # noqa: F401 (bsa_cns_window_t, defined with the other records)
 
 _lib = None
 E_NOMEM = -3
@@ -87,10 +87,6 @@ def text(cols, idxs, nseq, mlen, cns, qlt, alt, label, mbeg=0, mend=0, linewidth
     nvar = 0 if var is None else var.size
     return _two_pass(lambda o, cap, need: lib().bsa_msa_text(_p(cols), _p(idxs), nseq, mlen, _p(cns), _p(qlt), _p(alt), _p(var), nvar,
                                                             label.encode(), mbeg, mend, linewidth, o, cap, C.byref(need)))
-
-
-CNS_WINDOW_DTYPE = np.dtype([("cols_off", np.uint64), ("idxs_off", np.uint64), ("out_off", np.uint64),
-                             ("nall", np.uint32), ("nseq", np.uint32), ("nmax", np.uint32), ("mlen", np.uint32)])
 
 
 def call_consensus(cols, idxs, nall, nseq, nmax, mlen, par7):

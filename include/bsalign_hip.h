@@ -26,6 +26,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "bsalign_msa.h"           /* bsa_cns_window_t, the record bsa_window_msa_* writes */
 
 #ifdef __cplusplus
 extern "C" {
@@ -711,6 +712,95 @@ int      bsa_piece_cigars_batch(bsa_ctx_t *ctx,
                                 const bsa_result_t *out, const uint32_t *cigar, const uint64_t *cigar_off, size_t n,
                                 const bsa_piece_t *piece, size_t npiece,
                                 uint32_t *pcig, size_t pcig_cap, uint64_t *pcig_off /* npiece + 1 */, uint32_t *pstatus /* npiece, may be NULL */);
+
+/* bsa_window_msa_* : every window's draft-anchored multiple alignment, in the `msacols` layout of bsalign_msa.h -- what bsa_msa_call_consensus_batch,
+ *                    bsa_msa_text, bsa_msa_binary_write and bsa_msa_consensus take.  A window's pieces (bsa_window_pieces_*) with their guides
+ *                    (bsa_piece_cigars_*) already are a multiple alignment against the window's slice of the draft: every piece row is anchored to draft
+ *                    columns, and the only new columns are the insertion columns between draft columns.  This pass writes that alignment down as columns,
+ *                    with the bsa_cns_window_t record of every window, so that the chain align -> windows -> pieces -> guides -> MSA -> consensus needs
+ *                    neither the blob, the CIGAR arena, the pieces nor the guides on the host.
+ *                    A pass over public outputs (bsa_window_msa.hip): it touches no plan and changes no existing call.
+ * inputs           : d_piece, d_piece_off (nwin + 1), d_bases are what bsa_window_pieces_run left, piece_cap and bases_cap the room of d_piece and d_bases;
+ *                    d_pcig, d_pcig_off (piece_cap + 1) what bsa_piece_cigars_run left for the same piece_cap, pcig_cap the room of d_pcig.
+ * draft slice      : window g's slice is L = min(dlen[g], window) bases, base j = draft[doff[g] + j] & 3 at 1 B/base; with BSA_MODE_SEQ2BIT in flags draft is
+ *                    BaseBank.bits words and doff a base offset, layout and rules as for the align calls (d_draft 8-byte aligned, _run: BSA_E_ARG otherwise).
+ *                    The caller makes doff and dlen on the host from its targets' offsets and lengths (Python: window_drafts).  Precondition: the L bases
+ *                    of every window lie inside the draft.
+ * rows             : depth = piece_off[g + 1] - piece_off[g]; a window has depth 0 and no piece rows if piece_off[g + 1] > piece_cap or piece_off[g + 1] <
+ *                    piece_off[g].  Row r < depth is piece piece_off[g] + r, row depth is the draft: nall = depth + 1 and a column is mrow = depth + 4 bytes
+ *                    (nall rows, then the three consensus bytes).  The draft is the LAST row, so the caller decides whether it votes: nseq = depth leaves it
+ *                    out (vote 0), nseq = depth + 1 counts it (vote 1).
+ * a live piece     : piece j is LIVE if and only if all of these hold -- it has words and they are readable: pcig_off[j] < pcig_off[j + 1] <= pcig_cap; every
+ *                    word's op is M, I, D, = or X; every word's length is at least 1; the first and the last word are diagonal; the lengths of the words
+ *                    that advance q sum to len and those of the words that advance t to t_last - t_first + 1 (both sums in 64 bits); len >= 1; base_off + len
+ *                    <= bases_cap; and, with a = t_first % window and b = a + (t_last - t_first), b < L.  This predicate is the only door to a piece's words
+ *                    and codes: nothing the caller puts into these arrays makes the pass read outside them.  Every piece bsa_piece_cigars_run cuts from a
+ *                    complete chain is live; a piece with BSA_PIECE_ST_NOT_ON_PATH has no words and is dead.
+ * insertion columns: ins[j], 0 <= j < L, is the largest number of I units any live piece of the window has directly in front of draft column j (I words that
+ *                    follow each other add up); ins[0] = 0 always, a guide starting on a diagonal word.  Draft column j is MSA column c[j] = j + ins[0] + ..
+ *                    + ins[j]; mlen = L + the sum of ins (64 bits).  A window whose mlen would reach 2^31 has mlen 0 and no bytes.
+ * a live row       : for a <= j <= b: at c[j] the piece's code & 3 if j is a diagonal column of its guide, 4 if the guide deletes j; for a < j the m >= 0 bases
+ *                    the piece inserts in front of j go to the first m of the ins[j] columns in front of c[j], left-aligned and in read order, the others get
+ *                    4.  Every column in front of c[a] -- the insertion columns in front of c[a] included -- and every column behind c[b] gets 5: the code 5
+ *                    marks both ends of a read as the reference's MSA does (bspoa.h:3215-3234); 6 is never written.
+ * other bytes      : a dead row is 5 throughout; the draft row holds its base at every c[j] and 4 in every insertion column; the three consensus bytes of
+ *                    every column are written as 4, 0, 0.
+ * not in any MSA   : I units that fall exactly between the last aligned column of one window and the first of the next are in no piece
+ *                    (bsa_cigar_windows_* defines the pieces so) and therefore in no window's MSA.
+ * Example          : window = 10, one window, L = 10, draft 0 1 2 3 0 1 2 3 0 1;
+ *                      piece 0: t 0..9, words 4M 2I 6M,    codes 0 1 2 3 2 2 0 1 2 3 0 1;
+ *                      piece 1: t 2..7, words 2M 1I 1D 3M, codes 2 3 1 1 2 3.
+ *                    Only ins[4] = 2 is non-zero: mlen = 12, the draft columns are MSA columns 0 1 2 3 6 7 8 9 10 11, and
+ *                      row 0 (piece 0)  0 1 2 3 2 2 0 1 2 3 0 1
+ *                      row 1 (piece 1)  5 5 2 3 1 4 4 1 2 3 5 5      (its one inserted base left-aligned, then 4; draft column 4 deleted)
+ *                      draft row        0 1 2 3 4 4 0 1 2 3 0 1
+ *                    Column i is the 6 bytes row0[i] row1[i] draft[i] 4 0 0; the window is 72 bytes; cwin = {0, ~0, 0, nall 3, nseq = nmax = 2 + vote, mlen 12}.
+ * d_cwin[g]        : the record bsa_msa_call_consensus_batch takes, written for every window by every run: cols_off = d_cols_off[g], idxs_off = ~0 (storage
+ *                    order), out_off = the exclusive sum of mlen over the windows, nall = depth + 1, nseq = nmax = depth + vote, mlen.
+ * _bound           : host only, no GPU.  The sum over the windows of window * (depth_g + 4), plus ins_units * (the largest depth + 4), saturating; piece_off is
+ *                    the nwin + 1 offsets on the host, ins_units the I units of all the alignments' words (for instance the sum of out[k].ins).  It always
+ *                    suffices for the pieces of ONE chain: bytes = sum of (L_g + sum of ins_g)(depth_g + 4) with L_g <= window; ins_g[j] is a maximum over the
+ *                    window's pieces and so at most the sum of their I units in front of j; no two pieces of a pair share a column, so every I unit of a pair
+ *                    lies in at most one piece, and all insertion columns together are at most ins_units, each of at most (largest depth + 4) bytes.  It is
+ *                    loose where many reads insert at the same place; a count-only run (cols_cap 0) gives the exact need in d_cols_off[nwin].
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (4 bytes for every draft column of nwin * window, 1 byte a piece of piece_cap, 32 bytes a window; a run that has to grow it
+ *                    may synchronise once; BSA_E_NOMEM when it cannot).  window above 4096 is BSA_E_UNSUPPORTED (a window's line of ins / c stays in LDS;
+ *                    polishers use 500).
+ * arena            : the contract of bsa_window_pieces_run with one arena and the window as the unit.  For ANY cols_cap, 0 with a non-NULL d_cols and a NULL
+ *                    d_cols with cols_cap 0 (a count-only run) included:
+ *                      - all nwin + 1 entries of d_cols_off (bytes) and all nwin records of d_cwin are written and are those of a run with a large arena;
+ *                      - d_cols_off[nwin] is the number of bytes needed;
+ *                      - window g is written if and only if d_cols_off[g + 1] <= cols_cap;
+ *                      - a written window is written whole: every byte of every column;
+ *                      - a window that is not written has no byte of its range touched;
+ *                      - nothing at or above cols_cap, nor at or above the total, is touched;
+ *                      - the arena is never used as scratch.
+ *                    The output is a function of the inputs alone; a run leaves nothing behind that a later run reads.
+ * _batch           : all pointers are HOST memory; piece_cap is the number of pieces.  It uploads the pieces, codes, guides and the draft as far as the windows
+ *                    speak of it, runs, downloads the offsets and records FIRST and synchronises: cols_cap too small is BSA_E_CIGAR_CAP there, cols_off[nwin]
+ *                    = the bytes needed, cols untouched.  After it cols and cwin go to bsa_msa_call_consensus_batch as they are.
+ * errors (both)    : window == 0; flag bits other than BSA_MODE_SEQ2BIT; vote > 1; a NULL piece_off, pcig_off or cols_off; with nwin > 0 a NULL draft, doff, dlen
+ *                    or cwin; a cap without its arena; nwin or piece_cap above 0xFFFFFFF0: BSA_E_ARG.  nwin == 0 writes cols_off[0] = 0.
+ * Example          : a polisher's step on resident reads, behind the three calls of the bsa_piece_cigars_* example --
+ *                      bsa_window_msa_run(ctx, d_piece, d_piece_off, nwin, cap, d_bases, sum_qlen, d_pcig, cigar_cap + cap, d_pcig_off, d_draft, d_doff, d_dlen,
+ *                                         500, 0, 0, d_cols, cols_cap, d_cols_off, d_cwin); bsa_ctx_sync(ctx);
+ *                    then the MSA of every window, or only its consensus, comes down. */
+uint64_t bsa_window_msa_bound(const uint64_t *piece_off /* nwin + 1, host */, size_t nwin, uint32_t window, uint64_t ins_units);
+int      bsa_window_msa_run(bsa_ctx_t *ctx,
+                            const bsa_piece_t *d_piece, const uint64_t *d_piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                            const uint8_t *d_bases, size_t bases_cap,
+                            const uint32_t *d_pcig, size_t pcig_cap, const uint64_t *d_pcig_off /* piece_cap + 1 */,
+                            const uint8_t *d_draft, const uint64_t *d_doff /* nwin */, const uint32_t *d_dlen /* nwin */,
+                            uint32_t window, uint32_t flags /* BSA_MODE_SEQ2BIT or 0: the draft only */, uint32_t vote /* 0: nseq = depth; 1: the draft votes too */,
+                            uint8_t *d_cols, size_t cols_cap, uint64_t *d_cols_off /* nwin + 1, bytes */, bsa_cns_window_t *d_cwin /* nwin */);
+int      bsa_window_msa_batch(bsa_ctx_t *ctx,
+                              const bsa_piece_t *piece, const uint64_t *piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                              const uint8_t *bases, size_t bases_cap,
+                              const uint32_t *pcig, size_t pcig_cap, const uint64_t *pcig_off /* piece_cap + 1 */,
+                              const uint8_t *draft, const uint64_t *doff /* nwin */, const uint32_t *dlen /* nwin */,
+                              uint32_t window, uint32_t flags, uint32_t vote,
+                              uint8_t *cols, size_t cols_cap, uint64_t *cols_off /* nwin + 1 */, bsa_cns_window_t *cwin /* nwin */);
 
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
