@@ -155,6 +155,8 @@ def lib():
         if hasattr(L, "bsa_align8_x_choice_internal"):
             L.bsa_align8_x_choice_internal.argtypes = [C.POINTER(AlignParams), C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint64, C.c_int,
                                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+        if hasattr(L, "bsa_align8_trace_choice_internal"):
+            L.bsa_align8_trace_choice_internal.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         L.bsa_align_plan_destroy.argtypes = [vp]
         L.bsa_align_plan_destroy.restype = None
         L.bsa_align_plan_cells.argtypes = [vp]
@@ -317,6 +319,24 @@ def align8_x_choice(par, count, max_tlen, static_band=False, code_fmt=0, score=F
     if rc < 0:
         raise ValueError("bsa_align8_x_choice_internal: bad arguments")
     d = dict(zip(X_CHOICE_FIELDS, (int(v) for v in out)))
+    d.update(name=name.value.decode(), launch=rc == 1)
+    return d
+
+
+TRACE_CHOICE_FIELDS = ("form", "W", "fmt", "lanes", "pairs_per_block", "grid")
+TR_NONE, TR_WAVE, TR_LDS, TR_SIMPLE, TR_CODES2, TR_CODES2_WAVE = range(6)
+
+
+def align8_trace_choice(bw, pw, code_fmt, count, cus=256):
+    """what the traceback launcher of the compact path would launch for a chunk of `count` pairs at bandwidth bw with gap model pw (0 linear, 1 affine, 2 two
+    pieces) over slots of code format code_fmt (trace_choose; host only, under the BSA_ALIGN8_TRACE_* knobs as they stand): a dict of TRACE_CHOICE_FIELDS
+    (lanes: pairs per wave of the LDS walker, else 0) plus "name" and "launch" (False: the launcher returns an error)"""
+    out = (C.c_uint64 * len(TRACE_CHOICE_FIELDS))()
+    name = C.create_string_buffer(200)
+    rc = lib().bsa_align8_trace_choice_internal(bw, pw, code_fmt, count, cus, out, name, len(name))
+    if rc < 0:
+        raise ValueError("bsa_align8_trace_choice_internal: bad arguments")
+    d = dict(zip(TRACE_CHOICE_FIELDS, (int(v) for v in out)))
     d.update(name=name.value.decode(), launch=rc == 1)
     return d
 

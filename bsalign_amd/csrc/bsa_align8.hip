@@ -17,7 +17,7 @@
 //
 // HBM traffic per row and pair: one row record (see bsa_common.h) = (pw+1)*bw + 72 bytes written once;
 // the traceback kernel re-derives the path from those records exactly like the reference's backcal.
-#include "bsa_common.h"
+#include "bsa_walk.h"
 #include "bsa_dpp.h"
 #include <cstdlib>
 
@@ -441,7 +441,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 	const uint32_t ppos = a.first + g;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ out[pair] = rs; cig_cnt[ppos] = 0; return; }
 	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
 	const uint8_t *qseq = a.qst + a.qpoff[pair];
@@ -453,14 +453,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 	const int mode = a.mode & 3;
 	const int gapo1 = a.gapo1, gape1 = a.gape1, gapo2 = a.gapo2, gape2 = a.gape2;
 	// cigar scratch: the tail end of this pair's slot (tlen + 3 row records long)
-	uint32_t *cig_end = R.cigar_end(tlen);
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
+	bsa_cig_lane_t cig(R.cigar_end(tlen));
 	bool bad = false;
 	// ---- end cell (bsalign.h:4023-4045)
 	rs.score = BSA_SCORE_MIN;
@@ -482,9 +475,9 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 	}
 	if(!bad){ int b = R.beg(rs.te); if(rs.qe < b || rs.qe >= b + (int)bw) bad = true; }
 	// ---- backcal (bsalign.h:3704-3852)
+	uint32_t cg = 0;
 	if(!bad){
 		int Hs0 = 0, Hs1, pend = 0, prior_match = 0;
-		uint32_t cg = 0;
 		rs.qb = rs.qe; rs.qe++;
 		rs.tb = rs.te; rs.te++;
 		Hs1 = R.mtx_getscore(rs.tb, rs.qb);
@@ -494,7 +487,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 				Hs0 = R.mtx_getscore(rs.tb, rs.qb);
 				long long t = go + (long long)(pend >> 4) * ge;
 				if(Hs0 + t == Hs1){
-					cg = cig_add(cg, 2, (uint32_t)(pend >> 4));
+					cg = cig.add(cg, 2, (uint32_t)(pend >> 4));
 					rs.del += pend >> 4; rs.aln += pend >> 4;
 					Hs1 = Hs0; pend = 0;
 				} else {
@@ -542,11 +535,11 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 			if(bt == 0){
 				if(qseq[rs.qb] == tseq[rs.tb]) rs.mat++; else rs.mis++;
 				rs.qb--; rs.tb--; rs.aln++;
-				cg = cig_add(cg, 0, 1);
+				cg = cig.add(cg, 0, 1);
 				Hs1 = Hs0;
 			} else if(bt == 1){
 				if(rs.qb <= 0){
-					cg = cig_add(cg, 1, 1);
+					cg = cig.add(cg, 1, 1);
 					Hs1 = Hs0;
 					rs.qb--; rs.ins++; rs.aln++;
 				} else {
@@ -556,7 +549,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 						long long t = (pw == 2) ? (long long)max(gapo1 + sz * gape1, gapo2 + sz * gape2) : (long long)(gapo1 + sz * gape1);
 						Hs0 = R.mtx_getscore(rs.tb, rs.qb - sz);
 						if(Hs0 + t == Hs1){
-							cg = cig_add(cg, 1, (uint32_t)sz);
+							cg = cig.add(cg, 1, (uint32_t)sz);
 							Hs1 = Hs0;
 							rs.qb -= sz; rs.ins += sz; rs.aln += sz;
 							found = true;
@@ -571,26 +564,8 @@ __global__ void __launch_bounds__(64) k_align8_backcal(const Align8Args a, int p
 				continue;
 			}
 		}
-		if(!bad){
-			if(mode == BSA_MODE_OVERLAP){
-				if(cg) cig_push(cg);
-			} else {
-				uint32_t op = 0, sz = 0;
-				if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-				else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-				rs.aln += (int)sz;
-				cg = cig_add(cg, op, sz);
-				if(cg) cig_push(cg);
-			}
-			rs.qb++; rs.tb++;
-		}
 	}
-	if(bad){
-		atomicOr(&a.status[pair], BSA_ST_TRACE);
-		ncig = 0;
-	}
-	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	bsa_walk_end_lane(a.status, pair, ppos, mode, bad, cg, cig, rs, out, cig_cnt, false);       // (a flagged pair keeps its score and end cell)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -641,29 +616,14 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 	RowView R;
 	R.init(a.rows + a.slot_off[ppos], tlen, a.bw, pw);
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(skip){ if(live){ out[pair] = rs; cig_cnt[ppos] = 0; } return; }
 	const uint8_t *qseq = a.qst + a.qpoff[pair];
 	const uint8_t *tseq = a.tst + a.tpoff[pair];
 	const uint32_t bw = a.bw;
 	const int gapo1 = a.gapo1, gape1 = a.gape1, gapo2 = a.gapo2, gape2 = a.gape2;
-	uint32_t *cig_end = R.cigar_end(tlen);
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
-	uint64_t qwin = 0, twin = 0; int qwb = -1000, twb = -1000;     // 8 bases of each sequence in a register window
-	auto qbase_at = [&](int idx) -> int {
-		if(idx < qwb || idx >= qwb + 8){ qwb = max(idx - 7, 0); __builtin_memcpy(&qwin, qseq + qwb, 8); }
-		return (int)((qwin >> (8 * (idx - qwb))) & 0xffu);
-	};
-	auto tbase_at = [&](int idx) -> int {
-		if(idx < twb || idx >= twb + 8){ twb = max(idx - 7, 0); __builtin_memcpy(&twin, tseq + twb, 8); }
-		return (int)((twin >> (8 * (idx - twb))) & 0xffu);
-	};
+	bsa_cig_lane_t cig(R.cigar_end(tlen));
+	bsa_base_win_t qwin(qseq), twin(tseq);
 	bool bad = false;
 	// ---- end cell (global, bsalign.h:4034-4037)
 	const int lastbeg = R.beg((int)tlen - 1);
@@ -728,7 +688,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 			const int hv = rec_prefix<W>(rc, CELLS, fx);
 			const long long t = (pw == 2) ? (long long)max(gapo1 + isz * gape1, gapo2 + isz * gape2) : (long long)(gapo1 + isz * gape1);
 			if(hv + t == Hs1){
-				cg = cig_add(cg, 1, (uint32_t)isz);
+				cg = cig.add(cg, 1, (uint32_t)isz);
 				Hs1 = hv;
 				rs.qb -= isz; rs.ins += isz; rs.aln += isz;
 				state = ST_CELL;
@@ -741,7 +701,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 			const int hv = rec_prefix<W>(rc, CELLS, fx);
 			const long long t = go + (long long)(pend >> 4) * ge;
 			if(hv + t == Hs1){
-				cg = cig_add(cg, 2, (uint32_t)(pend >> 4));
+				cg = cig.add(cg, 2, (uint32_t)(pend >> 4));
 				rs.del += pend >> 4; rs.aln += pend >> 4;
 				Hs1 = hv; pend = 0;
 				state = ST_CELL;
@@ -759,7 +719,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 				ee = (pw >= 1) ? rec_byte(r1, W + xk) : gapo1 + gape1;
 				qq = (pw == 2) ? rec_byte(r1, 2 * W + xk) : 0;
 			}
-			const int qbase = qbase_at(rs.qb), tbase = tbase_at(rs.tb);
+			const int qbase = qwin.at(rs.qb), tbase = twin.at(rs.tb);
 			const uint32_t mr = (tbase == 0) ? a.mrow[0] : (tbase == 1) ? a.mrow[1] : (tbase == 2) ? a.mrow[2] : a.mrow[3];
 			const int s = __builtin_amdgcn_sbfe((int)mr, 8u * (uint32_t)qbase, 8u);
 			const int h = Hs1 - Hs0;
@@ -783,11 +743,11 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 				if(qbase == tbase) rs.mat++; else rs.mis++;
 				rs.qb--; rs.aln++;
 				row_down();
-				cg = cig_add(cg, 0, 1);
+				cg = cig.add(cg, 0, 1);
 				Hs1 = Hs0;
 			} else if(bt == 1){
 				if(rs.qb <= 0){
-					cg = cig_add(cg, 1, 1);
+					cg = cig.add(cg, 1, 1);
 					Hs1 = Hs0;
 					rs.qb--; rs.ins++; rs.aln++;
 				} else {
@@ -803,21 +763,7 @@ __global__ void __launch_bounds__(64) k_align8_backcal_g(const Align8Args a, bsa
 			}
 		}
 	}
-	if(!bad){
-		uint32_t op = 0, sz = 0;      // global: leading clip becomes I / D (bsalign.h:3827-3842)
-		if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-		else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-		rs.aln += (int)sz;
-		cg = cig_add(cg, op, sz);
-		if(cg) cig_push(cg);
-		rs.qb++; rs.tb++;
-	}
-	if(bad){
-		atomicOr(&a.status[pair], BSA_ST_TRACE);
-		ncig = 0;
-	}
-	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	bsa_walk_end_lane(a.status, pair, ppos, BSA_MODE_GLOBAL, bad, cg, cig, rs, out, cig_cnt, false);      // (global only; a flagged pair keeps its score and end cell)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -858,24 +804,26 @@ hipError_t bsa_launch_align8_fwd(const Align8Args &a, int pw, hipStream_t st){
 	}
 }
 
-hipError_t bsa_launch_align8_backcal(const Align8Args &a, int pw, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
-	// global mode, W <= 8: two-wave traceback (walker + prefetching helper); BSA_ALIGN8_TRACE1=1 forces the one-wave kernel
-	const bool force_one = [](){ const char *e = bsa_env("BSA_ALIGN8_TRACE1"); return e && e[0] == '1'; }();
-	if(!force_one && (a.mode & 3) == BSA_MODE_GLOBAL && a.bw / 16 <= 8 && a.count){
-		const uint32_t nb = (a.count + TRACE_LANES - 1) / TRACE_LANES;
-#define TRACE_CASE(WW) case WW: \
-			if(pw == 0) hipLaunchKernelGGL((k_align8_backcal_g<WW, 0>), dim3(nb), dim3(64), 0, st, a, out, cig_cnt); \
-			else if(pw == 1) hipLaunchKernelGGL((k_align8_backcal_g<WW, 1>), dim3(nb), dim3(64), 0, st, a, out, cig_cnt); \
-			else hipLaunchKernelGGL((k_align8_backcal_g<WW, 2>), dim3(nb), dim3(64), 0, st, a, out, cig_cnt); \
-			return hipGetLastError();
-		switch(a.bw / 16){
-			TRACE_CASE(1) TRACE_CASE(2) TRACE_CASE(4) TRACE_CASE(8)
-			default: break;
-		}
-#undef TRACE_CASE
+// global mode, W <= 8: the register-record walker, 16 pairs a wave (BSA_ALIGN8_TRACE1=1 forces the literal kernel); else nullptr: k_align8_backcal
+typedef void (*backcal_g_kernel_t)(const Align8Args, bsa_result_t*, uint32_t*);
+static backcal_g_kernel_t backcal_g_kernel(const Align8Args &a, int pw){
+	const char *e = bsa_env("BSA_ALIGN8_TRACE1");
+	if((e && e[0] == '1') || (a.mode & 3) != BSA_MODE_GLOBAL) return nullptr;
+	// (the instances are named in the order <W, 0>, <W, 1>, <W, 2>: the compiler emits them in the order they are named in, and what these kernels share is inlined by it)
+#define BACKCAL_G(WW) (pw <= 1 ? (pw == 0 ? k_align8_backcal_g<WW, 0> : k_align8_backcal_g<WW, 1>) : k_align8_backcal_g<WW, 2>)
+	switch(a.bw / 16){
+		case 1: return BACKCAL_G(1);
+		case 2: return BACKCAL_G(2);
+		case 4: return BACKCAL_G(4);
+		case 8: return BACKCAL_G(8);
+		default: return nullptr;
 	}
-	const uint32_t blocks = (a.count + 63) / 64;
-	if(blocks == 0) return hipSuccess;
-	hipLaunchKernelGGL(k_align8_backcal, dim3(blocks), dim3(64), 0, st, a, pw, out, cig_cnt);
+#undef BACKCAL_G
+}
+
+hipError_t bsa_launch_align8_backcal(const Align8Args &a, int pw, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
+	if(a.count == 0) return hipSuccess;
+	if(const backcal_g_kernel_t k = backcal_g_kernel(a, pw)) hipLaunchKernelGGL(k, dim3((a.count + TRACE_LANES - 1) / TRACE_LANES), dim3(64), 0, st, a, out, cig_cnt);
+	else hipLaunchKernelGGL(k_align8_backcal, dim3((a.count + 63) / 64), dim3(64), 0, st, a, pw, out, cig_cnt);
 	return hipGetLastError();
 }

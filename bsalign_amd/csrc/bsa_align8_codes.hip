@@ -14,69 +14,8 @@
 // a leading insertion / deletion; overlap and extend start at the best end cell -- the end-of-query candidates the
 // forward pass recorded or the maximum of the last row (row_max, bsalign.h:3213-3329, taken here from the end record) --
 // and overlap stops without a leading gap (bsalign.h:3822-3842).
-#include "bsa_common.h"
-
-// end cell of the non-global modes from the forward pass's end record (bsa_common.h bsa_code_end_t): the best
-// end-of-query candidate (strictly greater wins, in row order) against the maximum of the last row, whose tie rules are
-// the reference's: per lane the first best 32-vector chunk, lanes reduced in its register order, then the first
-// maximum inside the winning chunk (bsalign.h:3213-3329).
-// ref_bw != 0 (a whole-query band run at a wider register-kernel width, bsa_api.hip): the row maximum is taken over the
-// REFERENCE's band -- ref_bw columns, or roundup(qlen, 16) when ref_bw == 1 -- in the reference's striping of it (WR cells per
-// lane), whose tie rules depend on that striping; the end record is in natural order, so only the lane boundaries move.
-// `er`: the end record (the spare rows of a code slot, or the whole slot of a score-only pair: k_align8_score_finish)
-template<int WK>
-static __device__ void codes_end_cell(const bsa_code_end_t *er, uint32_t qlen, uint32_t tlen, uint32_t ref_bw, int &score, int &qe, int &te){
-	const int8_t *us = (const int8_t*)(er + 1);           // natural band order: lane l, cell x at l * W + x
-	const uint32_t W = ref_bw == 0u ? (uint32_t)WK : ref_bw == 1u ? (max(qlen, 1u) + 15u) / 16u : ref_bw / 16u;
-	// H in front of band position p, from the kernel's own 16 block starts
-	auto before = [&](uint32_t p) -> int { const uint32_t b = p / (uint32_t)WK; int h = er->ubegs[b]; for(uint32_t i = b * (uint32_t)WK; i < p; i++) h += us[i]; return h; };
-	int best = BSA_SCORE_MIN, bte = 0;
-	for(int l = 0; l < 16; l++){
-		const int sc = er->cand_sc[l], t = er->cand_te[l];
-		if(sc > best || (sc == best && sc != BSA_SCORE_MIN && t < bte)){ best = sc; bte = t; }
-	}
-	int lmax[16]; uint32_t lchunk[16];
-	for(uint32_t l = 0; l < 16; l++){
-		int base = (W == (uint32_t)WK) ? er->ubegs[l] : before(l * W);
-		lmax[l] = BSA_SCORE_MIN; lchunk[l] = 0;
-		for(uint32_t i = 0, c = 0; i < (uint32_t)W; i += 32, c++){
-			const uint32_t n = (i + 32 < (uint32_t)W) ? 32 : (uint32_t)W - i;
-			int run = 0, cmax = -32767;
-			for(uint32_t x = 0; x < n; x++){
-				run += us[l * W + i + x];
-				run = min(max(run, -32768), 32767);
-				cmax = max(cmax, run);
-			}
-			if(base + cmax > lmax[l]){ lmax[l] = base + cmax; lchunk[l] = c; }
-			base += run;
-		}
-	}
-	int ms, lane;
-	{
-		int mm[4], ii[4];
-		for(int k = 0; k < 4; k++){
-			int m01, i01, m23, i23;
-			if(lmax[4 + k] > lmax[k]){ m01 = lmax[4 + k]; i01 = 4 + k; } else { m01 = lmax[k]; i01 = k; }
-			if(lmax[12 + k] > lmax[8 + k]){ m23 = lmax[12 + k]; i23 = 12 + k; } else { m23 = lmax[8 + k]; i23 = 8 + k; }
-			if(m23 > m01){ mm[k] = m23; ii[k] = i23; } else { mm[k] = m01; ii[k] = i01; }
-		}
-		ms = mm[0]; lane = ii[0];
-		for(int k = 1; k < 4; k++) if(mm[k] > ms){ ms = mm[k]; lane = ii[k]; }
-	}
-	uint32_t x = lchunk[lane] * 32u, jj = x;
-	const uint32_t y = min(x + 32u, (uint32_t)W);
-	int umax = BSA_SCORE_MIN, uscr = 0;
-	for(; x < y; x++){
-		uscr += us[lane * W + x];
-		if(uscr > umax){ jj = x; umax = uscr; }
-	}
-	if(ms > best){ score = ms; qe = er->rbeg_last + (int)((uint32_t)lane * W + jj); te = (int)tlen - 1; }
-	else { score = best; qe = (int)qlen - 1; te = bte; }
-}
-template<int WK>
-static __device__ void codes_end_cell(const uint8_t *rows, uint32_t RB, uint32_t qlen, uint32_t tlen, uint32_t ref_bw, int &score, int &qe, int &te){
-	codes_end_cell<WK>((const bsa_code_end_t*)(rows + (size_t)bsa_code_rows(tlen) * RB), qlen, tlen, ref_bw, score, qe, te);
-}
+#include "bsa_walk.h"
+#include <cstdio>
 
 // BSA_MODE_SCORE_ONLY: result of a pair from the record the SCORE forward kernel left (bsa_score_rec_bytes), with the walkers' end-cell rules.
 // One thread a pair.  qb, tb, mat, mis, ins, del and aln would need the traceback: -1.  A global pair whose band never reached the query end is
@@ -150,22 +89,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 	const bool live = lane < (uint32_t)LPW && g < a.count;
 	const uint32_t ppos = a.first + (live ? g : 0u);
 	const uint32_t pair = a.order[ppos];
+	const bsa_code_slot_t s(a, ppos, pair, RB);
+	const uint32_t qlen = s.qlen;
+	const uint8_t *qseq = s.qseq, *tseq = s.tseq, *rows = s.rows;
+	const int *begs = s.begs;
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	const bool skip = !live || a.status[pair] != 0u;
-	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
-	const uint8_t *qseq = a.qst + a.qpoff[pair];
-	const uint8_t *tseq = a.tst + a.tpoff[pair];
-	const int *begs = (const int*)(a.rows + a.slot_off[ppos]);
-	const uint8_t *rows = (const uint8_t*)begs + bsa_begs_bytes(tlen);
-	uint32_t *cig_end = (uint32_t*)(rows + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * RB);
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
+	bsa_cig_lane_t cig(s.cig_end);
 	auto base_for = [&](uint32_t y) -> uint32_t { return (y == 0u) ? 0u : ((y >= 14u) ? 13u : y - 1u); };
 	auto slot = [&](int r) -> uint4& { return ring[((uint32_t)r & (CODE_RING_ROWS - 1u)) * (uint32_t)LPW + (live ? lane : 0u)]; };
 	// requested at the last service point, still in registers: two row groups (bsa_common.h: four rows of a block are 16
@@ -214,16 +145,9 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 	bool bad = false, done = skip;
 	uint32_t cury = 0;
 	if(!skip){
-		if(type == BSA_MODE_GLOBAL){
-			rs.score = begs[tlen + 1];
-			if(rs.score == (int)0x80000000u) bad = true;            // band never reached the query end (bsalign.h:4034)
-			rs.qe = (int)qlen - 1; rs.te = (int)tlen - 1;
-		} else codes_end_cell<W>(rows, RB, qlen, tlen, a.ref_bw, rs.score, rs.qe, rs.te);
+		int lastbeg;
+		bad = bsa_walk_start_lane<W>(a, s, RB, type, rs, lastbeg);
 		if(qlen >= (1u << 26)) bad = true;                          // band offsets are kept in 26 bits here
-		const int lastbeg = begs[rs.te + 1];
-		if(rs.qe < lastbeg || rs.qe >= lastbeg + bw) bad = true;    // end cell outside the stored band
-		rs.qb = rs.qe; rs.qe++;
-		rs.tb = rs.te; rs.te++;
 		cury = (uint32_t)max(min(rs.qb - lastbeg, bw - 1), 0) / W;
 		// prologue: two windows, filed immediately
 		request(rs.tb >> 2, base_for(cury)); file();
@@ -282,7 +206,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 			const uint32_t op = is_m ? 0u : is_i ? 1u : 2u;
 			const uint32_t n = is_i ? (uint32_t)sz : 1u;
 			const bool ext = op == (cg & 0xfu);
-			if(!ext && cg) cig_push(cg);
+			if(!ext && cg) cig.push(cg);
 			cg = ext ? cg + (n << 4) : ((n << 4) | op);
 			rs.mat += (is_m && same) ? 1 : 0;
 			rs.mis += (is_m && !same) ? 1 : 0;
@@ -298,9 +222,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 		// ---- general step (service iterations only)
 		slow = false;
 		if(bad || rs.qb < 0 || rs.tb < 0){
-			// a deletion run that reached row -1: an ordinary move with linear gaps; with affine gaps only the e = -63 sentinel of
-			// row -1 leads here and the reference then compares real scores -- literal path (BSA_ST_TRACE, hand-over)
-			if(dlen && !bad && (!lin || rs.qb >= bw)) bad = true;
+			if(dlen && !bad && bsa_drun_top_bad(lin, rs.qb, bw)) bad = true;        // a deletion run that reached row -1
 			dlen = 0;
 			done = true;
 			continue;
@@ -321,7 +243,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 		if(dlen){
 			// deletion run (bsalign.h:3730-3744), counted row by row: this row ends it if its stored e is a fresh opening
 			if(po & bit) dlen = 0;
-			else { cg = cig_add(cg, 2, 1); rs.del++; rs.aln++; rs.tb--; continue; }
+			else { cg = cig.add(cg, 2, 1); rs.del++; rs.aln++; rs.tb--; continue; }
 		}
 		const bool pmatch = !(rs.qb == beg_p && rs.qb) && prior_match;      // bsalign.h:3761-3764
 		const bool fm = (pm & bit) != 0u, fd = (pd & bit) != 0u;
@@ -335,10 +257,10 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 			const int tbase = (int)((e.w >> 26) & 3u);
 			if(qbase == tbase) rs.mat++; else rs.mis++;
 			rs.qb--; rs.aln++; rs.tb--;
-			cg = cig_add(cg, 0, 1);
+			cg = cig.add(cg, 0, 1);
 		} else if(bt == 1){
 			if(rs.qb <= 0){
-				cg = cig_add(cg, 1, 1);
+				cg = cig.add(cg, 1, 1);
 				rs.qb--; rs.ins++; rs.aln++;
 			} else {
 				int sz = 0;
@@ -356,36 +278,18 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_lds(const Align8Args 
 					}
 					if(sz == 0){ bad = true; slow = true; continue; }  // the reference's scan finds no length either: it never terminates
 				}
-				cg = cig_add(cg, 1, (uint32_t)sz);
+				cg = cig.add(cg, 1, (uint32_t)sz);
 				rs.qb -= sz; rs.ins += sz; rs.aln += sz;
 			}
 		} else {
-			cg = cig_add(cg, 2, 1); rs.del++; rs.aln++;
+			cg = cig.add(cg, 2, 1); rs.del++; rs.aln++;
 			dlen = 1; rs.tb--;                                           // the rows above decide how far the run goes
 		}
 		prior_match = 1;
 		if(rs.qb < 0 || rs.tb < 0) slow = true;                          // termination is a general step
 	}
 	if(skip){ if(live){ out[pair] = rs; cig_cnt[ppos] = 0; } return; }
-	if(!bad){
-		if(type == BSA_MODE_OVERLAP){ if(cg) cig_push(cg); }         // overlap: the alignment simply starts here (bsalign.h:3822-3826)
-		else {
-			uint32_t op = 0, sz = 0;      // global / extend: what is left at the top becomes a leading I / D (bsalign.h:3827-3842)
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			rs.aln += (int)sz;
-			cg = cig_add(cg, op, sz);
-			if(cg) cig_push(cg);
-		}
-		rs.qb++; rs.tb++;
-	}
-	if(bad){
-		atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	bsa_walk_end_lane(a.status, pair, ppos, type, bad, cg, cig, rs, out, cig_cnt);
 }
 
 // ---- one walk per wave (bandwidth 128) ---------------------------------------------------------------------------
@@ -421,67 +325,17 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 	const uint32_t ppos = a.first + blockIdx.x;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = 0; } return; }
 	const int type = a.mode & 3;
 	const bool lin = a.gapo1 == 0;
-	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
-	const uint8_t *qseq = a.qst + a.qpoff[pair];
-	const uint8_t *tseq = a.tst + a.tpoff[pair];
-	const int *begs = (const int*)(a.rows + a.slot_off[ppos]);
-	const uint8_t *rows = (const uint8_t*)begs + bsa_begs_bytes(tlen);
-	const uint32_t *codes = (const uint32_t*)rows;
-	uint32_t *cig_end = (uint32_t*)(rows + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * RB);
-	// CIGAR.  The walker does not merge runs step by step (that logic was a third of the scalar instructions of a step): it records
-	// one TOKEN per gap event -- (matches / mismatches since the last event, op, length), one token per lane -- and a gap that simply
-	// goes on (no match in between, same op: the rows of a deletion run, consecutive insertions) extends its own token, so that
-	// neighbouring tokens never carry the same op.  Every 64 tokens (the last one stays: it may still grow) the lanes turn their
-	// tokens into words side by side: an M word when the run is not empty, then the gap's word, positions from two prefix popcounts
-	// (word m at cig_end - (m + 1)).  The word sequence is the reference's run-length merge (bsalign.h:409-417) of the same op stream.
-	uint32_t ncig = 0, tokN = 0, tokB = 0;            // words written; the lane's token: run length, len << 2 | op (op 0: none)
-	// (uniform) tokens held; key = op of the last token << 28 | match / mismatch columns since it, so that "same op, nothing in between" is one
-	// compare (a walk over codes has fewer than 2^26 columns: bsa_api.hip sends longer queries to the literal kernels)
-	uint32_t ntok = 0, key = 0;
-	constexpr uint32_t KEYM = 0x0FFFFFFFu;
-	auto tok_flush = [&](uint32_t cnt){
-		const bool in = lane < cnt;
-		tokN &= KEYM;
-		const bool hasA = in && tokN != 0u, hasB = in && (tokB & 3u) != 0u;
-		const uint64_t mA = __ballot(hasA), mB = __ballot(hasB);
-		const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mA, 0u))
-			+ __builtin_amdgcn_mbcnt_hi((uint32_t)(mB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mB, 0u));
-		uint32_t *wp = cig_end - (ncig + below + 1u);
-		if(hasA){ *wp = tokN << 4; wp--; }                // (tokN: already without the key's op field)
-		if(hasB) *wp = ((tokB >> 2) << 4) | (tokB & 3u);
-		ncig += (uint32_t)(__popcll(mA) + __popcll(mB));
-	};
-	auto emit = [&](uint32_t op, uint32_t len){
-		if(op == 0u){ key += len; return; }
-		if(key == (op << 28)){ if(lane + 1u == ntok) tokB += len << 2; return; }
-		if(ntok == 64u){
-			tok_flush(63u);
-			tokN = (uint32_t)__builtin_amdgcn_readlane((int)tokN, 63); tokB = (uint32_t)__builtin_amdgcn_readlane((int)tokB, 63);
-			ntok = 1u;
-		}
-		if(lane == ntok){ tokN = key; tokB = (len << 2) | op; }       // (the op field of the key is masked off when the token is written)
-		ntok++; key = op << 28;
-	};
-	auto cig_finish = [&](){                          // the matches behind the last event, then everything out
-		if(key & KEYM){
-			if(ntok == 64u){ tok_flush(64u); ntok = 0u; }
-			if(lane == ntok){ tokN = key; tokB = 0u; }
-			ntok++; key = 0u;
-		}
-		tok_flush(ntok); ntok = 0u;
-	};
-	bool bad = false;
-	if(type == BSA_MODE_GLOBAL){
-		rs.score = begs[tlen + 1];
-		if(rs.score == (int)0x80000000u) bad = true;               // band never reached the query end (bsalign.h:4034)
-		rs.qe = (int)qlen - 1; rs.te = (int)tlen - 1;
-	} else codes_end_cell<W>(rows, RB, qlen, tlen, a.ref_bw, rs.score, rs.qe, rs.te);
-	rs.score = __builtin_amdgcn_readfirstlane(rs.score); rs.qe = __builtin_amdgcn_readfirstlane(rs.qe); rs.te = __builtin_amdgcn_readfirstlane(rs.te);
-	{ const int lb = begs[rs.te + 1]; if(rs.qe < lb || rs.qe >= lb + bw) bad = true; }
+	const bsa_code_slot_t s(a, ppos, pair, RB);
+	const uint32_t qlen = s.qlen;
+	const uint8_t *qseq = s.qseq, *tseq = s.tseq;
+	const int *begs = s.begs;
+	const uint32_t *codes = (const uint32_t*)s.rows;
+	bsa_cig_wave_t cig(s.cig_end, lane);               // one token per gap event (bsa_walk.h)
+	bool bad = bsa_walk_start_wave<W, false>(a, s, RB, type, lane, rs);
 	int x = rs.qe, y = rs.te;
 	const int x_start = x, y_start = y;
 	rs.qe++; rs.te++;
@@ -651,7 +505,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 			// n match / mismatch columns (possibly none): the count goes to the token key, the mismatches to the lanes' own counts (vector work on a
 			// unit that had room; masks, popcounts and additions of the scalar unit were a sixth of the walk's instructions when it was bound by them)
 			vmis += (uint32_t)((int)lane - k0) < (uint32_t)n ? nei : 0u;
-			key += (uint32_t)n;
+			cig.key += (uint32_t)n;
 			x -= n; y -= n;
 			if(k == 64) break;
 			if(x < 0 || y < 0){ walking = false; break; }
@@ -660,13 +514,13 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 			const uint32_t shk = (uint32_t)__builtin_amdgcn_readlane((int)sh, k);
 			if(shk < plim){
 				if(dl31){
-					emit(2u, 1u); y--; k0 = k + 1;
+					cig.emit(2u, 1u); y--; k0 = k + 1;
 					if(k0 > 63) break;
 					continue;
 				}
 				const uint32_t ik = (uint32_t)__builtin_amdgcn_readlane((int)info, k);
 				if(ik & 1u){
-					emit(2u, 1u); y--; dl31 = 0x80000000u; k0 = k + 1;
+					cig.emit(2u, 1u); y--; dl31 = 0x80000000u; k0 = k + 1;
 					if(k0 > 63) break;
 					continue;
 				}
@@ -675,7 +529,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 					const uint32_t cand = (uint32_t)__builtin_amdgcn_readlane((int)RR, k) & ((1u << ck) - 1u);
 					if(cand){
 						const int sz = (int)ck - (31 - (int)__builtin_clz(cand));
-						emit(1u, (uint32_t)sz);
+						cig.emit(1u, (uint32_t)sz);
 						x -= sz; rs.ins += sz; k0 = k;
 						if(x + k0 - 63 < qw_lo && qw_lo > 0){ q_refill(x); qKr = (int)lane + qw_lo; }
 						continue;
@@ -707,7 +561,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 			const Code wck = code_at(yb);
 			if(dl31){
 				if(wck.o & bit) dl31 = 0u;
-				else { emit(2u, 1u); y--; k0 = k + 1; if(k0 > 63) break; continue; }
+				else { cig.emit(2u, 1u); y--; k0 = k + 1; if(k0 > 63) break; continue; }
 			}
 			const bool pmatch = prior && !(x == bpk && x != 0);
 			const bool fm = (wck.m & bit) != 0u, fd = (wck.d & bit) != 0u;
@@ -717,10 +571,10 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 			prior = 1; plim = 32u; RMe = RM;
 			if(bt == 0){
 				vmis += (int)lane == k ? nei : 0u;
-				emit(0u, 1u);
+				cig.emit(0u, 1u);
 				x--; y--; k0 = k + 1;
 			} else if(bt == 1){
-				if(x <= 0){ emit(1u, 1u); x--; rs.ins++; }
+				if(x <= 0){ cig.emit(1u, 1u); x--; rs.ins++; }
 				else {
 					int sz = 0;
 					const uint32_t cand = wck.r & ~((bit << 1) - 1u) & FULL;
@@ -734,13 +588,13 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 						}
 						if(sz == 0){ bad = true; walking = false; break; }  // the reference's scan finds no length either
 					}
-					emit(1u, (uint32_t)sz);
+					cig.emit(1u, (uint32_t)sz);
 					x -= sz; rs.ins += sz;
 				}
 				k0 = k;
 				if(x >= 0 && x + k0 - 63 < qw_lo && qw_lo > 0){ q_refill(x); qKr = (int)lane + qw_lo; }
 			} else {
-				emit(2u, 1u);
+				cig.emit(2u, 1u);
 				y--; dl31 = 0x80000000u; k0 = k + 1;
 			}
 			if(k0 > 63) break;
@@ -749,33 +603,8 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_wave(const Align8Args
 		T -= 64;
 		curB = nxtB; curC = nxtC; nxtB = nx2B;
 	}
-	if(!bad && dl31 && y < 0 && (!lin || x >= bw)) bad = true;        // a deletion run that reached row -1: see the general step of the LDS kernel
-	if(!bad){
-		rs.qb = x; rs.tb = y;
-		{
-			// rs.ins holds the inserted columns of the walk: the other totals follow from its two ends, the mismatches from the lanes' counts
-			const int mcols = (x_start - x) - rs.ins;
-			uint32_t t = vmis;
-			t += (uint32_t)__shfl_xor((int)t, 32); t += (uint32_t)__shfl_xor((int)t, 16); t += (uint32_t)__shfl_xor((int)t, 8);
-			t += (uint32_t)__shfl_xor((int)t, 4); t += (uint32_t)__shfl_xor((int)t, 2); t += (uint32_t)__shfl_xor((int)t, 1);
-			rs.mis = __builtin_amdgcn_readfirstlane((int)t); rs.mat = mcols - rs.mis;
-			rs.del = (y_start - y) - mcols;
-		}
-		if(type != BSA_MODE_OVERLAP){
-			uint32_t op = 0, sz = 0;
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			if(sz) emit(op, sz);
-		}
-		cig_finish();
-		rs.qb++; rs.tb++;
-		rs.aln = rs.mat + rs.mis + rs.ins + rs.del;
-	} else {
-		if(lane == 0) atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = ncig; }
+	if(!bad && dl31 && y < 0 && bsa_drun_top_bad(lin, x, bw)) bad = true;        // a deletion run that reached row -1
+	bsa_walk_end_wave(a.status, s, ppos, type, bad, x, y, x_start, y_start, vmis, cig, rs, out, cig_cnt);
 }
 
 // plain version: every access is a load (W = 16, and the reference point for the prefetching kernel)
@@ -788,31 +617,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 	const uint32_t ppos = a.first + g;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ out[pair] = rs; cig_cnt[ppos] = 0; return; }
-	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
-	const uint8_t *qseq = a.qst + a.qpoff[pair];
-	const uint8_t *tseq = a.tst + a.tpoff[pair];
-	const int *begs = (const int*)(a.rows + a.slot_off[ppos]);
-	const uint8_t *rows = (const uint8_t*)begs + bsa_begs_bytes(tlen);
-	uint32_t *cig_end = (uint32_t*)(rows + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * RB);
+	const bsa_code_slot_t s(a, ppos, pair, RB);
+	const int *begs = s.begs;
+	const uint8_t *rows = s.rows;
 	const int bw = W * 16;
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
-	uint64_t qwin = 0, twin = 0; int qwb = -1000, twb = -1000;     // 8 bases of each sequence in a register window
-	auto qbase_at = [&](int idx) -> int {
-		if(idx < qwb || idx >= qwb + 8){ qwb = max(idx - 7, 0); __builtin_memcpy(&qwin, qseq + qwb, 8); }
-		return (int)((qwin >> (8 * (idx - qwb))) & 0xffu);
-	};
-	auto tbase_at = [&](int idx) -> int {
-		if(idx < twb || idx >= twb + 8){ twb = max(idx - 7, 0); __builtin_memcpy(&twin, tseq + twb, 8); }
-		return (int)((twin >> (8 * (idx - twb))) & 0xffu);
-	};
+	bsa_cig_lane_t cig(s.cig_end);
+	bsa_base_win_t qwin(s.qseq), twin(s.tseq);
 	// flag planes of block y of row r: (M, D, R, Od), each W bits, cell k = bit W-1-k
 	struct Code { uint32_t m, d, r, o; };
 	auto unpack = [&](uint32_t w0, uint32_t w1) -> Code {
@@ -826,21 +638,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 		const uint32_t *rp = (const uint32_t*)rows + bsa_code_off((uint32_t)r, y, CW);
 		return unpack(rp[0], (CW > 1) ? rp[CW - 1] : 0u);
 	};
-	bool bad = false;
 	const int type = a.mode & 3;
 	const bool lin = a.gapo1 == 0;                                 // linear gaps (piecewise 0)
-	if(type == BSA_MODE_GLOBAL){
-		rs.score = begs[tlen + 1];
-		if(rs.score == (int)0x80000000u) bad = true;               // band never reached the query end (bsalign.h:4034)
-		rs.qe = (int)qlen - 1; rs.te = (int)tlen - 1;
-	} else codes_end_cell<W>(rows, RB, qlen, tlen, a.ref_bw, rs.score, rs.qe, rs.te);
-	if(rs.qe < begs[rs.te + 1] || rs.qe >= begs[rs.te + 1] + bw) bad = true;
-	rs.qb = rs.qe; rs.qe++;
-	rs.tb = rs.te; rs.te++;
+	int lastbeg;
+	bool bad = bsa_walk_start_lane<W>(a, s, RB, type, rs, lastbeg);
 	int prior_match = 0;
 	uint32_t cg = 0;
 	// band offsets: beg_c = row tb, beg_p = row tb-1 (begs[r + 1] = offset of row r, begs[0] = 0 for row -1)
-	int beg_c = begs[rs.tb + 1], beg_p = begs[rs.tb], beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
+	int beg_c = lastbeg, beg_p = begs[rs.tb], beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
 	auto row_up = [&](){ rs.tb--; beg_c = beg_p; beg_p = beg_pp; beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0; };
 	while(!bad){
 		if(rs.qb < 0 || rs.tb < 0) break;
@@ -855,14 +660,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 		else bt = fd ? 2 : fm ? 0 : 1;
 		prior_match = 1;
 		if(bt == 0){
-			const int qbase = qbase_at(rs.qb), tbase = tbase_at(rs.tb);
+			const int qbase = qwin.at(rs.qb), tbase = twin.at(rs.tb);
 			if(qbase == tbase) rs.mat++; else rs.mis++;
 			rs.qb--; rs.aln++;
 			row_up();
-			cg = cig_add(cg, 0, 1);
+			cg = cig.add(cg, 0, 1);
 		} else if(bt == 1){
 			if(rs.qb <= 0){
-				cg = cig_add(cg, 1, 1);
+				cg = cig.add(cg, 1, 1);
 				rs.qb--; rs.ins++; rs.aln++;
 			} else {
 				// nearest cell to the left with R set: cells left of k are the bits above `bit`
@@ -879,7 +684,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 					}
 					if(sz == 0){ bad = true; break; }                     // the reference's scan finds no length either: it never terminates
 				}
-				cg = cig_add(cg, 1, (uint32_t)sz);
+				cg = cig.add(cg, 1, (uint32_t)sz);
 				rs.qb -= sz; rs.ins += sz; rs.aln += sz;
 			}
 		} else {
@@ -887,7 +692,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 			int len = 1;
 			for(;;){
 				const int r = rs.tb - len;
-				if(r == -1){ if(!lin || rs.qb >= bw) bad = true; break; }      // see the general step of the LDS kernel
+				if(r == -1){ if(bsa_drun_top_bad(lin, rs.qb, bw)) bad = true; break; }
 				const int pr = rs.qb - begs[r + 1];
 				if(pr < 0 || pr >= bw){ bad = true; break; }
 				const Code c2 = load_code(r, (uint32_t)pr / W);
@@ -895,31 +700,13 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes_simple(const Align8Ar
 				len++;
 			}
 			if(bad) break;
-			cg = cig_add(cg, 2, (uint32_t)len);
+			cg = cig.add(cg, 2, (uint32_t)len);
 			rs.del += len; rs.aln += len;
 			rs.tb -= len;
 			beg_c = begs[rs.tb + 1]; beg_p = (rs.tb >= 0) ? begs[rs.tb] : 0; beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
 		}
 	}
-	if(!bad){
-		if(type == BSA_MODE_OVERLAP){ if(cg) cig_push(cg); }         // overlap: the alignment simply starts here (bsalign.h:3822-3826)
-		else {
-			uint32_t op = 0, sz = 0;      // global / extend: what is left at the top becomes a leading I / D (bsalign.h:3827-3842)
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			rs.aln += (int)sz;
-			cg = cig_add(cg, op, sz);
-			if(cg) cig_push(cg);
-		}
-		rs.qb++; rs.tb++;
-	}
-	if(bad){
-		atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	bsa_walk_end_lane(a.status, pair, ppos, type, bad, cg, cig, rs, out, cig_cnt);
 }
 
 // two-piece gaps (8 bits per cell, bsa_common.h; bandwidth 128): the plain walker with the nine facts of a cell
@@ -935,50 +722,26 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2(const Align8Args a, 
 	const uint32_t ppos = a.first + g;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ out[pair] = rs; cig_cnt[ppos] = 0; return; }
-	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
-	const uint8_t *qseq = a.qst + a.qpoff[pair];
-	const uint8_t *tseq = a.tst + a.tpoff[pair];
-	const int *begs = (const int*)(a.rows + a.slot_off[ppos]);
-	const uint8_t *rows = (const uint8_t*)begs + bsa_begs_bytes(tlen);
-	uint32_t *cig_end = (uint32_t*)(rows + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * RB);
+	const bsa_code_slot_t s(a, ppos, pair, RB);
+	const int *begs = s.begs;
+	const uint8_t *rows = s.rows;
 	const int bw = W * 16;
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
-	uint64_t qwin = 0, twin = 0; int qwb = -1000, twb = -1000;     // 8 bases of each sequence in a register window
-	auto qbase_at = [&](int idx) -> int {
-		if(idx < qwb || idx >= qwb + 8){ qwb = max(idx - 7, 0); __builtin_memcpy(&qwin, qseq + qwb, 8); }
-		return (int)((qwin >> (8 * (idx - qwb))) & 0xffu);
-	};
-	auto tbase_at = [&](int idx) -> int {
-		if(idx < twb || idx >= twb + 8){ twb = max(idx - 7, 0); __builtin_memcpy(&twin, tseq + twb, 8); }
-		return (int)((twin >> (8 * (idx - twb))) & 0xffu);
-	};
+	bsa_cig_lane_t cig(s.cig_end);
+	bsa_base_win_t qwin(s.qseq), twin(s.tseq);
 	auto load_code = [&](int r, uint32_t y) -> Blk {
 		Blk b; const uint32_t *p = (const uint32_t*)rows + bsa_code_off((uint32_t)r, y, CW);
 #pragma unroll
 		for(uint32_t d = 0; d < CW; d++) b.w[d] = p[d];
 		return b;
 	};
-	bool bad = false;
 	const int type = a.mode & 3;
-	if(type == BSA_MODE_GLOBAL){
-		rs.score = begs[tlen + 1];
-		if(rs.score == (int)0x80000000u) bad = true;           // band never reached the query end (bsalign.h:4034)
-		rs.qe = (int)qlen - 1; rs.te = (int)tlen - 1;
-	} else codes_end_cell<W>(rows, RB, qlen, tlen, a.ref_bw, rs.score, rs.qe, rs.te);      // overlap / extend: the best end cell (bsalign.h:4023-4046)
-	if(rs.qe < begs[rs.te + 1] || rs.qe >= begs[rs.te + 1] + bw) bad = true;
-	rs.qb = rs.qe; rs.qe++;
-	rs.tb = rs.te; rs.te++;
+	int lastbeg;
+	bool bad = bsa_walk_start_lane<W>(a, s, RB, type, rs, lastbeg);
 	int prior_match = 0;
 	uint32_t cg = 0;
-	int beg_c = begs[rs.tb + 1], beg_p = begs[rs.tb], beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
+	int beg_c = lastbeg, beg_p = begs[rs.tb], beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
 	auto row_up = [&](){ rs.tb--; beg_c = beg_p; beg_p = beg_pp; beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0; };
 	while(!bad){
 		if(rs.qb < 0 || rs.tb < 0) break;
@@ -995,14 +758,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2(const Align8Args a, 
 		else bt = d ? 2 : fM ? 0 : 1;
 		prior_match = 1;
 		if(bt == 0){
-			const int qbase = qbase_at(rs.qb), tbase = tbase_at(rs.tb);
+			const int qbase = qwin.at(rs.qb), tbase = twin.at(rs.tb);
 			if(qbase == tbase) rs.mat++; else rs.mis++;
 			rs.qb--; rs.aln++;
 			row_up();
-			cg = cig_add(cg, 0, 1);
+			cg = cig.add(cg, 0, 1);
 		} else if(bt == 1){
 			if(rs.qb <= 0){
-				cg = cig_add(cg, 1, 1);
+				cg = cig.add(cg, 1, 1);
 				rs.qb--; rs.ins++; rs.aln++;
 			} else {
 				// the chains that equal h here (only reached with M = D = D2 = 0): the nearest cell to the left at which one of
@@ -1031,7 +794,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2(const Align8Args a, 
 					const bool h1 = ch1 && (plane(hc, 4) & hb) != 0u, h2 = ch2 && (plane(hc, 5) & hb) != 0u;
 					if(!((h1 && c1 >= c2) || (h2 && c2 >= c1))){ bad = true; break; }
 				}
-				cg = cig_add(cg, 1, (uint32_t)sz);
+				cg = cig.add(cg, 1, (uint32_t)sz);
 				rs.qb -= sz; rs.ins += sz; rs.aln += sz;
 			}
 		} else {
@@ -1052,31 +815,13 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2(const Align8Args a, 
 				len++;
 			}
 			if(bad) break;
-			cg = cig_add(cg, 2, (uint32_t)len);
+			cg = cig.add(cg, 2, (uint32_t)len);
 			rs.del += len; rs.aln += len;
 			rs.tb -= len;
 			beg_c = begs[rs.tb + 1]; beg_p = (rs.tb >= 0) ? begs[rs.tb] : 0; beg_pp = (rs.tb >= 1) ? begs[rs.tb - 1] : 0;
 		}
 	}
-	if(!bad){
-		if(type == BSA_MODE_OVERLAP){ if(cg) cig_push(cg); }     // overlap: the alignment simply starts here (bsalign.h:3822-3826)
-		else {
-			uint32_t op = 0, sz = 0;      // global / extend: what is left at the top becomes a leading I / D (bsalign.h:3827-3842)
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			rs.aln += (int)sz;
-			cg = cig_add(cg, op, sz);
-			if(cg) cig_push(cg);
-		}
-		rs.qb++; rs.tb++;
-	}
-	if(bad){
-		atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	bsa_walk_end_lane(a.status, pair, ppos, type, bad, cg, cig, rs, out, cig_cnt);
 }
 
 // ---- two-piece gaps, one walk per wave (the scheme of k_align8_trace_codes_wave with the nine facts of a cell) -------
@@ -1097,70 +842,17 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 	const uint32_t ppos = a.first + blockIdx.x;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = 0; } return; }
-	const uint32_t qlen = a.qlen[pair], tlen = a.tlen[pair];
-	const uint8_t *qseq = a.qst + a.qpoff[pair];
-	const uint8_t *tseq = a.tst + a.tpoff[pair];
-	const int *begs = (const int*)(a.rows + a.slot_off[ppos]);
-	const uint8_t *rows = (const uint8_t*)begs + bsa_begs_bytes(tlen);
-	const uint32_t *codes = (const uint32_t*)rows;
-	uint32_t *cig_end = (uint32_t*)(rows + ((size_t)bsa_code_rows(tlen) + BSA_CODE_SPARE_ROWS) * RB);
+	const bsa_code_slot_t s(a, ppos, pair, RB);
+	const uint32_t qlen = s.qlen;
+	const uint8_t *qseq = s.qseq, *tseq = s.tseq;
+	const int *begs = s.begs;
+	const uint32_t *codes = (const uint32_t*)s.rows;
 	const int go1 = a.gapo1, ge1 = a.gape1, go2 = a.gapo2, ge2 = a.gape2;
-	// CIGAR.  The walker does not merge runs step by step (that logic was a third of the scalar instructions of a step): it records
-	// one TOKEN per gap event -- (matches / mismatches since the last event, op, length), one token per lane -- and a gap that simply
-	// goes on (no match in between, same op: the rows of a deletion run, consecutive insertions) extends its own token, so that
-	// neighbouring tokens never carry the same op.  Every 64 tokens (the last one stays: it may still grow) the lanes turn their
-	// tokens into words side by side: an M word when the run is not empty, then the gap's word, positions from two prefix popcounts
-	// (word m at cig_end - (m + 1)).  The word sequence is the reference's run-length merge (bsalign.h:409-417) of the same op stream.
-	uint32_t ncig = 0, tokN = 0, tokB = 0;            // words written; the lane's token: run length, len << 2 | op (op 0: none)
-	// (uniform) tokens held; key = op of the last token << 28 | match / mismatch columns since it (k_align8_trace_codes_wave)
-	uint32_t ntok = 0, key = 0;
-	constexpr uint32_t KEYM = 0x0FFFFFFFu;
-	auto tok_flush = [&](uint32_t cnt){
-		const bool in = lane < cnt;
-		tokN &= KEYM;
-		const bool hasA = in && tokN != 0u, hasB = in && (tokB & 3u) != 0u;
-		const uint64_t mA = __ballot(hasA), mB = __ballot(hasB);
-		const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mA, 0u))
-			+ __builtin_amdgcn_mbcnt_hi((uint32_t)(mB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mB, 0u));
-		uint32_t *wp = cig_end - (ncig + below + 1u);
-		if(hasA){ *wp = tokN << 4; wp--; }
-		if(hasB) *wp = ((tokB >> 2) << 4) | (tokB & 3u);
-		ncig += (uint32_t)(__popcll(mA) + __popcll(mB));
-	};
-	auto emit = [&](uint32_t op, uint32_t len){
-		if(op == 0u){ key += len; return; }
-		if(key == (op << 28)){ if(lane + 1u == ntok) tokB += len << 2; return; }
-		if(ntok == 64u){
-			tok_flush(63u);
-			tokN = (uint32_t)__builtin_amdgcn_readlane((int)tokN, 63); tokB = (uint32_t)__builtin_amdgcn_readlane((int)tokB, 63);
-			ntok = 1u;
-		}
-		if(lane == ntok){ tokN = key; tokB = (len << 2) | op; }       // (the op field of the key is masked off when the token is written)
-		ntok++; key = op << 28;
-	};
-	auto cig_finish = [&](){                          // the matches behind the last event, then everything out
-		if(key & KEYM){
-			if(ntok == 64u){ tok_flush(64u); ntok = 0u; }
-			if(lane == ntok){ tokN = key; tokB = 0u; }
-			ntok++; key = 0u;
-		}
-		tok_flush(ntok); ntok = 0u;
-	};
-	bool bad = false;
+	bsa_cig_wave_t cig(s.cig_end, lane);               // one token per gap event (bsa_walk.h)
 	const int type = a.mode & 3;
-	if(type == BSA_MODE_GLOBAL){
-		rs.score = begs[tlen + 1];
-		if(rs.score == (int)0x80000000u) bad = true;               // band never reached the query end (bsalign.h:4034)
-		rs.qe = (int)qlen - 1; rs.te = (int)tlen - 1;
-	} else {
-		// overlap / extend: the best end cell (bsalign.h:4023-4046), worked out by one lane from the end record behind the code rows
-		int sc = 0, qe = 0, te = 0;
-		if(lane == 0) codes_end_cell<8>((const uint8_t*)codes, 64u * CW, qlen, tlen, a.ref_bw, sc, qe, te);
-		rs.score = __shfl(sc, 0); rs.qe = __shfl(qe, 0); rs.te = __shfl(te, 0);
-	}
-	{ const int lb = begs[rs.te + 1]; if(rs.qe < lb || rs.qe >= lb + bw) bad = true; }
+	bool bad = bsa_walk_start_wave<8, true>(a, s, RB, type, lane, rs);      // (the end cell of overlap / extend: worked out by one lane)
 	int x = rs.qe, y = rs.te;
 	const int x_start = x, y_start = y;
 	rs.qe++; rs.te++;
@@ -1267,21 +959,21 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 			const int n = k - k0;
 			// n match / mismatch columns (possibly none): the count goes to the token key, the mismatches to the lanes' own counts
 			vmis += (uint32_t)((int)lane - k0) < (uint32_t)n ? nei : 0u;
-			key += (uint32_t)n;
+			cig.key += (uint32_t)n;
 			x -= n; y -= n;
 			if(k == 64) break;
 			if(x < 0 || y < 0){ walking = false; break; }
 			const uint32_t shk = (uint32_t)__builtin_amdgcn_readlane((int)sh, k);
 			if(shk < plim){
 				if(dl){
-					emit(2u, 1u); y--; k0 = k + 1;
+					cig.emit(2u, 1u); y--; k0 = k + 1;
 					if(k0 > 63) break;
 					continue;
 				}
 				const uint32_t ik = (uint32_t)__builtin_amdgcn_readlane((int)info, k);
 				if(ik & 3u){                                                // not M and D or D2 set: a deletion of that piece opens
 					if(x == 0){ bad = true; walking = false; break; }         // (at query column 0 the flags cannot tell: k_align8_trace_codes2)
-					emit(2u, 1u); y--; dl = (ik & 1u) ? DL1 : DL2; ndl = 0u; k0 = k + 1;
+					cig.emit(2u, 1u); y--; dl = (ik & 1u) ? DL1 : DL2; ndl = 0u; k0 = k + 1;
 					if(k0 > 63) break;
 					continue;
 				}
@@ -1300,7 +992,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 						const int c1 = go1 + sz * ge1, c2 = go2 + sz * ge2;
 						const bool h1 = ch1 && ((r1k >> hp) & 1u), h2 = ch2 && ((r2k >> hp) & 1u);
 						if(!((h1 && c1 >= c2) || (h2 && c2 >= c1))){ bad = true; walking = false; break; }
-						emit(1u, (uint32_t)sz);
+						cig.emit(1u, (uint32_t)sz);
 						x -= sz; rs.ins += sz; k0 = k;
 						if(x + k0 - 63 < qw_lo && qw_lo > 0){ q_refill(x); qKr = (int)lane + qw_lo; }
 						continue;
@@ -1324,7 +1016,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 			const uint2 cc = code_at(yb);
 			if(dl){
 				if((cc.y >> (dl == DL2 ? 24 : 16)) & bit){ dl = 0u; ndl = 0x80000000u; }
-				else { emit(2u, 1u); y--; k0 = k + 1; if(k0 > 63) break; continue; }
+				else { cig.emit(2u, 1u); y--; k0 = k + 1; if(k0 > 63) break; continue; }
 			}
 			const bool pmatch = prior && !(x == bpk && x != 0);
 			const bool fA = (cc.x & bit) != 0u, fD = ((cc.x >> 8) & bit) != 0u, fD2 = ((cc.x >> 16) & bit) != 0u, fB = ((cc.x >> 24) & bit) != 0u;
@@ -1336,10 +1028,10 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 			prior = 1; plim = 32u; RMe = RM;
 			if(bt == 0){
 				vmis += (int)lane == k ? nei : 0u;
-				emit(0u, 1u);
+				cig.emit(0u, 1u);
 				x--; y--; k0 = k + 1;
 			} else if(bt == 1){
-				if(x <= 0){ emit(1u, 1u); x--; rs.ins++; }
+				if(x <= 0){ cig.emit(1u, 1u); x--; rs.ins++; }
 				else {
 					const bool ch1 = fB, ch2 = fA == fB;
 					auto rplane = [&](const uint2 &w) -> uint32_t { return ((ch1 ? w.y : 0u) | (ch2 ? (w.y >> 8) : 0u)) & 0xFFu; };
@@ -1362,14 +1054,14 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 						const bool h1 = ch1 && (hc.y & hb) != 0u, h2 = ch2 && ((hc.y >> 8) & hb) != 0u;
 						if(!((h1 && c1 >= c2) || (h2 && c2 >= c1))){ bad = true; walking = false; break; }
 					}
-					emit(1u, (uint32_t)sz);
+					cig.emit(1u, (uint32_t)sz);
 					x -= sz; rs.ins += sz;
 				}
 				k0 = k;
 				if(x >= 0 && x + k0 - 63 < qw_lo && qw_lo > 0){ q_refill(x); qKr = (int)lane + qw_lo; }
 			} else {
 				if(x == 0){ bad = true; walking = false; break; }             // (query column 0: k_align8_trace_codes2)
-				emit(2u, 1u);
+				cig.emit(2u, 1u);
 				y--; dl = d == 1 ? DL1 : DL2; ndl = 0u; k0 = k + 1;
 			}
 			if(k0 > 63) break;
@@ -1379,99 +1071,72 @@ __global__ void __launch_bounds__(64) k_align8_trace_codes2_wave(const Align8Arg
 		curB = nxtB; curC = nxtC; nxtB = nx2B;
 	}
 	if(!bad && dl && y < 0) bad = true;                            // a deletion run that reached row -1: the reference compares real scores there -- literal path
-	if(!bad){
-		rs.qb = x; rs.tb = y;
-		{
-			// rs.ins holds the inserted columns of the walk: the other totals follow from its two ends, the mismatches from the lanes' counts
-			const int mcols = (x_start - x) - rs.ins;
-			uint32_t t = vmis;
-			t += (uint32_t)__shfl_xor((int)t, 32); t += (uint32_t)__shfl_xor((int)t, 16); t += (uint32_t)__shfl_xor((int)t, 8);
-			t += (uint32_t)__shfl_xor((int)t, 4); t += (uint32_t)__shfl_xor((int)t, 2); t += (uint32_t)__shfl_xor((int)t, 1);
-			rs.mis = __builtin_amdgcn_readfirstlane((int)t); rs.mat = mcols - rs.mis;
-			rs.del = (y_start - y) - mcols;
-		}
-		if(type != BSA_MODE_OVERLAP){              // global / extend: what is left at the top becomes a leading I / D (bsalign.h:3827-3842)
-			uint32_t op = 0, sz = 0;
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			if(sz) emit(op, sz);
-		}
-		cig_finish();
-		rs.qb++; rs.tb++;
-		rs.aln = rs.mat + rs.mis + rs.ins + rs.del;
-	} else {
-		if(lane == 0) atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = ncig; }
+	bsa_walk_end_wave(a.status, s, ppos, type, bad, x, y, x_start, y_start, vmis, cig, rs, out, cig_cnt);
 }
 
-template<int W>
-static void launch_trace_lds(const Align8Args &a, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
-	// Pairs per wave: 32 where the batch is large enough (100 k pairs on MI355X, ms per launch: 64 -> 46, 32 -> 31.0,
-	// 16 -> 31.2, 8 -> 57: instruction issue binds at few lanes per wave, the walk's own dependent chain at many); smaller
-	// batches take fewer, so that there are still a few waves per SIMD to interleave.
-	int dev = 0, cus = 256;
-	if(hipGetDevice(&dev) == hipSuccess){
-		int v = 0;
-		if(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-	}
-	const uint32_t want_waves = (uint32_t)cus * 4u * 3u;            // about three waves per SIMD
-	uint32_t lanes = 4;
-	while(lanes < 32u && a.count / lanes > want_waves) lanes <<= 1;
-	const dim3 grid((a.count + lanes - 1) / lanes);
-	switch(lanes){
-		case 4:  hipLaunchKernelGGL((k_align8_trace_codes_lds<W, 4>), grid, dim3(64), 0, st, a, out, cig_cnt); break;
-		case 8:  hipLaunchKernelGGL((k_align8_trace_codes_lds<W, 8>), grid, dim3(64), 0, st, a, out, cig_cnt); break;
-		case 16: hipLaunchKernelGGL((k_align8_trace_codes_lds<W, 16>), grid, dim3(64), 0, st, a, out, cig_cnt); break;
-		default: hipLaunchKernelGGL((k_align8_trace_codes_lds<W, 32>), grid, dim3(64), 0, st, a, out, cig_cnt); break;
-	}
-}
-
-// code format 1 (bsa_common.h) is read by the one-walk-per-wave kernel at bandwidth 128 only
-bool bsa_align8_trace_reads_do2(const Align8Args &a, int pw){
+// WHAT THE TRACEBACK OVER CODE SLOTS LAUNCHES (trace_choose decides it once; bsa_launch_align8_trace_codes runs it, bsa_align8_trace_reads_do2 tells the plan which
+// code format the forward pass may write).  BSA_ALIGN8_TRACE_SIMPLE=1: the plain kernels (kept as the reference point); BSA_ALIGN8_TRACE_WAVE=0: the pair-per-lane kernels.
+enum TForm : uint32_t { TR_NONE, TR_WAVE, TR_LDS, TR_SIMPLE, TR_CODES2, TR_CODES2_WAVE };      // k_align8_trace_codes_wave<W, FMT>, _codes_lds<W, lanes>, _codes_simple<W>, _codes2<W>, _codes2_wave
+struct TraceChoice { TForm form; uint32_t W, fmt, lanes, ppb, grid; const char *name; };        // lanes: pairs per wave of the LDS walker (else 0); ppb: pairs a block of 64
+static TraceChoice trace_choose(uint32_t bw, int pw, uint32_t code_fmt, uint32_t count, int cus){
+	TraceChoice c = { TR_NONE, bw / 16u, code_fmt, 0u, 0u, 0u, nullptr };
+	if(bw != 64u && bw != 128u && bw != 256u) return c;
 	const char *se = bsa_env("BSA_ALIGN8_TRACE_SIMPLE"), *we = bsa_env("BSA_ALIGN8_TRACE_WAVE");
-	return pw == 1 && a.bw == 128u && !(se && se[0] == '1') && !(we && we[0] == '0');
+	const bool simple = se && se[0] == '1', wave = !(we && we[0] == '0');
+	TForm f;
+	if(pw == 2) f = (bw == 128u && wave) ? TR_CODES2_WAVE : TR_CODES2;          // (two-piece gaps have one pair-per-lane walker: the plain one)
+	else f = simple ? TR_SIMPLE : wave ? TR_WAVE : bw == 256u ? TR_SIMPLE : TR_LDS;
+	// code format 1 (bsa_common.h) is read by the one-walk-per-wave kernel at bandwidth 128 only, and written for affine gaps only
+	if(code_fmt > 1u || (code_fmt == 1u && !(f == TR_WAVE && bw == 128u && pw == 1))) return c;
+	c.form = f; c.ppb = (f == TR_WAVE || f == TR_CODES2_WAVE) ? 1u : 64u;
+	if(f == TR_LDS){
+		// Pairs per wave: 32 where the batch is large enough (100 k pairs on MI355X, ms per launch: 64 -> 46, 32 -> 31.0,
+		// 16 -> 31.2, 8 -> 57: instruction issue binds at few lanes per wave, the walk's own dependent chain at many); smaller
+		// batches take fewer, so that there are still a few waves per SIMD to interleave.
+		const uint32_t want_waves = (uint32_t)cus * 4u * 3u;            // about three waves per SIMD
+		c.lanes = 4u;
+		while(c.lanes < 32u && count / c.lanes > want_waves) c.lanes <<= 1;
+		c.ppb = c.lanes;
+	}
+	c.grid = (count + c.ppb - 1u) / c.ppb;
+	c.name = f == TR_WAVE ? "k_align8_trace_codes_wave" : f == TR_LDS ? "k_align8_trace_codes_lds" : f == TR_SIMPLE ? "k_align8_trace_codes_simple"
+		: f == TR_CODES2 ? "k_align8_trace_codes2" : "k_align8_trace_codes2_wave";
+	return c;
 }
+// the one place that names each instance
+typedef void (*trace_kernel_t)(const Align8Args, bsa_result_t*, uint32_t*);
+template<int W>
+static trace_kernel_t trace_lds_kernel(uint32_t lanes){
+	return lanes == 4u ? k_align8_trace_codes_lds<W, 4> : lanes == 8u ? k_align8_trace_codes_lds<W, 8> : lanes == 16u ? k_align8_trace_codes_lds<W, 16> : k_align8_trace_codes_lds<W, 32>;
+}
+static trace_kernel_t trace_kernel(const TraceChoice &c){
+	switch(c.form){
+		case TR_WAVE:   return c.W == 4u ? k_align8_trace_codes_wave<4> : c.W == 16u ? k_align8_trace_codes_wave<16> : c.fmt ? k_align8_trace_codes_wave<8, 1> : k_align8_trace_codes_wave<8>;
+		case TR_LDS:    return c.W == 4u ? trace_lds_kernel<4>(c.lanes) : trace_lds_kernel<8>(c.lanes);
+		case TR_SIMPLE: return c.W == 4u ? k_align8_trace_codes_simple<4> : c.W == 8u ? k_align8_trace_codes_simple<8> : k_align8_trace_codes_simple<16>;
+		case TR_CODES2: return c.W == 4u ? k_align8_trace_codes2<4> : c.W == 8u ? k_align8_trace_codes2<8> : k_align8_trace_codes2<16>;
+		case TR_CODES2_WAVE: return k_align8_trace_codes2_wave;
+		default: return nullptr;
+	}
+}
+
+bool bsa_align8_trace_reads_do2(const Align8Args &a, int pw){ return trace_choose(a.bw, pw, 1u, 1u, 1).form != TR_NONE; }
 
 hipError_t bsa_launch_align8_trace_codes(const Align8Args &a, int pw, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st){
 	if(a.count == 0) return hipSuccess;
-	if(a.code_fmt == 1u && !bsa_align8_trace_reads_do2(a, pw)) return hipErrorInvalidValue;
-	if(pw == 2){
-		if(a.bw == 64u){ bsa_last_trace_kernel = "k_align8_trace_codes2"; hipLaunchKernelGGL((k_align8_trace_codes2<4>), dim3((a.count + 63u) / 64u), dim3(64), 0, st, a, out, cig_cnt); return hipGetLastError(); }
-		if(a.bw == 256u){ bsa_last_trace_kernel = "k_align8_trace_codes2"; hipLaunchKernelGGL((k_align8_trace_codes2<16>), dim3((a.count + 63u) / 64u), dim3(64), 0, st, a, out, cig_cnt); return hipGetLastError(); }
-		if(a.bw != 128u) return hipErrorInvalidValue;
-		const char *we = bsa_env("BSA_ALIGN8_TRACE_WAVE");              // =0: the pair-per-lane walker
-		if(we && we[0] == '0'){ bsa_last_trace_kernel = "k_align8_trace_codes2"; hipLaunchKernelGGL((k_align8_trace_codes2<8>), dim3((a.count + 63u) / 64u), dim3(64), 0, st, a, out, cig_cnt); }
-		else { bsa_last_trace_kernel = "k_align8_trace_codes2_wave"; hipLaunchKernelGGL(k_align8_trace_codes2_wave, dim3(a.count), dim3(64), 0, st, a, out, cig_cnt); }
-		return hipGetLastError();
-	}
-	// BSA_ALIGN8_TRACE_SIMPLE=1: the plain kernel (kept as the reference point)
-	const bool simple = [](){ const char *e = bsa_env("BSA_ALIGN8_TRACE_SIMPLE"); return e && e[0] == '1'; }();
-	const uint32_t blocks = (a.count + 63u) / 64u;
-	bsa_last_trace_kernel = simple ? "k_align8_trace_codes_simple" : (a.bw == 256u) ? "k_align8_trace_codes_simple" : "k_align8_trace_codes_lds";
-	// one walk per wave (BSA_ALIGN8_TRACE_WAVE=0: the pair-per-lane kernels)
-	const char *we = bsa_env("BSA_ALIGN8_TRACE_WAVE");
-	const bool wave = !simple && !(we && we[0] == '0');
-	if(wave) bsa_last_trace_kernel = "k_align8_trace_codes_wave";
-	switch(a.bw / 16){
-		case 4:
-			if(simple) hipLaunchKernelGGL((k_align8_trace_codes_simple<4>), dim3(blocks), dim3(64), 0, st, a, out, cig_cnt);
-			else if(wave) hipLaunchKernelGGL((k_align8_trace_codes_wave<4>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			else launch_trace_lds<4>(a, out, cig_cnt, st);
-			break;
-		case 8:
-			if(simple) hipLaunchKernelGGL((k_align8_trace_codes_simple<8>), dim3(blocks), dim3(64), 0, st, a, out, cig_cnt);
-			else if(wave && a.code_fmt == 1u) hipLaunchKernelGGL((k_align8_trace_codes_wave<8, 1>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			else if(wave) hipLaunchKernelGGL((k_align8_trace_codes_wave<8>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			else launch_trace_lds<8>(a, out, cig_cnt, st);
-			break;
-		case 16:
-			if(wave) hipLaunchKernelGGL((k_align8_trace_codes_wave<16>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt);
-			else hipLaunchKernelGGL((k_align8_trace_codes_simple<16>), dim3(blocks), dim3(64), 0, st, a, out, cig_cnt);
-			break;
-		default: return hipErrorInvalidValue;
-	}
+	const TraceChoice c = trace_choose(a.bw, pw, a.code_fmt, a.count, bsa_cus());
+	if(c.form == TR_NONE) return hipErrorInvalidValue;
+	bsa_last_trace_kernel = c.name;
+	hipLaunchKernelGGL(trace_kernel(c), dim3(c.grid), dim3(64), 0, st, a, out, cig_cnt);
 	return hipGetLastError();
+}
+
+// trace_choose as plain numbers on a device of `cus` CUs, under the BSA_ALIGN8_TRACE_* knobs as they stand (no device, for tests of its contract): out = form, W, fmt,
+// lanes, pairs a block, grid; name: what the launch reports.  1 = a launch, 0 = none (the launcher returns hipErrorInvalidValue), -1 = bad arguments.
+extern "C" int bsa_align8_trace_choice_internal(uint32_t bw, int pw, uint32_t code_fmt, uint32_t count, int cus, uint64_t *out, char *name, size_t name_cap){
+	if(!out || !name || !name_cap || count == 0u || cus <= 0 || pw < 0 || pw > 2) return -1;
+	const TraceChoice c = trace_choose(bw, pw, code_fmt, count, cus);
+	out[0] = c.form; out[1] = c.W; out[2] = c.fmt; out[3] = c.lanes; out[4] = c.ppb; out[5] = c.grid;
+	snprintf(name, name_cap, "%s", c.name ? c.name : "");
+	return c.form != TR_NONE ? 1 : 0;
 }

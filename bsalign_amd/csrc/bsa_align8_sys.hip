@@ -24,7 +24,7 @@
 // store their dwords of the same k side by side (one kilobyte per store instruction).  Overlap / extend mode: row -1 and the score left of
 // column 0 as row_init / the driver set them, the end cell searched for (last query column, then row_max of the last row in the reference's
 // striping).  Two-piece gaps: a second vertical state Q through the rings, a second horizontal chain G, eight facts per cell.
-#include "bsa_common.h"
+#include "bsa_walk.h"
 #include <type_traits>
 
 static __device__ __forceinline__ int sys_shr1(int fill, int x){                 // lane l <- lane l - 1 over the whole wave; lane 0 <- fill
@@ -384,7 +384,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_sys(const Align8Args a, bsa
 	const uint32_t ppos = a.first + g;
 	const uint32_t pair = a.order[ppos];
 	bsa_result_t rs;
-	rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
+	bsa_result_zero(rs);
 	if(a.status[pair] != 0u){ if(wr){ out[pair] = rs; cig_cnt[ppos] = 0; } return; }
 	const int qlen = (int)a.qlen[pair], tlen_ = (int)a.tlen[pair];
 	const uint8_t *qseq = a.qst + a.qpoff[pair], *tseq = a.tst + a.tpoff[pair];
@@ -392,14 +392,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_sys(const Align8Args a, bsa
 	const SysHdr *hdr = (const SysHdr*)slot;
 	const uint8_t *codes = slot + bsa_sys_codes_off((uint32_t)qlen, PW);
 	const int NW = (int)bsa_sys_words((uint32_t)qlen);
-	uint32_t *cig_end = (uint32_t*)(a.rows + slot_end[ppos]);
-	uint32_t ncig = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; if(wr) *(cig_end - ncig) = w; };
-	auto cig_add = [&](uint32_t cg, uint32_t op, uint32_t sz) -> uint32_t {   // bsalign.h:409-417
-		if(op == (cg & 0xf)) return cg + (sz << 4);
-		if(cg) cig_push(cg);
-		return (sz << 4) | op;
-	};
+	bsa_cig_lane_t cig((uint32_t*)(a.rows + slot_end[ppos]), wr);
 	// the facts of cell (x, r): tile r >> 6, wavefront step t = x + (r & 63), word t >> 5, bit 31 - (t & 31)
 	const uint4 *gt = (const uint4*)codes;
 	int tg0 = -1, tg1 = -1, tg2 = -1, tg3 = -1, pf_id = -1;          // the tiles in the LDS slots (slot = word index mod 4), the tile waiting in `pf`
@@ -476,9 +469,9 @@ __global__ void __launch_bounds__(64) k_align8_trace_sys(const Align8Args a, bsa
 		if(bt == 0){
 			if(qc == tc) rs.mat++; else rs.mis++;
 			rs.qb--; rs.tb--; rs.aln++;
-			cg = cig_add(cg, 0, 1);
+			cg = cig.add(cg, 0, 1);
 		} else if(bt == 1){
-			if(rs.qb <= 0){ cg = cig_add(cg, 1, 1); rs.qb--; rs.ins++; rs.aln++; }
+			if(rs.qb <= 0){ cg = cig.add(cg, 1, 1); rs.qb--; rs.ins++; rs.aln++; }
 			else {
 				// the nearest cell to the left at which an insertion reaching its right neighbour opens (bsalign.h:3798-3814)
 				int sz = 0;
@@ -504,7 +497,7 @@ __global__ void __launch_bounds__(64) k_align8_trace_sys(const Align8Args a, bsa
 					}
 				}
 				if(sz == 0){ bad = true; break; }                                       // the reference's scan finds no length either
-				cg = cig_add(cg, 1, (uint32_t)sz);
+				cg = cig.add(cg, 1, (uint32_t)sz);
 				rs.qb -= sz; rs.ins += sz; rs.aln += sz;
 			}
 		} else {
@@ -519,28 +512,12 @@ __global__ void __launch_bounds__(64) k_align8_trace_sys(const Align8Args a, bsa
 				len++;
 			}
 			if(bad) break;
-			cg = cig_add(cg, 2, (uint32_t)len);
+			cg = cig.add(cg, 2, (uint32_t)len);
 			rs.del += len; rs.aln += len;
 			rs.tb -= len;
 		}
 	}
-	if(!bad){
-		if((a.mode & 3) == BSA_MODE_OVERLAP){ if(cg) cig_push(cg); }       // overlap: the alignment simply starts where the walk left the matrix
-		else {
-			uint32_t op = 0, sz = 0;          // global / extend: what is left at the top becomes a leading I / D (bsalign.h:3827-3842)
-			if(rs.qb >= 0){ op = 1; sz = (uint32_t)rs.qb + 1u; rs.ins += (int)sz; rs.qb = -1; }
-			else if(rs.tb >= 0){ op = 2; sz = (uint32_t)rs.tb + 1u; rs.del += (int)sz; rs.tb = -1; }
-			rs.aln += (int)sz;
-			cg = cig_add(cg, op, sz);
-			if(cg) cig_push(cg);
-		}
-		rs.qb++; rs.tb++;
-	} else {
-		if(wr) atomicOr(&a.status[pair], BSA_ST_TRACE);
-		rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
-	}
-	if(wr){ out[pair] = rs; cig_cnt[ppos] = ncig; }
+	bsa_walk_end_lane(a.status, pair, ppos, a.mode & 3, bad, cg, cig, rs, out, cig_cnt);
 }
 
 hipError_t bsa_launch_align8_fwd_sys(const Align8Args &a, int pw, uint32_t max_qlen, hipStream_t st){
@@ -564,15 +541,9 @@ hipError_t bsa_launch_align8_trace_sys(const Align8Args &a, int pw, bsa_result_t
 	if(a.count == 0) return hipSuccess;
 	bool wave = a.count < 16384u;            // a pair per wave while that leaves no SIMD idle, a pair per lane for large batches (1 kbp x 100 k pairs: 3.6 ms against 16.9)
 	if(const char *e = bsa_env("BSA_ALIGN8_SYS_TRACE")) wave = e[0] != 'l';            // "lane" / "wave"
-	if(wave){
-		if(pw == 0) hipLaunchKernelGGL((k_align8_trace_sys<0, true>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt, slot_end);
-		else if(pw == 1) hipLaunchKernelGGL((k_align8_trace_sys<1, true>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt, slot_end);
-		else hipLaunchKernelGGL((k_align8_trace_sys<2, true>), dim3(a.count), dim3(64), 0, st, a, out, cig_cnt, slot_end);
-	} else {
-		const dim3 grid((a.count + 63u) / 64u);
-		if(pw == 0) hipLaunchKernelGGL((k_align8_trace_sys<0, false>), grid, dim3(64), 0, st, a, out, cig_cnt, slot_end);
-		else if(pw == 1) hipLaunchKernelGGL((k_align8_trace_sys<1, false>), grid, dim3(64), 0, st, a, out, cig_cnt, slot_end);
-		else hipLaunchKernelGGL((k_align8_trace_sys<2, false>), grid, dim3(64), 0, st, a, out, cig_cnt, slot_end);
-	}
+	void (*k)(const Align8Args, bsa_result_t*, uint32_t*, const uint64_t*) =
+		wave ? (pw == 0 ? k_align8_trace_sys<0, true> : pw == 1 ? k_align8_trace_sys<1, true> : k_align8_trace_sys<2, true>)
+		     : (pw == 0 ? k_align8_trace_sys<0, false> : pw == 1 ? k_align8_trace_sys<1, false> : k_align8_trace_sys<2, false>);
+	hipLaunchKernelGGL(k, dim3(wave ? a.count : (a.count + 63u) / 64u), dim3(64), 0, st, a, out, cig_cnt, slot_end);
 	return hipGetLastError();
 }

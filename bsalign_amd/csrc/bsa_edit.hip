@@ -17,7 +17,7 @@
 //
 // Mapping: one pair per lane (64 pairs per wave), all state in VGPRs, no cross-lane traffic; the kernel is
 // HBM-bound: per row and pair it writes the two planes (W*16 bytes = 2 bits per band cell), nothing else.
-#include "bsa_common.h"
+#include "bsa_walk.h"
 #include "bsa_dpp.h"
 
 typedef uint64_t u64;
@@ -763,8 +763,8 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 	}
 	// ---- backtrace
 	uint32_t *cig_end = (uint32_t*)((uint8_t*)rows + (size_t)(tlen + 1 + a.pad_rows) * (2 * NW) * 8);
-	uint32_t ncig = 0, cg = 0, op = 0;
-	auto cig_push = [&](uint32_t w){ ncig++; *(cig_end - ncig) = w; };
+	uint32_t cg = 0, op = 0;
+	bsa_cig_lane_t cig(cig_end);
 	int x = rx, y = ry;
 	bool bad = (rx >= (int)qlen);
 	rs.qe = x + 1; rs.te = y + 1;
@@ -776,15 +776,7 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 	int cached_y = y;
 	// 8 bases of each sequence in a register window: the common step (equal bases, no plane lookup) then touches
 	// memory once per 8 steps instead of twice per step
-	u64 qwin = 0, twin = 0; int qwb = -1000, twb = -1000;
-	auto qbase_at = [&](int idx) -> int {
-		if(idx < qwb || idx >= qwb + 8){ qwb = max(idx - 7, 0); __builtin_memcpy(&qwin, qs + qwb, 8); }
-		return (int)((qwin >> (8 * (idx - qwb))) & 0xffu);
-	};
-	auto tbase_at = [&](int idx) -> int {
-		if(idx < twb || idx >= twb + 8){ twb = max(idx - 7, 0); __builtin_memcpy(&twin, ts + twb, 8); }
-		return (int)((twin >> (8 * (idx - twb))) & 0xffu);
-	};
+	bsa_base_win_t qw(qs), tw(ts);
 	// COOP service state
 	// RR rows (one per lane) and 32 bases of each sequence per service point: a walker may move SVC rows / bases before
 	// the next one (the lookups of a step touch rows y + 1 and y)
@@ -871,9 +863,9 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 				tv = (t1 << st_) | (st_ ? t0 >> (64u - st_) : 0ull);
 				reach = min(min(eq, et) + 1u, svc_left);
 			} else {
-				(void)qbase_at(x); (void)tbase_at(y);        // windows now hold [qwb, qwb + 8) with x inside, same for y
-				qv = qwin << (8u * (7u - (uint32_t)(x - qwb))); tv = twin << (8u * (7u - (uint32_t)(y - twb)));
-				reach = (uint32_t)min(x - qwb, y - twb) + 1u;
+				(void)qw.at(x); (void)tw.at(y);        // windows now hold [wb, wb + 8) with x inside, same for y
+				qv = qw.win << (8u * (7u - (uint32_t)(x - qw.wb))); tv = tw.win << (8u * (7u - (uint32_t)(y - tw.wb)));
+				reach = (uint32_t)min(x - qw.wb, y - tw.wb) + 1u;
 			}
 			const u64 df = qv ^ tv;
 			if((df >> 56) == 0ull){
@@ -896,7 +888,7 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 				}
 			}
 			if(op == (cg & 0xf)) cg += 0x10u * step;
-			else { if(cg) cig_push(cg); cg = (0x10u * step) | op; }
+			else { if(cg) cig.push(cg); cg = (0x10u * step) | op; }
 			active = x >= 0 && y >= 0;
 			svc_left -= min(step, svc_left);
 		}
@@ -913,27 +905,27 @@ __global__ void __launch_bounds__(64) k_edit_trace(const EditArgs a, bsa_result_
 		if(rs.qb){
 			op = 1;
 			if(op == (cg & 0xf)) cg += 0x10u * (uint32_t)rs.qb;
-			else { if(cg) cig_push(cg); cg = (0x10u * (uint32_t)rs.qb) | op; }
+			else { if(cg) cig.push(cg); cg = (0x10u * (uint32_t)rs.qb) | op; }
 			rs.ins += rs.qb; rs.qb = 0;
 		}
 		if((type == BSA_MODE_GLOBAL || type == BSA_MODE_EXTEND) && rs.tb){
 			op = 2;
 			if(op == (cg & 0xf)) cg += 0x10u * (uint32_t)rs.tb;
-			else { if(cg) cig_push(cg); cg = (0x10u * (uint32_t)rs.tb) | op; }
+			else { if(cg) cig.push(cg); cg = (0x10u * (uint32_t)rs.tb) | op; }
 			rs.del += rs.tb; rs.tb = 0;
 		}
 		rs.aln = rs.mat + rs.mis + rs.ins + rs.del;
-		if(cg) cig_push(cg);
+		if(cg) cig.push(cg);
 		if(type == BSA_MODE_OVERLAP) rs.score = smin + rs.te - rs.tb;
 		else if(type == BSA_MODE_EXTEND) rs.score = smin;
 		else rs.score = score;
 	} else {
 		atomicOr(&a.status[pair], BSA_ST_TRACE);
 		rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
+		cig.n = 0;
 	}
 	out[pair] = rs;
-	cig_cnt[ppos] = ncig;
+	cig_cnt[ppos] = cig.n;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1052,46 +1044,7 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 		a.fwd_ry[ppos], rx, ry, smin, score);
 	// ---- backtrace
 	uint32_t *cig_end = (uint32_t*)((uint8_t*)rows + (size_t)(tlen + 1 + a.pad_rows) * (2 * NW) * 8);
-	// CIGAR: one token per gap event (matches / mismatches since the last event, op, length), one token per lane; a gap that goes
-	// on (same op, no match in between) extends its own token, so neighbouring tokens never carry the same op and every 64 tokens
-	// the lanes turn them into words side by side (an M word when the run is not empty, then the gap's word; positions from two
-	// prefix popcounts; word m at cig_end - (m + 1)).  The same scheme as k_align8_trace_codes_wave (bsa_align8_codes.hip).
-	uint32_t ncig = 0, tokN = 0, tokB = 0;            // words written; the lane's token: run length, len << 2 | op (op 0: none)
-	// (uniform) tokens held; key = op of the last token << 28 | match / mismatch columns since it, so that "same op, nothing in between" is one
-	// compare (28 bits: the length field of a CIGAR word, length << 4 | op in 32 bits -- a longer run has no word in the reference's format either)
-	uint32_t ntok = 0, key = 0;
-	constexpr uint32_t KEYM = 0x0FFFFFFFu;
-	auto tok_flush = [&](uint32_t cnt){
-		const bool in = lane < cnt;
-		tokN &= KEYM;
-		const bool hasA = in && tokN != 0u, hasB = in && (tokB & 3u) != 0u;
-		const u64 mA = __ballot(hasA), mB = __ballot(hasB);
-		const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mA >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mA, 0u))
-			+ __builtin_amdgcn_mbcnt_hi((uint32_t)(mB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mB, 0u));
-		uint32_t *wp = cig_end - (ncig + below + 1u);
-		if(hasA){ *wp = tokN << 4; wp--; }
-		if(hasB) *wp = ((tokB >> 2) << 4) | (tokB & 3u);
-		ncig += (uint32_t)(__popcll(mA) + __popcll(mB));
-	};
-	auto emit = [&](uint32_t op, uint32_t len){
-		if(op == 0u){ key += len; return; }
-		if(key == (op << 28)){ if(lane + 1u == ntok) tokB += len << 2; return; }
-		if(ntok == 64u){
-			tok_flush(63u);
-			tokN = (uint32_t)__builtin_amdgcn_readlane((int)tokN, 63); tokB = (uint32_t)__builtin_amdgcn_readlane((int)tokB, 63);
-			ntok = 1u;
-		}
-		if(lane == ntok){ tokN = key; tokB = (len << 2) | op; }       // (the op field of the key is masked off when the token is written)
-		ntok++; key = op << 28;
-	};
-	auto cig_finish = [&](){
-		if(key & KEYM){
-			if(ntok == 64u){ tok_flush(64u); ntok = 0u; }
-			if(lane == ntok){ tokN = key; tokB = 0u; }
-			ntok++; key = 0u;
-		}
-		tok_flush(ntok); ntok = 0u;
-	};
+	bsa_cig_wave_t cig(cig_end, lane);               // one token per gap event (bsa_walk.h)
 	int x = rx, y = ry;
 #ifdef EDIT_DBG
 	uint32_t dbg_lit = 0, dbg_tiles = 0, dbg_demand = 0;
@@ -1303,7 +1256,7 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 			const int n = k - k0;
 			// n match / mismatch columns (possibly none): the count goes to the token key, the mismatches to the lanes' own counts
 			vmis += (uint32_t)((int)lane - k0) < (uint32_t)n ? nei : 0u;
-			key += (uint32_t)n;
+			cig.key += (uint32_t)n;
 			x -= n; y -= n;
 			const uint32_t ek = (uint32_t)__builtin_amdgcn_readlane((int)ev, k);
 			if(!(ek & 4u) || x < 0) break;                           // end of the tile / of the walk
@@ -1320,11 +1273,11 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 				if(!isI){ const int u1 = plane_bit((uint32_t)y, 0, pb0), u2 = plane_bit((uint32_t)y, 1, pb0); isD = u1 == 1 && u2 == 0; }
 			}
 			if(isI){
-				rs.ins++; emit(1u, 1u); x--; k0 = k;
+				rs.ins++; cig.emit(1u, 1u); x--; k0 = k;
 				if(x + k0 - 63 < qw_lo && qw_lo > 0){ q_refill(x); qK = (int)lane + qw_lo; }
 			}
-			else if(isD){ emit(2u, 1u); y--; k0 = k + 1; }
-			else { vmis += (int)lane == k ? 1u : 0u; emit(0u, 1u); x--; y--; k0 = k + 1; }    // a mismatch the masks could not decide
+			else if(isD){ cig.emit(2u, 1u); y--; k0 = k + 1; }
+			else { vmis += (int)lane == k ? 1u : 0u; cig.emit(0u, 1u); x--; y--; k0 = k + 1; }    // a mismatch the masks could not decide
 			if(k0 > 62) break;
 		}
 	}
@@ -1333,27 +1286,25 @@ __global__ void __launch_bounds__(64) k_edit_trace_wave(const EditArgs a, bsa_re
 		{
 			// rs.ins holds the inserted columns of the walk: the other totals follow from its two ends, the mismatches from the lanes' counts
 			const int mcols = (rx - x) - rs.ins;
-			uint32_t t = vmis;
-			for(int o = 32; o; o >>= 1) t += (uint32_t)__shfl_xor((int)t, o);
-			rs.mis = __builtin_amdgcn_readfirstlane((int)t); rs.mat = mcols - rs.mis;
+			rs.mis = bsa_wave_sum(vmis); rs.mat = mcols - rs.mis;
 			rs.del = (ry - y) - mcols;
 		}
-		if(rs.qb){ emit(1u, (uint32_t)rs.qb); rs.ins += rs.qb; rs.qb = 0; }
-		if((type == BSA_MODE_GLOBAL || type == BSA_MODE_EXTEND) && rs.tb){ emit(2u, (uint32_t)rs.tb); rs.del += rs.tb; rs.tb = 0; }
+		if(rs.qb){ cig.emit(1u, (uint32_t)rs.qb); rs.ins += rs.qb; rs.qb = 0; }
+		if((type == BSA_MODE_GLOBAL || type == BSA_MODE_EXTEND) && rs.tb){ cig.emit(2u, (uint32_t)rs.tb); rs.del += rs.tb; rs.tb = 0; }
 		rs.aln = rs.mat + rs.mis + rs.ins + rs.del;
-		cig_finish();
+		cig.finish();
 		if(type == BSA_MODE_OVERLAP) rs.score = smin + rs.te - rs.tb;
 		else if(type == BSA_MODE_EXTEND) rs.score = smin;
 		else rs.score = score;
 	} else {
 		if(lane == 0) atomicOr(&a.status[pair], BSA_ST_TRACE);
 		rs.score = 0; rs.qb = rs.qe = rs.tb = rs.te = 0; rs.mat = rs.mis = rs.ins = rs.del = rs.aln = 0;
-		ncig = 0;
+		cig.ncig = 0;
 	}
 #ifdef EDIT_DBG
 	if(lane == 0 && blockIdx.x < 12u) printf("walk %u (tiled %d): %u tiles, %u fetched on demand, %u literal steps, qlen %u tlen %u\n", blockIdx.x, (int)TILED, dbg_tiles, dbg_demand, dbg_lit, qlen, tlen);
 #endif
-	if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = ncig; }
+	if(lane == 0){ out[pair] = rs; cig_cnt[ppos] = cig.ncig; }
 }
 
 // BSA_MODE_SCORE_ONLY: the records of the SCORE forward kernels (a pair's last row) -> results, one pair per wave, through the walkers' own
