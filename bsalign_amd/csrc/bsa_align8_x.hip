@@ -32,6 +32,8 @@
 // Two of these differ between the row bodies on purpose (HISTORY.md 19): x_forward_abs forms the row target of global steering in integers (x_rt_*, the double expression
 // where a row's product divides evenly) and shifts the slots of a row that does not move by one two to an instruction (x_slots_up / x_slots_down), and it forms
 // rbase behind a wave-level test of its two readers; x_forward keeps the double expression on every renewal, one v_cndmask_b32 a slot and rbase on every live row.
+// A third since HISTORY.md 20: in its biased frame x_forward_abs forms the noise sum of band steering with v_sad_u16 on the unsigned H^ patterns; x_forward's signed
+// differences keep the packed absolute values and the per-half sum.
 #include "bsa_common.h"
 #include "bsa_dpp.h"
 #include <algorithm>
@@ -196,8 +198,9 @@ template<int L> static __device__ __forceinline__ uint32_t x_shift_up(uint32_t x
 }
 // inclusive prefix maximum over the lanes of a group, per half (Sklansky: nothing crosses a group)
 template<int L> static __device__ __forceinline__ uint32_t x_scan_max(uint32_t x){
-	uint32_t y = XDPP(x, x, XQP(0, 0, 2, 2), 0xf); x = x_max(x, y);
-	y = XDPP(x, x, XQP(0, 1, 1, 1), 0xf); x = x_max(x, y);
+	// (both quad permutes give every lane a source: the bound_ctrl form has the same values and no `old` operand, which cost a v_mov_b32 a step)
+	uint32_t y = XDPPZ(x, XQP(0, 0, 2, 2), 0xf); x = x_max(x, y);
+	y = XDPPZ(x, XQP(0, 1, 1, 1), 0xf); x = x_max(x, y);
 	if constexpr (L == 8){
 		const uint32_t z = XDPP(x, x, XQP(3, 3, 3, 3), 0xf);
 		y = XDPP(x, z, XROW_SHR(4), 0xA); x = x_max(x, y);
@@ -211,6 +214,15 @@ template<int L> static __device__ __forceinline__ uint32_t x_sum(uint32_t x){
 	if constexpr (L == 8) x = x_add(x, XDPPZ(x, XHALF_MIRROR, 0xf));
 	return x;
 }
+// the same sum of one 32-bit number a lane: a plain add takes the DPP operand itself (v_add_u32_dpp), a packed one cannot
+template<int L> static __device__ __forceinline__ uint32_t x_sum32(uint32_t x){
+	x += XDPPZ(x, XQP(1, 0, 3, 2), 0xf);
+	x += XDPPZ(x, XQP(2, 3, 0, 1), 0xf);
+	if constexpr (L == 8) x += XDPPZ(x, XHALF_MIRROR, 0xf);
+	return x;
+}
+// |a.lo - b.lo| + |a.hi - b.hi| + c, the halves read as UNSIGNED 16-bit numbers, the sum one 32-bit number (v_sad_u16)
+static __device__ __forceinline__ uint32_t x_sad(uint32_t a, uint32_t b, uint32_t c){ return __builtin_amdgcn_sad_u16(a, b, c); }
 
 template<int W>
 static __device__ __forceinline__ void x_load_qcodes(const uint8_t *p, uint32_t *w){
@@ -1018,7 +1030,7 @@ static __device__ __forceinline__ void x_forward(const Align8Args &a, const uint
 // (bsa_align8_flag_span derives it for every scoring of the guard), so of n = b - a bits 8 .. 15 are all clear (equal) or all set: two instructions a cell, the packed
 // difference and one v_bitop3_b32 that puts the cell's bit of ~n into the accumulator (x_ins; the saturating form it replaces took three, the last a v_pk_mad_u16):
 //     M: n = d - h     R: n = hg - fm     D: n = E - h     Od: n = hg - en   (= (h - en) + gapo: zero exactly where the field h - en equals -gapo)
-// Cell 0 alone keeps the saturating comparison for M (pass 2 says why).  The two-bit D / Od fields are a Horner multiply-add (x_acc) and fill the low byte.
+// Cell 0 alone keeps the saturating comparison for M, in the waves that take the first-cell rule (the fix-up behind pass 2 says why).  The two-bit D / Od fields are a Horner multiply-add (x_acc) and fill the low byte.
 // PW: 1 one-piece gaps, 0 linear gaps (gapo = 0: E^ of a cell is its upper neighbour's H^, R and Od are always set).  DO2: the two-bit D / Od fields (four lanes, one piece);
 // otherwise the four planes, with D (h == E) and Od (field == -gapo) accumulated as they are stored too.  L = 8: bandwidth 256, a half is one reference block of sixteen cells.
 // EXT: the staging area and the window come from the caller (k_align8_fwd_x_mix).
@@ -1238,11 +1250,15 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		const uint32_t d0s = x_add(Hp[0], S[0]);
 		uint32_t d0h = d0s;
 		// q0m and q0d are read by the fix-up of rbeg = 0 alone (behind pass 2), and every live row at rbeg = 0 sets them below: they start without a value, at no instruction
-		uint32_t q0m, q0d;
-		asm volatile("" : "=v"(q0m), "=v"(q0d));
+		// (q0s likewise: d0s of a row that takes the first-cell rule, read by the fix-up of cell 0's M flag behind pass 2)
+		uint32_t q0m, q0d, q0s;
+		asm volatile("" : "=v"(q0m), "=v"(q0d), "=v"(q0s));
 		const uint32_t fini = x_add(Hp[0], MINF16);
 		// (a row that stays, mov = 0, or whose band jumped; rbeg = 0 implies mov = 0 on that row, rbeg being the sum of the moves, so every live row at rbeg = 0 comes here)
-		if(__builtin_expect((__builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u) & actm) != 0ull, 0)){
+		// (the live lanes of such rows, kept as a scalar mask: the only rows on which d0h can differ from d0s, which the fix-ups behind pass 2 ask again)
+		const uint64_t fcm = __builtin_amdgcn_ballot_w64(mov - 1u >= (uint32_t)BW - 1u) & actm;
+		if(__builtin_expect(fcm != 0ull, 0)){
+			q0s = d0s;
 			const int hp0 = x_lo16(Hp[0]);
 			const int HBr = base + hp0 + GE * ((int)rbeg + (int)i - 2);
 			// A ROW THAT STAYS AT rbeg > 0 has rh = SCORE_MIN, and then hh = (SCORE_MIN - HBr) + s0 with s0 <= 127 (a matrix entry or the pad score) while
@@ -1342,24 +1358,29 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 				// field == -gapo: hg - en = (h - en) + gapo, in gapo .. 0 because hg <= en <= h
 				if constexpr (PW != 0) accO[k >> 3] = ins(accO[k >> 3], x_sub(hg, en));
 			}
-			// Cell 0 keeps the saturating comparison, its flag put at bit 15: lane 0's h comes from d0h (the first-cell rule) while M compares with d0s, and where
-			// d0h < d0s the difference h - d0s can be negative, which saturates to "no match" and would read as a match from the bits of d0s - h.
-			if(k == 0) accM[0] = x_shl15(x_satsubu(ONE1, x_sub(h, d[0])));
-			else accM[k >> 3] = ins(accM[k >> 3], x_sub(d[k], h));
+			// (cell 0's flag is right wherever d0h is d0s, i.e. in every wave that did not take the first-cell rule: the fix-up behind the loop has the others)
+			accM[k >> 3] = ins(accM[k >> 3], x_sub(d[k], h));
 			Hp[k] = h;
 			if(k == 0){ tmpE0 = en; hfirst = h; }
 			else E[k - 1] = en;
 		}
 		// ---- flags of special cells (x_forward's, on accumulators that are not inverted; the one-bit flags sit in the HIGH byte of a half, cell 0 of eight in
 		// bit 15, the two-bit fields in the low byte)
-		if(__builtin_expect((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull, 0)){
-			if(first && rbeg == 0u){
-				const uint32_t hl = hfirst & 0xffffu;
-				accM[0] = (accM[0] & ~0x8000u) | ((hl == q0m) ? 0x8000u : 0u);
-				if constexpr (DO2){
-					const uint32_t fld = (accDO[0] >> 6) & 3u;
-					accDO[0] = (accDO[0] & ~0xC0u) | ((hl == q0d) ? 0x40u : 0u) | ((fld == (uint32_t)(-GO)) ? 0x80u : 0u);
-				} else accD[0] = (accD[0] & ~0x8000u) | ((hl == q0d) ? 0x8000u : 0u);
+		// A WAVE THAT TOOK THE FIRST-CELL RULE (fcm, the scalar mask of that test; every live row at rbeg = 0 is among its rows) forms cell 0's M flag again, by the
+		// saturating comparison: there lane 0's h comes from d0h while M compares with d0s (kept in q0s), and where d0h < d0s the difference h - d0s can be negative,
+		// which saturates to "no match" and would read as a match from the bits of d0s - h that the two-instruction insert looks at.  In every other wave d0h is d0s
+		// in every lane, h >= d[0] as in the other cells, and the insert's bit stands: two instructions for cell 0 on those rows, where the saturating form took three.
+		if(__builtin_expect(fcm != 0ull, 0)){
+			accM[0] = (accM[0] & 0x7FFF7FFFu) | x_shl15(x_satsubu(ONE1, x_sub(hfirst, q0s)));
+			if((__builtin_amdgcn_ballot_w64(rbeg == 0u) & actm) != 0ull){
+				if(first && rbeg == 0u){
+					const uint32_t hl = hfirst & 0xffffu;
+					accM[0] = (accM[0] & ~0x8000u) | ((hl == q0m) ? 0x8000u : 0u);
+					if constexpr (DO2){
+						const uint32_t fld = (accDO[0] >> 6) & 3u;
+						accDO[0] = (accDO[0] & ~0xC0u) | ((hl == q0d) ? 0x40u : 0u) | ((fld == (uint32_t)(-GO)) ? 0x80u : 0u);
+					} else accD[0] = (accD[0] & ~0x8000u) | ((hl == q0d) ? 0x8000u : 0u);
+				}
 			}
 		}
 		// Moves of two and more: the cells whose upper neighbour (D / Od) or diagonal predecessor (M) is an entering cell lose those flags.  GENERAL FORM, per lane,
@@ -1533,20 +1554,39 @@ static __device__ __forceinline__ void x_forward_abs(const Align8Args &a, const 
 		}
 		// ---- adaptive band + global steering (x_forward's, the block differences read from H^)
 		{
-			uint32_t x;
-			if constexpr (CR == 1){
-				const uint32_t dl = x_add(x_sub(Hp[W - 1], Hsh), x_i16(W * GE));          // ubegs[b + 1] - ubegs[b]
-				x = x_max(dl, x_sub(0u, dl));
+			uint32_t nzsum;
+			if constexpr (M3){
+				// ubegs[b + 1] - ubegs[b] = H^(end of block b) - H^(left of it) + c gape over a block of c = 16 / CR cells.  In the biased frame every H^ of a live row is
+				// a pattern in 0x0401 .. 0x7BFF (bsa_align8_abs_rows), and so is the virtual column of Hsh up to one gape below (>= 0x0401 - 127), so the halves are their own
+				// values as UNSIGNED numbers and v_sad_u16 adds |a - b| of both halves into one 32-bit sum.  The constant goes UPWARD, onto the value left of the block (- c gape >= 0):
+				// at most 0x7BFF + 16 * 127 = 0x83EF, inside 16 bits for every gape of the guard (|gape| <= 127), at either block size; added to the block's last cell it would
+				// go below zero at sixteen cells a block (0x0401 - 16 * 127).  A pair's sum is 2 L CR <= 16 terms below 2^16 each: no carry is lost in 32 bits, where the packed
+				// sum kept two 16-bit halves.  (Lanes of dead pairs and of rows past a short target sum arbitrary patterns: nothing reads their mov.)
+				const uint32_t NC16 = x_i16(-(W / CR) * GE);
+				uint32_t n;
+				if constexpr (CR == 1) n = x_sad(Hp[W - 1], x_add(Hsh, NC16), 0u);
+				else {
+					n = x_sad(Hp[W / 2 - 1], x_add(Hsh, NC16), 0u);
+					n = x_sad(Hp[W - 1], x_add(Hp[W / 2 - 1], NC16), n);
+				}
+				nzsum = x_sum32<L>(n);
 			} else {
-				const uint32_t HGE16 = x_i16((W / 2) * GE);
-				const uint32_t da = x_add(x_sub(Hp[W / 2 - 1], Hsh), HGE16), db = x_add(x_sub(Hp[W - 1], Hp[W / 2 - 1]), HGE16);
-				x = x_add(x_max(da, x_sub(0u, da)), x_max(db, x_sub(0u, db)));
+				// (the frame at 0: scores can be negative as int16, which v_sad_u16 would misread)
+				uint32_t x;
+				if constexpr (CR == 1){
+					const uint32_t dl = x_add(x_sub(Hp[W - 1], Hsh), x_i16(W * GE));          // ubegs[b + 1] - ubegs[b]
+					x = x_max(dl, x_sub(0u, dl));
+				} else {
+					const uint32_t HGE16 = x_i16((W / 2) * GE);
+					const uint32_t da = x_add(x_sub(Hp[W / 2 - 1], Hsh), HGE16), db = x_add(x_sub(Hp[W - 1], Hp[W / 2 - 1]), HGE16);
+					x = x_add(x_max(da, x_sub(0u, da)), x_max(db, x_sub(0u, db)));
+				}
+				x = x_sum<L>(x);
+				nzsum = (x & 0xffffu) + (x >> 16);
 			}
-			x = x_sum<L>(x);
-			const int nzsum = (int)((x & 0xffffu) + (x >> 16));
 			const uint32_t bcf = x_bcast_first<L>(Hp[0]);
 			const int d16 = x_hi16(bcl) - x_lo16(bcf) + (BW - 1) * GE;          // ubegs[16] - ubegs[0]
-			uint32_t nz = (uint32_t)(nzsum / 16);
+			uint32_t nz = nzsum / 16u;
 			nz = nz / (uint32_t)WR * 16u / 2u;
 			const int noisy = (int)((16u > nz) ? 16u : nz);
 			int rbx;
