@@ -179,6 +179,8 @@ def lib():
         if hasattr(L, "bsa_edit_choice_internal"):
             L.bsa_edit_choice_internal.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.POINTER(C.c_uint64), C.c_char_p, C.c_char_p, C.c_size_t]
+        if hasattr(L, "bsa_seq16_internal"):
+            L.bsa_seq16_internal.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, u8p, u32p]
         L.bsa_kmer_edit_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
                                           vp, u32p, C.c_size_t, u64p, u32p]
         L.bsa_kmer_edit_batch2.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, u64p, u32p, C.c_size_t, C.POINTER(KmerParams),
@@ -359,6 +361,19 @@ def edit_choice(bw, wide, count, mode=MODE_GLOBAL, bandwidth=0, score=False, alo
     d = dict(zip(EDIT_CHOICE_FIELDS, (int(v) for v in out)))
     d.update(fwd_name=fwd.value.decode(), trace_name=trace.value.decode(), launch=rc == 1)
     return d
+
+
+def seq16(blob, off, length, i, packed=False, rev=0, padcode=0):
+    """the sixteen staged codes of positions [i, i + 16) of the sequence of `length` bases at `off` of `blob`, as every staging kernel reads them
+    (bsa_seq16_internal: the host side of the kernels' reader; no device).  blob: uint8 codes and a byte offset, or (packed) uint64 BSA_MODE_SEQ2BIT
+    words and a base offset; rev: 0 forwards, 1 the reverse complement, 2 forwards as a plan with MODE_QSTRAND reads an unmarked query.
+    -> (uint8[16], whether a code above 3 was met)"""
+    b = np.ascontiguousarray(blob, dtype=np.uint64 if packed else np.uint8)
+    out, bad = np.zeros(16, dtype=np.uint8), C.c_uint32(0)
+    rc = lib().bsa_seq16_internal(C.c_void_p(b.ctypes.data), off, length, i, int(packed), rev, padcode, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(bad))
+    if rc != 0:
+        raise ValueError("bsa_seq16_internal: bad arguments")
+    return out, bool(bad.value)
 
 
 def pack2bit(codes):

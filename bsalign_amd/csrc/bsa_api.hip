@@ -260,121 +260,6 @@ static int ctx_ws_reserve(bsa_ctx *c, size_t bytes){
 // small utility kernels
 // ------------------------------------------------------------------------------------------------
 
-// stage one pair per TPP threads -- a wave for short pairs (a block per pair spent most of its time being launched), the whole block
-// for long ones: copy query codes (padded with BSA_QPAD_CODE) and target bytes, validate codes
-// QS (plans with BSA_MODE_QSTRAND): bit 63 of qoff[k] asks for the query's reverse complement -- piece i of it is the 16 stored bytes that
-// end at qlen - i, byte-reversed and complemented, and the piece done byte by byte is the one that holds the START of the stored query
-template<int TPP, bool QS = false>
-__global__ void __launch_bounds__(256) k_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
-		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
-		uint8_t *qst, uint8_t *tst, uint32_t qpad, uint32_t tpad, uint32_t *status, uint32_t n){
-	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
-	if(k >= n) return;
-	const uint32_t ql = qlen[k], tl = tlen[k];
-	const uint64_t qo = qoff[k];
-	const bool qrev = QS && (qo & BSA_QOFF_REVCOMP) != 0;
-	const uint8_t *q = seqs + (QS ? qo & ~BSA_QOFF_REVCOMP : qo), *t = seqs + toff[k];
-	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
-	uint32_t bad = 0;
-	// 16 bytes per thread and trip (the staged regions are 16-byte aligned and a whole number of 16-byte pieces, the source is
-	// not aligned and ends with the sequence): whole pieces with two 8-byte loads, the piece that holds the end byte by byte
-	auto copy = [&](const uint8_t *src, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode, bool rev){
-		const uint32_t total = (len + pad + 15u) & ~15u;
-		for(uint32_t i = lane * 16u; i < total; i += (uint32_t)TPP * 16u){
-			uint64_t v0, v1;
-			if(i + 16u <= len){
-				if(QS && rev){
-					__builtin_memcpy(&v1, src + (len - i - 16u), 8); __builtin_memcpy(&v0, src + (len - i - 8u), 8);
-					v0 = __builtin_bswap64(v0); v1 = __builtin_bswap64(v1);
-				} else { __builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8); }
-				if((v0 | v1) & 0xFCFCFCFCFCFCFCFCull){ bad = 1; v0 &= 0x0303030303030303ull; v1 &= 0x0303030303030303ull; }
-				if(QS && rev){ v0 ^= 0x0303030303030303ull; v1 ^= 0x0303030303030303ull; }
-			} else {
-				v0 = v1 = 0;
-#pragma unroll
-				for(uint32_t b = 0; b < 16u; b++){
-					uint8_t c = (i + b < len) ? ((QS && rev) ? src[len - 1u - i - b] : src[i + b]) : padcode;
-					if(i + b < len && c > 3){ bad = 1; c &= 3; }
-					if(QS && rev && i + b < len) c ^= 3;
-					if(b < 8u) v0 |= (uint64_t)c << (8u * b); else v1 |= (uint64_t)c << (8u * (b - 8u));
-				}
-			}
-			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32);
-			*(uint4*)(dst + i) = o;
-		}
-	};
-	copy(q, dq, ql, qpad, (uint8_t)BSA_QPAD_CODE, qrev);
-	copy(t, dt, tl, tpad, (uint8_t)0, false);
-	uint32_t st = 0;
-	if((TPP == 64) ? __any((int)bad) : __syncthreads_or((int)bad)) st |= BSA_ST_BAD_BASE;
-	if(ql == 0 || tl == 0) st |= BSA_ST_EMPTY;
-	if(lane == 0) status[k] = st;
-}
-
-// k_stage for BSA_MODE_SEQ2BIT blobs: the offsets are base offsets into 2-bit packed words (bsa_bits16); the staged bytes, the padding
-// and the empty-pair flag are k_stage's.  No code is above 3, so no BSA_ST_BAD_BASE.  QS: a marked query comes through bsa_bits16_rc.
-template<int TPP, bool QS = false>
-__global__ void __launch_bounds__(256) k_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
-		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
-		uint8_t *qst, uint8_t *tst, uint32_t qpad, uint32_t tpad, uint32_t *status, uint32_t n){
-	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
-	if(k >= n) return;
-	const uint32_t ql = qlen[k], tl = tlen[k];
-	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
-	// 16 bases per thread and trip from at most two words, expanded to one 16-byte store
-	auto copy = [&](uint64_t off, uint8_t *dst, uint32_t len, uint32_t pad, uint8_t padcode, bool rev){
-		const uint32_t total = (len + pad + 15u) & ~15u;
-		for(uint32_t i = lane * 16u; i < total; i += (uint32_t)TPP * 16u){
-			const uint32_t x = (QS && rev) ? (i < len ? bsa_bits16_rc(seqs, off, off + len - i) : 0u) : bsa_bits16(seqs, off + i, off + len);
-			uint64_t v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
-			if(i + 16u > len){ v0 = bsa_pad_bytes(v0, (int64_t)len - i, padcode); v1 = bsa_pad_bytes(v1, (int64_t)len - i - 8, padcode); }
-			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32);
-			*(uint4*)(dst + i) = o;
-		}
-	};
-	const uint64_t qo = qoff[k];
-	copy(QS ? qo & ~BSA_QOFF_REVCOMP : qo, dq, ql, qpad, (uint8_t)BSA_QPAD_CODE, QS && (qo & BSA_QOFF_REVCOMP) != 0);
-	copy(toff[k], dt, tl, tpad, (uint8_t)0, false);
-	if(lane == 0) status[k] = (ql == 0 || tl == 0) ? BSA_ST_EMPTY : 0u;
-}
-
-// bsa_seq_pack2bit: 32 codes a thread into one word of the BSA_MODE_SEQ2BIT layout (c & 3; a code above 3 sets *bad)
-__global__ void __launch_bounds__(256) k_pack2bit(const uint8_t *codes, uint64_t nbases, uint64_t *bits, uint32_t *bad){
-	const uint64_t w = (uint64_t)blockIdx.x * 256u + threadIdx.x, b0 = w * 32u;
-	if(b0 >= nbases) return;
-	uint64_t v = 0, hi = 0;
-	if(b0 + 32u <= nbases){
-#pragma unroll
-		for(uint32_t j = 0; j < 4u; j++){
-			uint64_t c;
-			__builtin_memcpy(&c, codes + b0 + 8u * j, 8);
-			hi |= c;
-#pragma unroll
-			for(uint32_t b = 0; b < 8u; b++) v |= ((c >> (8u * b)) & 3ull) << (62u - 2u * (8u * j + b));
-		}
-		hi &= 0xFCFCFCFCFCFCFCFCull;
-	} else {
-		for(uint32_t j = 0; b0 + j < nbases; j++){
-			const uint8_t c = codes[b0 + j];
-			hi |= c & 0xFCu;
-			v |= (uint64_t)(c & 3u) << (62u - 2u * j);
-		}
-	}
-	bits[w] = v;
-	if(bad && hi) *bad = 1u;
-}
-
-extern "C" int bsa_seq_pack2bit(bsa_ctx_t *c, const uint8_t *d_codes, uint64_t nbases, uint64_t *d_bits, uint32_t *d_bad){
-	if(!c || (nbases && (!d_codes || !d_bits))) return BSA_E_ARG;
-	if(nbases == 0) return BSA_OK;
-	(void)hipSetDevice(c->device);
-	const uint64_t words = (nbases + 31u) / 32u, blocks = (words + 255u) / 256u;
-	if(blocks > 0x7FFFFFFFull){ c->err = "bsa_seq_pack2bit: too many bases"; return BSA_E_ARG; }
-	hipLaunchKernelGGL(k_pack2bit, dim3((uint32_t)blocks), dim3(256), 0, c->stream, d_codes, nbases, d_bits, d_bad);
-	HIPCHK(c, hipGetLastError());
-	return BSA_OK;
-}
-
 // one wave per pair: copy the CIGAR words a traceback kernel left at the tail of the pair's row slot
 __global__ void __launch_bounds__(256) k_cigar_collect(const uint8_t *rows, const uint64_t *slot_end,
 		uint32_t first, uint32_t count, const uint32_t *cnt, const uint64_t *off, uint32_t *tmp, uint64_t cap){
@@ -1055,23 +940,12 @@ extern "C" int bsa_align_run(bsa_align_plan_t *p, const uint8_t *d_seqs, bsa_res
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
 	{
-		// which staging kernel: 1 B/base or 2-bit words, a block per pair for long pairs (>= 8192 staged bytes) or a wave, and -- only in
-		// plans with BSA_MODE_QSTRAND -- the instantiations that look at bit 63 of qoff[k]
+		// staging (bsa_stage.hip): a block per pair for long pairs (>= 8192 staged bytes), else a wave
 		const bool blk = p->stage_bytes / std::max<size_t>(n, 1) >= 8192;
-		const dim3 grid(blk ? n : (n + 3u) / 4u);
-#define BSA_STAGE(K, SEQS) hipLaunchKernelGGL(K, grid, dim3(256), 0, st, SEQS, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, \
-			p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->qpad, p->tpad, status, n)
-		const uint64_t *d_words = (const uint64_t*)d_seqs;
-		if(p->seq2bit){
-			if(p->qstrand){ if(blk) BSA_STAGE((k_stage2b<256, true>), d_words); else BSA_STAGE((k_stage2b<64, true>), d_words); }
-			else if(blk) BSA_STAGE(k_stage2b<256>, d_words); else BSA_STAGE(k_stage2b<64>, d_words);
-		} else {
-			if(p->qstrand){ if(blk) BSA_STAGE((k_stage<256, true>), d_seqs); else BSA_STAGE((k_stage<64, true>), d_seqs); }
-			else if(blk) BSA_STAGE(k_stage<256>, d_seqs); else BSA_STAGE(k_stage<64>, d_seqs);
-		}
-#undef BSA_STAGE
+		const StageArgs sa = { d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, nullptr, nullptr, nullptr,
+			p->qpad, p->tpad, status, n };
+		HIPCHK(c, bsa_launch_stage(sa, p->seq2bit, blk ? 256u : 64u, p->qstrand, st));
 	}
-	HIPCHK(c, hipGetLastError());
 	Align8Args a = align8_scoring_args(&p->par, p->bw, p->par.mode);
 	a.qst = p->d_qst; a.tst = p->d_tst; a.qpoff = p->d_qpoff; a.tpoff = p->d_tpoff;
 	a.qlen = p->d_qlen; a.tlen = p->d_tlen; a.order = p->d_order; a.slot_off = p->d_slot;
@@ -1774,8 +1648,12 @@ extern "C" int bsa_edit_run(bsa_edit_plan_t *p, const uint8_t *d_seqs, bsa_resul
 	}
 	if(!d_seqs) return BSA_E_ARG;
 	uint32_t *status = d_status ? d_status : p->d_status_own;
-	HIPCHK(c, bsa_launch_edit_stage(d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, p->d_qpoff, p->d_tpoff, p->d_qboff, p->d_qwords,
-		p->d_qst, p->d_tst, p->d_qbits, status, n, st, p->seq2bit, p->qstrand));
+	{
+		// staging (bsa_stage.hip): a wave per pair from 65 536 pairs on, a block below
+		const StageArgs sa = { d_seqs, p->d_qoff, p->d_qlen, p->d_toff, p->d_tlen, p->d_qpoff, p->d_tpoff, p->d_qst, p->d_tst, p->d_qboff, p->d_qwords, p->d_qbits,
+			16u, 16u, status, n };
+		HIPCHK(c, bsa_launch_stage(sa, p->seq2bit, n >= 65536u ? 64u : 256u, p->qstrand, st));
+	}
 	EditArgs a;
 	memset(&a, 0, sizeof(a));
 	a.qst = p->d_qst; a.tst = p->d_tst; a.qpoff = p->d_qpoff; a.tpoff = p->d_tpoff;

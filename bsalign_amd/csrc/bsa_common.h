@@ -22,55 +22,8 @@ static inline int bsa_cus(){
 #define BSA_SCORE_MIN  (-(0x7FFFFFFF >> 2))    // bsalign.h:58
 #define BSA_QPAD_CODE  4                       // staged query code for columns >= qlen (S = -63, bsalign.h:2157-2160)
 
-// BSA_MODE_SEQ2BIT blobs (include/bsalign_hip.h): base i at bits 62 - 2 (i % 32) of word i / 32.  The 16 bases [pos, pos + 16) as a
-// 32-bit value LSB first (base pos + j at bits 2j, 2j + 1), bases at or past `end` zero.  Loads the word of `pos` and, only when a base
-// before `end` lies in it, the next one -- never a word behind the one that holds base end - 1 (a caller's array may end there).
-__device__ __forceinline__ uint32_t bsa_bits16(const uint64_t *w, uint64_t pos, uint64_t end){
-	if(pos >= end) return 0u;
-	const uint64_t idx = pos >> 5, rem = end - pos;
-	const uint32_t r = (uint32_t)(pos & 31u);
-	uint64_t hi = w[idx] << (2u * r);                               // MSB first: base pos at bits 63:62
-	if(r > 16u && ((pos + (rem < 16u ? rem : 16u) - 1u) >> 5) != idx) hi |= w[idx + 1] >> (64u - 2u * r);      // (funnel shift across the word boundary)
-	uint32_t x = __builtin_bitreverse32((uint32_t)(hi >> 32));      // base pos + j at bits 2j (its low bit) and 2j + 1 swapped ...
-	x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);         // ... and swapped back
-	if(rem < 16u) x &= (1u << (2u * (uint32_t)rem)) - 1u;
-	return x;
-}
-// BSA_MODE_QSTRAND: the reverse twin -- the 16 bases [end - 16, end) read backwards and complemented (3 - c), LSB first: base end - 1 - j at
-// bits 2j, 2j + 1, bases before `beg` zero.  Inside a word the MSB-first order IS the wanted order read from the other end (base p + 1 sits
-// two bits below base p), so there is no bit reversal: a funnel shift, a NOT and a mask.  Loads the word of base end - 1 and, only when a
-// base at or after `beg` lies in it, the one in front -- never a word in front of the one that holds base `beg`.
-__device__ __forceinline__ uint32_t bsa_bits16_rc(const uint64_t *w, uint64_t beg, uint64_t end){
-	if(end <= beg) return 0u;
-	const uint64_t last = end - 1u, idx = last >> 5, rem = end - beg;
-	const uint32_t r = (uint32_t)(last & 31u);
-	uint32_t x = (uint32_t)(w[idx] >> (62u - 2u * r));              // base end - 1 at bits 1:0, the r bases in front of it above
-	if(r < 15u && ((end - (rem < 16u ? rem : 16u)) >> 5) != idx) x |= (uint32_t)w[idx - 1] << (2u * r + 2u);      // (funnel shift across the word boundary)
-	x = ~x;
-	if(rem < 16u) x &= (1u << (2u * (uint32_t)rem)) - 1u;
-	return x;
-}
-// 8 codes (2 bits each, LSB first) -> 8 bytes
-__device__ __forceinline__ uint64_t bsa_spread8(uint32_t x){
-	uint64_t v = x & 0xFFFFu;
-	v = (v | (v << 24)) & 0x000000FF000000FFull;
-	v = (v | (v << 12)) & 0x000F000F000F000Full;
-	return (v | (v << 6)) & 0x0303030303030303ull;
-}
-// the even bits of x, packed (bit 2j -> bit j)
-__device__ __forceinline__ uint32_t bsa_even16(uint32_t x){
-	x &= 0x55555555u;
-	x = (x | (x >> 1)) & 0x33333333u;
-	x = (x | (x >> 2)) & 0x0F0F0F0Fu;
-	x = (x | (x >> 4)) & 0x00FF00FFu;
-	return (x | (x >> 8)) & 0x0000FFFFu;
-}
-// bytes [rem, 8) of v replaced by `pad` (rem may be <= 0 or >= 8)
-__device__ __forceinline__ uint64_t bsa_pad_bytes(uint64_t v, int64_t rem, uint8_t pad){
-	if(rem >= 8) return v;
-	const uint64_t keep = rem <= 0 ? 0ull : (1ull << (8u * (uint32_t)rem)) - 1ull;
-	return (v & keep) | ((uint64_t)pad * 0x0101010101010101ull & ~keep);
-}
+// the blob readers (bsa_bits16, bsa_bits16_rc, bsa_spread8, bsa_even16, bsa_pad_bytes, bsa_seq16) are in bsa_seq.h
+#include "bsa_seq.h"
 
 // device-side description of one batch chunk of the 8-bit path
 // bytes of padding behind the band of a staged query (bsa_api.hip: qpad = widest band + BSA_QPAD_TAIL): the forward kernels' LDS query window
@@ -339,10 +292,16 @@ EditChoice bsa_edit_choose(const EditArgs &a, bool alone);          // a's class
 // and fwd[1] form, n, tiled, track, lanes, grid, block; of trace form, tiled, lanes, grid; row_fmt.  false = no forward launch
 bool bsa_edit_choice(uint32_t bw, uint32_t wide, uint32_t count, int mode, uint32_t bandwidth, bool score, bool alone, int cus, int occ_plain, int occ_coop,
 		uint64_t out[BSA_EDIT_CHOICE_WORDS], const char **fwd_name, const char **trace_name);
-hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
-		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit = false,       // seq2bit: BSA_MODE_SEQ2BIT words
-		bool qstrand = false);                                                                                          // qstrand: BSA_MODE_QSTRAND, bit 63 of qoff[k] asks for the reverse complement
+// the staging launch of both plans (bsa_stage.hip): the blob with its offsets and lengths by pair, the staged regions and their offsets, and -- the edit
+// plan's, null in the align plan's, which the kernel is chosen by -- the planes with their word offsets and sizes; qpad / tpad: the align form's padding
+struct StageArgs {
+	const uint8_t *seqs; const uint64_t *qoff; const uint32_t *qlen; const uint64_t *toff; const uint32_t *tlen;
+	const uint64_t *qpoff, *tpoff; uint8_t *qst, *tst;
+	const uint64_t *qboff; const uint32_t *qwords; uint64_t *qbits;
+	uint32_t qpad, tpad; uint32_t *status; uint32_t n;
+};
+// seq2bit: BSA_MODE_SEQ2BIT words; tpp: threads per pair, 64 or 256 (the caller's rule); qstrand: BSA_MODE_QSTRAND, bit 63 of qoff[k] asks for the reverse complement
+hipError_t bsa_launch_stage(const StageArgs &a, bool seq2bit, uint32_t tpp, bool qstrand, hipStream_t st);
 hipError_t bsa_launch_edit_fwd(const EditArgs &a, const EditChoice &c, hipStream_t st);
 hipError_t bsa_launch_edit_trace(const EditArgs &a, const EditChoice &c, bsa_result_t *out, uint32_t *cig_cnt, hipStream_t st);
 hipError_t bsa_launch_edit_score_finish(const EditArgs &a, bsa_result_t *out, hipStream_t st);        // BSA_MODE_SCORE_ONLY: records -> results

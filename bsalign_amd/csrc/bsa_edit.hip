@@ -1335,127 +1335,8 @@ __global__ void __launch_bounds__(256) k_edit_score_finish(const EditArgs a, bsa
 	if(lane == 0) out[pair] = rs;
 }
 
-// stage one pair per block: query -> two bit planes (bit p of plane b = bit b of base p; zero beyond qlen),
-// query and target bytes copied (the traceback compares bases), codes validated
-// (TPP threads per pair: the block for few long pairs, a wave for batches of many -- the k-mer path stages 1.5 M pieces of ~26 bp)
-// QS (plans with BSA_MODE_QSTRAND): bit 63 of qoff[k] asks for the query's reverse complement -- piece i of it is the 16 stored bytes that
-// end at qlen - i, byte-reversed and complemented; bytes and planes are then those of the reverse complement
-template<int TPP, bool QS = false>
-__global__ void __launch_bounds__(256) k_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
-		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
-		const uint64_t *qboff, const uint32_t *qwords, uint8_t *qst, uint8_t *tst, u64 *qbits, uint32_t *status, uint32_t n){
-	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
-	if(k >= n) return;
-	const uint32_t ql = qlen[k], tl = tlen[k], nw = qwords[k];
-	const uint64_t qo = qoff[k];
-	const bool qrev = QS && (qo & BSA_QOFF_REVCOMP) != 0;
-	const uint8_t *q = seqs + (QS ? qo & ~BSA_QOFF_REVCOMP : qo), *t = seqs + toff[k];
-	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
-	u64 *p0 = qbits + qboff[k], *p1 = p0 + nw;
-	uint32_t bad = 0;
-	// 16 bases per thread and trip: two 8-byte loads (the piece that holds the end byte by byte), the staged bytes as one 16-byte
-	// store, the two planes as 16 bits each (bit 0 / bit 1 of eight bytes gathered by a multiplication)
-	auto piece = [&](const uint8_t *src, uint32_t len, uint32_t i, u64 &v0, u64 &v1, bool rev){
-		if(i + 16u <= len){
-			if(QS && rev){
-				__builtin_memcpy(&v1, src + (len - i - 16u), 8); __builtin_memcpy(&v0, src + (len - i - 8u), 8);
-				v0 = __builtin_bswap64(v0); v1 = __builtin_bswap64(v1);
-			} else { __builtin_memcpy(&v0, src + i, 8); __builtin_memcpy(&v1, src + i + 8, 8); }
-			if((v0 | v1) & 0xFCFCFCFCFCFCFCFCull){ bad = 1; v0 &= 0x0303030303030303ull; v1 &= 0x0303030303030303ull; }
-			if(QS && rev){ v0 ^= 0x0303030303030303ull; v1 ^= 0x0303030303030303ull; }
-		} else {
-			v0 = v1 = 0;
-#pragma unroll
-			for(uint32_t b = 0; b < 16u; b++){
-				uint8_t c = (i + b < len) ? ((QS && rev) ? src[len - 1u - i - b] : src[i + b]) : (uint8_t)0;
-				if(c > 3){ bad = 1; c &= 3; }
-				if(QS && rev && i + b < len) c ^= 3;
-				if(b < 8u) v0 |= (u64)c << (8u * b); else v1 |= (u64)c << (8u * (b - 8u));
-			}
-		}
-	};
-	auto gather = [](u64 v) -> uint32_t { return (uint32_t)(((v & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56); };   // bit 0 of byte j -> bit j
-	const uint32_t qbytes = (ql + 16u + 15u) & ~15u, qplane = nw * 64u;
-	for(uint32_t i = lane * 16u; i < max(qbytes, qplane); i += (uint32_t)TPP * 16u){
-		u64 v0, v1;
-		piece(q, ql, i, v0, v1, qrev);
-		if(i < qbytes){ uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dq + i) = o; }
-		if(i < qplane){
-			((uint16_t*)p0)[i >> 4] = (uint16_t)(gather(v0) | (gather(v1) << 8));
-			((uint16_t*)p1)[i >> 4] = (uint16_t)(gather(v0 >> 1) | (gather(v1 >> 1) << 8));
-		}
-	}
-	const uint32_t tbytes = (tl + 16u + 15u) & ~15u;
-	for(uint32_t i = lane * 16u; i < tbytes; i += (uint32_t)TPP * 16u){
-		u64 v0, v1;
-		piece(t, tl, i, v0, v1, false);
-		uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dt + i) = o;
-	}
-	uint32_t st = 0;
-	if((TPP == 64) ? __any((int)bad) : __syncthreads_or((int)bad)) st |= BSA_ST_BAD_BASE;
-	if(ql == 0 || tl == 0) st |= BSA_ST_EMPTY;
-	if(lane == 0) status[k] = st;
-}
-
-// k_edit_stage for BSA_MODE_SEQ2BIT blobs: base offsets into 2-bit packed words (bsa_common.h, bsa_bits16).  The two planes come straight
-// from the bits (bit 0 / bit 1 of each base de-interleaved), the staged bytes from spreading them; zero beyond the sequence, no
-// BSA_ST_BAD_BASE (no code is above 3).  QS: a marked query comes through bsa_bits16_rc.
-template<int TPP, bool QS = false>
-__global__ void __launch_bounds__(256) k_edit_stage2b(const uint64_t *seqs, const uint64_t *qoff, const uint32_t *qlen,
-		const uint64_t *toff, const uint32_t *tlen, const uint64_t *qpoff, const uint64_t *tpoff,
-		const uint64_t *qboff, const uint32_t *qwords, uint8_t *qst, uint8_t *tst, u64 *qbits, uint32_t *status, uint32_t n){
-	const uint32_t k = (TPP == 64) ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x, lane = threadIdx.x & (uint32_t)(TPP - 1);
-	if(k >= n) return;
-	const uint32_t ql = qlen[k], tl = tlen[k], nw = qwords[k];
-	const uint64_t qraw = qoff[k], to = toff[k];
-	const bool qrev = QS && (qraw & BSA_QOFF_REVCOMP) != 0;
-	const uint64_t qo = QS ? qraw & ~BSA_QOFF_REVCOMP : qraw;
-	uint8_t *dq = qst + qpoff[k], *dt = tst + tpoff[k];
-	u64 *p0 = qbits + qboff[k], *p1 = p0 + nw;
-	const uint32_t qbytes = (ql + 16u + 15u) & ~15u, qplane = nw * 64u;
-	for(uint32_t i = lane * 16u; i < max(qbytes, qplane); i += (uint32_t)TPP * 16u){
-		const uint32_t x = (QS && qrev) ? (i < ql ? bsa_bits16_rc(seqs, qo, qo + ql - i) : 0u) : bsa_bits16(seqs, qo + i, qo + ql);
-		if(i < qbytes){
-			const u64 v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
-			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dq + i) = o;
-		}
-		if(i < qplane){
-			((uint16_t*)p0)[i >> 4] = (uint16_t)bsa_even16(x);
-			((uint16_t*)p1)[i >> 4] = (uint16_t)bsa_even16(x >> 1);
-		}
-	}
-	const uint32_t tbytes = (tl + 16u + 15u) & ~15u;
-	for(uint32_t i = lane * 16u; i < tbytes; i += (uint32_t)TPP * 16u){
-		const uint32_t x = bsa_bits16(seqs, to + i, to + tl);
-		const u64 v0 = bsa_spread8(x), v1 = bsa_spread8(x >> 16);
-		uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32); *(uint4*)(dt + i) = o;
-	}
-	if(lane == 0) status[k] = (ql == 0 || tl == 0) ? BSA_ST_EMPTY : 0u;
-}
-
 bool bsa_edit_supported_bw(uint32_t bw){       // register kernels up to 16 words, the generic kernel beyond
 	return bw >= 64 && (bw % 64) == 0;
-}
-
-// Every launch of this file is one row of a switch over a packed key, one row macro per kernel wrapper (a key written twice does not compile; a description without
-// a row launches nothing and is hipErrorInvalidValue).  The staging kernels: keyed by the blob's format, the threads per pair and QS.
-constexpr uint32_t stage_key(bool seq2bit, uint32_t tpp, bool qs){ return (uint32_t)seq2bit | (uint32_t)qs << 1 | tpp << 2; }
-#define E_STAGE_ARGS qoff, qlen, toff, tlen, qpoff, tpoff, qboff, qwords, qst, tst, (u64*)qbits, status, n
-#define E_STAGE_K(TPP, QS) case stage_key(false, TPP, QS): hipLaunchKernelGGL((k_edit_stage<TPP, QS>), grid, dim3(256), 0, st, seqs, E_STAGE_ARGS); break;
-#define E_STAGE2B_K(TPP, QS) case stage_key(true, TPP, QS): hipLaunchKernelGGL((k_edit_stage2b<TPP, QS>), grid, dim3(256), 0, st, (const uint64_t*)seqs, E_STAGE_ARGS); break;
-hipError_t bsa_launch_edit_stage(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const uint64_t *toff, const uint32_t *tlen,
-		const uint64_t *qpoff, const uint64_t *tpoff, const uint64_t *qboff, const uint32_t *qwords,
-		uint8_t *qst, uint8_t *tst, uint64_t *qbits, uint32_t *status, uint32_t n, hipStream_t st, bool seq2bit, bool qstrand){
-	if(n == 0) return hipSuccess;
-	// a wave per pair from 65 536 pairs on, a block below; the QS instantiations only for plans with BSA_MODE_QSTRAND
-	const uint32_t tpp = n >= 65536u ? 64u : 256u;
-	const dim3 grid(tpp == 64u ? (n + 3u) / 4u : n);
-	switch(stage_key(seq2bit, tpp, qstrand)){
-		E_STAGE_K(64, false) E_STAGE_K(256, false) E_STAGE_K(64, true) E_STAGE_K(256, true)
-		E_STAGE2B_K(64, false) E_STAGE2B_K(256, false) E_STAGE2B_K(64, true) E_STAGE2B_K(256, true)
-		default: return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
 }
 
 // The launchers' BSA_EDIT_* knobs, each read here and nowhere else (BSA_EDIT_NO_MERGE is the plan's, bsa_api.hip); edit_choose takes them anew for every choice.
@@ -1552,6 +1433,8 @@ EditChoice bsa_edit_choose(const EditArgs &a, bool alone){
 	return edit_choose(a.bw, a.wide, a.count, a.mode, a.bandwidth, a.score != 0u, alone, bsa_cus(), occ_plain, occ_coop);
 }
 
+// Every launch of this file is one row of a switch over a packed key, one row macro per kernel wrapper (a key written twice does not compile; a description without
+// a row launches nothing and is hipErrorInvalidValue).
 // The forward kernels: every instance the file builds is one row, keyed by the description that runs it (n: NW, G or WPL; TRACK: the register kernels outside global mode)
 constexpr uint32_t fwd_key(uint32_t form, uint32_t n, bool tiled, bool track, bool score){ return form | n << 3 | (uint32_t)tiled << 8 | (uint32_t)track << 9 | (uint32_t)score << 10; }
 #define E_REG_K1(N, TRACK, SCORE) case fwd_key(E_REG, N, false, TRACK, SCORE): hipLaunchKernelGGL((k_edit_fwd<N, TRACK, SCORE>), grid, block, 0, st, a, f.lanes); break;

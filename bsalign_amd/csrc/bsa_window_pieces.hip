@@ -18,8 +18,8 @@
 //            function of the record indices, so what the atomics did to the slots does not show.  The windows that fit are a prefix of the
 //            windows (both offset arrays ascend); the wave of the last one leaves the number of records written for the gather;
 //   gather : 16 lanes a piece, four pieces a wave, over the records just written (k_window_pieces_gather<PACKED, STRANDS>): the bytes in front
-//            of the first 16-byte border of the destination one a lane, then 16 codes a lane and trip -- two unaligned 8-byte loads (byte-reversed
-//            and ^ 3 for a marked read, as k_stage<.., true> does) or bsa_bits16 / bsa_bits16_rc from packed words -- into one aligned 16-byte
+//            of the first 16-byte border of the destination one a lane, then 16 codes a lane and trip -- the staging kernels' reader (bsa_seq.h,
+//            bsa_seq16: two unaligned 8-byte loads, byte-reversed and ^ 3 for a marked read, or two bits a base from packed words) -- into one aligned 16-byte
 //            store, then the bytes behind the last border one a lane.  Every load lies inside the piece, so inside the read.
 // No LDS in this file's kernels, plain C++ with vector loads, stores and atomics only.
 #include "bsa_pass.h"
@@ -105,8 +105,6 @@ __global__ void __launch_bounds__(256) k_window_pieces_order(const bsa_window_t 
 	}
 }
 
-static __device__ __forceinline__ uint64_t wp_load8(const uint8_t *p){ uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
-
 // PK: BSA_MODE_SEQ2BIT words; QS: BSA_MODE_QSTRAND, bit 63 of qoff[k] asks for the reverse complement
 template<bool PK, bool QS>
 __global__ void __launch_bounds__(256) k_window_pieces_gather(const uint8_t *seqs, const uint64_t *qoff, const uint32_t *qlen, const bsa_piece_t *piece,
@@ -133,21 +131,19 @@ __global__ void __launch_bounds__(256) k_window_pieces_gather(const uint8_t *seq
 		if(gl < head) dst[gl] = code(qf + gl);
 		const uint32_t body = (len - head) >> 4;
 		for(uint32_t c = gl; c < body; c += 16u){
-			const uint32_t x = qf + head + 16u * c;                              // q'[x, x + 16)
-			uint64_t v0, v1;
+			const uint32_t x = qf + head + 16u * c;                              // q'[x, x + 16): a whole piece of the read (x + 16 <= qf + len <= ql)
+			// The reader (bsa_seq16) is given the read's own bounds, the loads are the piece's: with sixteen bases or more between them the second-word
+			// conditions of bsa_bits16 (pos, end) and bsa_bits16_rc (beg, end) look at pos + 15 and at end - 16 alone, whatever `end` and `beg` are.
+			// "A whole piece", said in the terms the reader tests, so that its end-piece paths are not compiled in (each holds: x + 16 <= ql, off < 2^63):
+			__builtin_assume(x + 16u <= ql);
 			if(PK){
-				const uint32_t bits = rev ? bsa_bits16_rc(words, off + (ql - x - 16u), off + (ql - x)) : bsa_bits16(words, off + x, off + x + 16u);
-				v0 = bsa_spread8(bits); v1 = bsa_spread8(bits >> 16);
-			} else {
-				if(rev){
-					const uint8_t *s = seqs + off + (ql - x - 16u);              // the 16 stored bytes that end at ql - x, read backwards
-					v1 = __builtin_bswap64(wp_load8(s)); v0 = __builtin_bswap64(wp_load8(s + 8));
-					v0 ^= 0x0303030303030303ull; v1 ^= 0x0303030303030303ull;
-				} else { v0 = wp_load8(seqs + off + x); v1 = wp_load8(seqs + off + x + 8u); }
-				v0 &= 0x0303030303030303ull; v1 &= 0x0303030303030303ull;
+				__builtin_assume(off + x < off + ql); __builtin_assume((off + ql) - (off + x) >= 16u);          // bsa_bits16(w, off + x, off + ql)
+				__builtin_assume(off + ql - x > off); __builtin_assume((off + ql - x) - off >= 16u);            // bsa_bits16_rc(w, off, off + ql - x)
 			}
-			uint4 o; o.x = (uint32_t)v0; o.y = (uint32_t)(v0 >> 32); o.z = (uint32_t)v1; o.w = (uint32_t)(v1 >> 32);
-			*(uint4*)(dst + head + 16u * c) = o;
+			uint64_t v0, v1;
+			uint32_t bad = 0;                                                    // (codes are taken & 3; nobody is told)
+			bsa_seq16<PK, QS>(seqs, off, ql, x, rev, (uint8_t)0, v0, v1, bad);
+			bsa_store16(dst + head + 16u * c, v0, v1);
 		}
 		const uint32_t tb = head + 16u * body;
 		if(gl < len - tb) dst[tb + gl] = code(qf + tb + gl);

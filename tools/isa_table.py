@@ -4,6 +4,8 @@
     hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S parent/bsa_align8_x.hip -o parent.s      (the same for the candidate)
     python tools/isa_table.py parent.s candidate.s [-o profiles/x_shared_isa.json] [--rename REGEX REPL ...]
 
+Either side may be several assembly files joined by commas (a.s,b.s), for a change that moves kernels between files: their kernels form one table.
+
 Reads the registers, scratch, LDS and spill count of every kernel from the assembly's metadata, counts each kernel's instruction lines (all, and those
 that begin with v_) and hashes its instruction text (labels without the function's number, so that kernels added before it do not change it).  --rename
 rewrites the candidate's mangled kernel names before they are matched (the first pattern that matches a name decides), for a change that adds a template parameter: the kernels keep their rows.  Prints the kernels whose figures differ; exit status 1 when the sets of kernels differ or scratch, LDS, a spill count or the
@@ -78,7 +80,11 @@ def main():
     ap.add_argument("-o", "--out")
     ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     a = ap.parse_args()
-    par, cand = read_asm(a.parent), read_asm(a.candidate, a.rename)
+    par, cand = {}, {}
+    for path in a.parent.split(","):
+        par.update(read_asm(path))
+    for path in a.candidate.split(","):
+        cand.update(read_asm(path, a.rename))
     names = demangle(sorted(set(par) | set(cand)))
     bad = set(par) != set(cand)
     table = {}
