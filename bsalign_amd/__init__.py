@@ -99,6 +99,8 @@ _lib = None
 # bsa_cns_window_t (include/bsalign_msa.h): what bsa_window_msa_* writes and bsa_msa_call_consensus_batch takes
 CNS_WINDOW_DTYPE = np.dtype([("cols_off", np.uint64), ("idxs_off", np.uint64), ("out_off", np.uint64),
                              ("nall", np.uint32), ("nseq", np.uint32), ("nmax", np.uint32), ("mlen", np.uint32)])
+# d_status of bsa_window_cns_*: the first clause of the live predicate that a window fails (BSA_CNS_ST_*)
+CNS_ST_OK, CNS_ST_BAD_RECORD, CNS_ST_TOO_DEEP, CNS_ST_NO_ROOM = 0, 1, 2, 3
 DIAGDP_PROB_DTYPE = np.dtype([("seq0", np.uint64), ("seq1", np.uint64), ("mats0", np.uint64, (4,)), ("mats1", np.uint64, (4,)),
                               ("out0", np.uint64), ("out1", np.uint64), ("mlen", np.uint32), ("mbeg", np.uint32), ("mend", np.uint32), ("W", np.uint32)])
 
@@ -218,6 +220,14 @@ def lib():
             L.bsa_window_msa_run.argtypes = [vp, vp, u64p, C.c_size_t, C.c_size_t, u8p, C.c_size_t, u32p, C.c_size_t, u64p, u8p, u64p, u32p,
                                              C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t, u64p, vp]
             L.bsa_window_msa_batch.argtypes = L.bsa_window_msa_run.argtypes
+        if hasattr(L, "bsa_window_cns_run"):
+            L.bsa_cns_model_create.argtypes = [vp, vp, C.POINTER(vp)]
+            L.bsa_cns_model_destroy.argtypes = [vp]
+            L.bsa_cns_model_destroy.restype = None
+            L.bsa_window_cns_run.argtypes = [vp, vp, u8p, C.c_size_t, vp, C.c_size_t, C.c_uint32, u8p, u8p, u8p, C.c_size_t, u32p, vp, u32p,
+                                             u8p, u8p, u8p, C.c_size_t, u64p]
+            L.bsa_window_cns_batch.argtypes = L.bsa_window_cns_run.argtypes
+            L.bsa_window_cns_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_cns_run.argtypes[1:]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -509,11 +519,15 @@ class Context:
         if rc != 0:
             raise BsaError(rc, "bsa_ctx_create: no usable GPU; this library has no CPU fallback")
         self.h = h
+        self._models = []
         if workspace_limit:
             lib().bsa_ctx_set_workspace_limit(self.h, workspace_limit)
 
     def close(self):
         if self.h:
+            for m in getattr(self, "_models", []):              # (a model is closed with its context)
+                m.close()
+            self._models = []
             lib().bsa_ctx_destroy(self.h)
             self.h = None
 
@@ -947,6 +961,101 @@ class Context:
         self._chk(lib().bsa_window_msa_run(self.h, ptr(d_piece), ptr(d_piece_off), nwin, piece_cap, ptr(d_bases), bases_cap, ptr(d_pcig), pcig_cap,
                                            ptr(d_pcig_off), ptr(d_draft), ptr(d_doff), ptr(d_dlen), int(window), int(flags), int(vote),
                                            ptr(d_cols), cols_cap, ptr(d_cols_off), ptr(d_cwin)))
+
+    def cns_model(self, par7):
+        """bsa_cns_model_create: the consensus model of the seven rates (bsa_cns_params_t: psub pins pdel piex pdex hins hdel) resident on the device,
+        for window_cns_run; closed with the context (or by its own close())."""
+        m = CnsModel(self, par7)
+        self._models.append(m)
+        return m
+
+    def window_cns_run(self, model, d_cols, cols_cap, d_cwin, nwin, max_rows, d_cns, d_qlt, d_alt, out_cap, d_clen, d_score=None, d_status=None,
+                       d_seq=None, d_seq_qlt=None, d_seq_alt=None, seq_cap=0, d_seq_off=None):
+        """bsa_window_cns_run on torch tensors (plumbing only), asynchronous on the context's stream: d_cols and d_cwin as window_msa_run left them,
+        cols_cap and out_cap the room of d_cols and of each of d_cns, d_qlt, d_alt; max_rows the largest nseq of the records; d_clen (32-bit),
+        d_score (float64) and d_status (32-bit) one entry a window.  With d_seq_off (nwin + 1 64-bit words) the windows' called bases are packed:
+        window g's are d_seq[d_seq_off[g] : d_seq_off[g + 1]] where d_seq_off[g + 1] <= seq_cap, likewise d_seq_qlt and d_seq_alt (either may be
+        None); d_seq_off[nwin] is what a complete run needs."""
+        size = lambda t: t.numel() * t.element_size()
+        if d_cols is not None and size(d_cols) < cols_cap:
+            raise ValueError("window_cns_run: d_cols holds fewer than cols_cap bytes")
+        if d_cwin is not None and size(d_cwin) < 40 * nwin:
+            raise ValueError("window_cns_run: d_cwin holds fewer than nwin records")
+        if any(t is not None and size(t) < out_cap for t in (d_cns, d_qlt, d_alt)):
+            raise ValueError("window_cns_run: an output array holds fewer than out_cap bytes")
+        if any(t is not None and size(t) < w * nwin for t, w in ((d_clen, 4), (d_score, 8), (d_status, 4))):
+            raise ValueError("window_cns_run: d_clen, d_score or d_status holds fewer than nwin entries")
+        if any(t is not None and size(t) < seq_cap for t in (d_seq, d_seq_qlt, d_seq_alt)):
+            raise ValueError("window_cns_run: a compact array holds fewer than seq_cap bytes")
+        if d_seq_off is not None and size(d_seq_off) < 8 * (nwin + 1):
+            raise ValueError("window_cns_run: d_seq_off holds fewer than nwin + 1 offsets")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_cns_run(self.h, model.h if model is not None else None, ptr(d_cols), cols_cap, ptr(d_cwin), nwin, int(max_rows),
+                                           ptr(d_cns), ptr(d_qlt), ptr(d_alt), out_cap, ptr(d_clen), ptr(d_score), ptr(d_status),
+                                           ptr(d_seq), ptr(d_seq_qlt), ptr(d_seq_alt), seq_cap, ptr(d_seq_off)))
+
+    def window_cns(self, msas, par7, max_rows=None):
+        """bsa_window_cns_batch on what Context.window_msa returned (the list over the windows of (cols, cwin)): every window's consensus and the
+        polished sequence of the call.  Returns (a list over the windows of (cns, qlt, alt, score, status, cols) -- the called bases, both quality
+        strings, the log probability of the best path, CNS_ST_*, and the window's columns with their three consensus bytes written --,
+        (seq, seq_qlt, seq_alt, seq_off): the windows' called bases and qualities one behind the other, window g's at seq_off[g] : seq_off[g + 1]).
+        max_rows: the largest nseq the call accepts (default: the largest of the records)."""
+        nwin = len(msas)
+        cwin = np.zeros(max(nwin, 1), dtype=CNS_WINDOW_DTYPE)
+        parts, cacc, oacc = [], 0, 0
+        for g, (cols, rec) in enumerate(msas):
+            cols = _np(cols, np.uint8).reshape(-1)
+            cwin[g] = (cacc, 0xFFFFFFFFFFFFFFFF, oacc, rec["nall"], rec["nseq"], rec["nmax"], rec["mlen"])
+            parts.append(cols)
+            cacc += cols.size
+            oacc += int(rec["mlen"])
+        blob = _np(np.concatenate([np.zeros(0, np.uint8)] + parts), np.uint8).copy()
+        if max_rows is None:
+            max_rows = int(cwin["nseq"][:nwin].max()) if nwin else 0
+        par7 = np.ascontiguousarray(par7, np.float32)
+        cns, qlt, alt = (np.zeros(max(oacc, 1), np.uint8) for _ in range(3))
+        clen, score, status = np.zeros(max(nwin, 1), np.uint32), np.zeros(max(nwin, 1), np.float64), np.zeros(max(nwin, 1), np.uint32)
+        soff = np.zeros(nwin + 1, dtype=np.uint64)
+        seq, sq, sa, cap = None, None, None, 0
+        for _ in range(2):                                     # a count-only call says what is needed
+            rc = lib().bsa_window_cns_batch(self.h, _p(par7), _p(blob) if cacc else None, cacc, _p(cwin), nwin, int(max_rows), _p(cns), _p(qlt), _p(alt), oacc,
+                                            _p(clen), _p(score), _p(status), _p(seq) if cap else None, _p(sq) if cap else None, _p(sa) if cap else None, cap, _p(soff))
+            if rc != -5 or int(soff[nwin]) <= cap:
+                break
+            cap = int(soff[nwin])
+            seq, sq, sa = (np.zeros(cap, dtype=np.uint8) for _ in range(3))
+        self._chk(rc)
+        res = []
+        for g in range(nwin):
+            w = cwin[g]
+            o, n, c0 = int(w["out_off"]), int(clen[g]), int(w["cols_off"])
+            res.append((cns[o:o + n].copy(), qlt[o:o + n].copy(), alt[o:o + n].copy(), float(score[g]), int(status[g]),
+                        blob[c0:c0 + parts[g].size].reshape(int(w["mlen"]), int(w["nall"]) + 3).copy()))
+        empty = np.zeros(0, np.uint8)
+        return res, (seq if cap else empty, sq if cap else empty.copy(), sa if cap else empty.copy(), soff)
+
+
+class CnsModel:
+    """a consensus model resident on the device -- bsa_cns_model_create / bsa_cns_model_destroy (Context.cns_model)"""
+
+    def __init__(self, ctx, par7):
+        par7 = np.ascontiguousarray(par7, np.float32)
+        if par7.shape != (7,):
+            raise ValueError("cns_model: seven rates (psub pins pdel piex pdex hins hdel)")
+        h = C.c_void_p()
+        ctx._chk(lib().bsa_cns_model_create(ctx.h, _p(par7), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if self.h:
+            lib().bsa_cns_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def window_gbase(target_id, target_len, window):

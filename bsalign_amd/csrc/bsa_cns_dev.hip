@@ -15,9 +15,9 @@
 // the masses can differ from the host's in their last bits -- the consensus, both quality strings and every column's three bytes are
 // compared byte for byte in tests/test_cns_gpu.py, the log probability with a relative tolerance of 1e-12 (stated there).
 // Compiled with -ffp-contract=off: no multiply-add the host does not make.
-#include "../../include/bsalign_msa.h"
-#include "../../include/bsalign_hip.h"
-#include <hip/hip_runtime.h>
+// The two kernels have one launch site, bsa_cns_launch_internal (bsa_cns_dev.h), which the resident form shares (bsa_window_cns.hip:
+// bsa_window_cns_run on the columns and records bsa_window_msa_run left); the model's tables are filled in one place too.
+#include "bsa_cns_dev.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -34,20 +34,6 @@ constexpr double kDead = -1000000000.0;
 constexpr double kPhredCap = 90.0;
 constexpr int kGap = 4;
 constexpr int kAbsentIdx = 25;                 // table index of a read that is not in the column: five zeros
-
-struct CnsWinDev {
-	uint64_t cols_off, idxs_off;               // window's columns in the blob; its column order in the index blob (words), ~0: storage order
-	uint64_t out_off;                          // where its consensus / qualities go
-	uint64_t mass_off, org_off;                // workspace: (mlen + 1) x 5 doubles; (mlen + 1) packed origins (3 bits a state)
-	uint32_t nall, nseq, nmax, mlen;
-};
-
-struct CnsModelDev {
-	double cost[5][26][5];                     // [anchor][event * 5 + symbol | 25][target]
-	uint8_t next[5][25][5];
-	uint8_t pad[7];
-	double ln10, logp, log1mp, psub;
-};
 
 __device__ __forceinline__ double merge_log(double acc, double v){
 	if(v == kDead) return acc;
@@ -257,6 +243,37 @@ __global__ void __launch_bounds__(64) k_cns_finish(uint8_t *cols, const uint32_t
 
 }  // namespace
 
+void bsa_cns_model_fill_internal(const bsa_cns_params_t *par, CnsModelDev *mod, double *lf, uint32_t nlf){
+	memset(mod, 0, sizeof(CnsModelDev));
+	double cost[5][5][5][5]; uint8_t next[5][5][5][5]; double consts[4];
+	bsa_cns_model_internal(par, &cost[0][0][0][0], &next[0][0][0][0], lf, nlf, consts);
+	for(int a0 = 0; a0 < 5; a0++){
+		for(int d = 0; d < 5; d++) for(int b = 0; b < 5; b++) for(int a = 0; a < 5; a++){ mod->cost[a0][d * 5 + b][a] = cost[a0][d][b][a]; mod->next[a0][d * 5 + b][a] = next[a0][d][b][a]; }
+		for(int a = 0; a < 5; a++) mod->cost[a0][kAbsentIdx][a] = 0.0;
+	}
+	mod->ln10 = consts[0]; mod->logp = consts[1]; mod->log1mp = consts[2]; mod->psub = consts[3];
+}
+
+int bsa_cns_launch_internal(hipStream_t st, uint8_t *d_cols, const uint32_t *d_idxs, const CnsWinDev *d_wins, size_t nwin, const CnsModelDev *d_model,
+		const double *d_lf, uint8_t *d_ws, uint64_t max_nseq, uint8_t *d_cns, uint8_t *d_qlt, uint8_t *d_alt, uint32_t *d_clen, double *d_score, int steps){
+	uint32_t nsp;
+	const size_t lds = bsa_cns_lds_bytes(max_nseq, &nsp);
+	if(lds > BSA_CNS_LDS_MAX) return BSA_E_UNSUPPORTED;                      // (about 9900 reads in a window)
+	if(nwin == 0) return BSA_OK;
+#define CNS_TRY(call) do { hipError_t _e = (call); if(_e != hipSuccess) return (_e == hipErrorOutOfMemory) ? BSA_E_NOMEM : BSA_E_HIP; } while(0)
+	if(steps & 1){
+		if(lds > 64 * 1024) CNS_TRY(hipFuncSetAttribute((const void*)k_cns_dp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+		hipLaunchKernelGGL(k_cns_dp, dim3((uint32_t)nwin), dim3(64), lds, st, d_cols, d_idxs, d_wins, d_model, d_ws, nsp);
+		CNS_TRY(hipGetLastError());
+	}
+	if(steps & 2){
+		hipLaunchKernelGGL(k_cns_finish, dim3((uint32_t)nwin), dim3(64), 0, st, d_cols, d_idxs, d_wins, d_model, d_lf, d_ws, d_cns, d_qlt, d_alt, d_clen, d_score);
+		CNS_TRY(hipGetLastError());
+	}
+#undef CNS_TRY
+	return BSA_OK;
+}
+
 extern "C" int bsa_msa_call_consensus_batch(bsa_ctx_t *c, uint8_t *cols, size_t cols_bytes, const uint32_t *idxs, size_t idxs_words,
 		const bsa_cns_window_t *win, size_t nwin, const bsa_cns_params_t *par, uint8_t *cns, uint8_t *qlt, uint8_t *alt, size_t out_bytes,
 		uint32_t *clen, double *score){
@@ -287,23 +304,13 @@ extern "C" int bsa_msa_call_consensus_batch(bsa_ctx_t *c, uint8_t *cols, size_t 
 		d.org_off = wsb; wsb += (((size_t)w.mlen + 1) * sizeof(uint16_t) + 255) & ~(size_t)255;
 		max_nseq = std::max(max_nseq, w.nseq); max_nmax = std::max(max_nmax, w.nmax);
 	}
-	const uint32_t nsp = (max_nseq + 3u) & ~3u;
-	const size_t lds = sizeof(double) * 650 + 640 + (size_t)nsp * 16;
-	if(lds > 160 * 1024) return BSA_E_UNSUPPORTED;                           // (about 9900 reads in a window)
+	if(bsa_cns_lds_bytes(max_nseq, nullptr) > BSA_CNS_LDS_MAX) return BSA_E_UNSUPPORTED;      // (about 9900 reads in a window)
 	// the model: tables from the host's libm
 	std::vector<uint8_t> mh(sizeof(CnsModelDev), 0);
 	CnsModelDev *mod = (CnsModelDev*)mh.data();
 	const uint32_t nlf = std::min<uint32_t>(std::max<uint32_t>(max_nmax, 1u), 1000u) + 1u;
 	std::vector<double> lf(nlf);
-	{
-		double cost[5][5][5][5]; uint8_t next[5][5][5][5]; double consts[4];
-		bsa_cns_model_internal(par, &cost[0][0][0][0], &next[0][0][0][0], lf.data(), nlf, consts);
-		for(int a0 = 0; a0 < 5; a0++){
-			for(int d = 0; d < 5; d++) for(int b = 0; b < 5; b++) for(int a = 0; a < 5; a++){ mod->cost[a0][d * 5 + b][a] = cost[a0][d][b][a]; mod->next[a0][d * 5 + b][a] = next[a0][d][b][a]; }
-			for(int a = 0; a < 5; a++) mod->cost[a0][kAbsentIdx][a] = 0.0;
-		}
-		mod->ln10 = consts[0]; mod->logp = consts[1]; mod->log1mp = consts[2]; mod->psub = consts[3];
-	}
+	bsa_cns_model_fill_internal(par, mod, lf.data(), nlf);
 	auto up = [](size_t b){ return (b + 255) & ~(size_t)255; };
 	const size_t outb = (cns || qlt || alt) ? out_bytes : 0;
 	const size_t o_cols = 0, o_idx = o_cols + up(cols_bytes), o_win = o_idx + up(idxs_words * 4 + 4), o_mod = o_win + up(nwin * sizeof(CnsWinDev)),
@@ -319,12 +326,9 @@ extern "C" int bsa_msa_call_consensus_batch(bsa_ctx_t *c, uint8_t *cols, size_t 
 	CNS_TRY(hipMemcpyAsync(d + o_win, wd.data(), nwin * sizeof(CnsWinDev), hipMemcpyHostToDevice, st));
 	CNS_TRY(hipMemcpyAsync(d + o_mod, mod, sizeof(CnsModelDev), hipMemcpyHostToDevice, st));
 	CNS_TRY(hipMemcpyAsync(d + o_lf, lf.data(), nlf * 8, hipMemcpyHostToDevice, st));
-	if(lds > 64 * 1024) CNS_TRY(hipFuncSetAttribute((const void*)k_cns_dp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-	hipLaunchKernelGGL(k_cns_dp, dim3((uint32_t)nwin), dim3(64), lds, st, d + o_cols, (const uint32_t*)(d + o_idx), (const CnsWinDev*)(d + o_win), (const CnsModelDev*)(d + o_mod), d + o_ws, nsp);
-	CNS_TRY(hipGetLastError());
-	hipLaunchKernelGGL(k_cns_finish, dim3((uint32_t)nwin), dim3(64), 0, st, d + o_cols, (const uint32_t*)(d + o_idx), (const CnsWinDev*)(d + o_win), (const CnsModelDev*)(d + o_mod),
-		(const double*)(d + o_lf), d + o_ws, cns ? d + o_cns : nullptr, qlt ? d + o_qlt : nullptr, alt ? d + o_alt : nullptr, (uint32_t*)(d + o_clen), (double*)(d + o_score));
-	CNS_TRY(hipGetLastError());
+	rc = bsa_cns_launch_internal(st, d + o_cols, (const uint32_t*)(d + o_idx), (const CnsWinDev*)(d + o_win), nwin, (const CnsModelDev*)(d + o_mod), (const double*)(d + o_lf), d + o_ws,
+		max_nseq, cns ? d + o_cns : nullptr, qlt ? d + o_qlt : nullptr, alt ? d + o_alt : nullptr, (uint32_t*)(d + o_clen), (double*)(d + o_score), 3);
+	if(rc != BSA_OK) return rc;
 	CNS_TRY(hipMemcpyAsync(cols, d + o_cols, cols_bytes, hipMemcpyDeviceToHost, st));           // the three consensus bytes of every column
 	if(cns) CNS_TRY(hipMemcpyAsync(cns, d + o_cns, out_bytes, hipMemcpyDeviceToHost, st));
 	if(qlt) CNS_TRY(hipMemcpyAsync(qlt, d + o_qlt, out_bytes, hipMemcpyDeviceToHost, st));

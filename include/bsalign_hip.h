@@ -802,6 +802,94 @@ int      bsa_window_msa_batch(bsa_ctx_t *ctx,
                               uint32_t window, uint32_t flags, uint32_t vote,
                               uint8_t *cols, size_t cols_cap, uint64_t *cols_off /* nwin + 1 */, bsa_cns_window_t *cwin /* nwin */);
 
+/* bsa_window_cns_* : the consensus of every window's MSA where bsa_window_msa_run left it, and the windows' called bases packed into contiguous polished
+ *                    sequence -- the last step of the chain align -> windows -> pieces -> guides -> MSA -> consensus.  The automaton is that of
+ *                    bsa_msa_call_consensus_batch (bsalign_msa.h; bsa_cns_dev.hip's two kernels, unchanged, on the same tables): what differs is that the
+ *                    columns and records are DEVICE memory, that the records are judged on the device, and that nothing but the polished sequence has to
+ *                    come down.  A pass over public outputs (bsa_window_cns.hip): it touches no plan and changes no existing call.
+ * the model        : bsa_cns_model_create builds the tables of the rates `par` as bsa_msa_call_consensus_batch does (the logarithms by the host's libm, the
+ *                    all-zero entry of an absent read) and the table log(k!) at its full 1001 entries (entry k is a running sum from 0 and does not depend
+ *                    on the table's length, so every entry is the one the host-pointer call uploads), and uploads both once with synchronous copies: it may
+ *                    synchronise, and it is the only place where parameters cross to the device.  A model belongs to its context and is used by any number
+ *                    of runs; destroy it when no run that uses it is in flight (bsa_ctx_sync) and before its context.  NULL is fine to destroy.
+ * inputs           : d_cols and d_cwin are what bsa_window_msa_run left for nwin windows (any arrays of this layout serve); cols_cap is the room of d_cols.
+ *                    max_rows is the caller's promise of the largest nseq -- the host knows it from piece_off and vote: the largest depth + vote -- and sizes
+ *                    the automaton's LDS (16 bytes a row): a max_rows that needs more than 160 KB (about 9900 rows) is BSA_E_UNSUPPORTED.
+ * outputs          : d_cns, d_qlt, d_alt of out_cap bytes each, the layout of bsa_msa_call_consensus_batch: window g's called bases, their qualities and
+ *                    alternative qualities at [out_off, out_off + clen) of a range of room mlen (the rest of the range is not touched); d_clen[g] = clen,
+ *                    d_score[g] = the log probability of the best path, d_status[g] = BSA_CNS_ST_* (d_score and d_status may be NULL).  The three consensus
+ *                    bytes of every column of a live window are written as the host form writes them: called symbol (4: a gap), quality, alternative quality.
+ * the live window  : window g runs if and only if ALL of the clauses below hold; they are tested on the device in 64-bit arithmetic that cannot wrap, and
+ *                    d_status[g] reports the FIRST that fails --
+ *                      BSA_CNS_ST_BAD_RECORD : idxs_off == ~0 (storage order only: the resident form takes no index blob);  nseq <= nall;  nmax <= nall;
+ *                                              mlen < 2^31;  with the stride nall + 3 and mlen * stride formed in 64 bits, neither cols_off + mlen * stride
+ *                                              nor out_off + mlen wraps;
+ *                      BSA_CNS_ST_TOO_DEEP   : nseq <= max_rows;
+ *                      BSA_CNS_ST_NO_ROOM    : cols_off + mlen * stride <= cols_cap;  out_off + mlen <= out_cap;  t[g + 1] <= min(out_cap, cols_cap / 4),
+ *                                              where t is the pass's own exclusive sum of mlen over the windows that pass every clause in front of this one.
+ *                    t is the workspace cursor and bounds the scratch from the host; on what bsa_window_msa_run writes t equals out_off, so the last clause
+ *                    adds nothing there.  BSA_CNS_ST_OK is 0.  A window with mlen == 0 is live, with clen 0 and score 0.  This predicate is the only door to a
+ *                    window's columns, its outputs and its workspace: nothing a caller puts into d_cwin makes the pass read or write outside [0, cols_cap)
+ *                    of d_cols, outside [0, out_cap) of the three output arrays, or outside its scratch.  A window that is not live gets d_clen[g] = 0 and
+ *                    d_score[g] = 0; no byte of its columns is touched (its three consensus bytes stay 4 0 0) and no byte of its output range.
+ *                    The ranges of distinct live windows are expected to be disjoint, as the MSA pass makes them; where a caller makes them overlap, the
+ *                    bytes in the overlap are unspecified and nothing else is affected.
+ * compaction       : with d_seq_off (nwin + 1 entries) the exclusive sum of d_clen goes into it, and window g's bytes [out_off, out_off + clen) of d_cns,
+ *                    d_qlt and d_alt are copied to [d_seq_off[g], d_seq_off[g + 1]) of d_seq, d_seq_qlt and d_seq_alt (either quality array may be NULL).
+ *                    With bsa_window_pieces_*'s gbase numbering (Python: window_gbase) a draft's windows are consecutive, so its polished sequence is ONE
+ *                    range: from d_seq_off of its first window to d_seq_off behind its last.  That range is what comes down.
+ * arena            : the contract of bsa_window_pieces_run with the window as the unit.  For ANY seq_cap, 0 with non-NULL arrays and NULL arrays with
+ *                    seq_cap 0 (a count-only run) included:
+ *                      - all nwin + 1 entries of d_seq_off are written and are those of a run with a large arena; d_seq_off[nwin] is the bytes needed;
+ *                      - window g is copied if and only if d_seq_off[g + 1] <= seq_cap; a copied window is copied whole;
+ *                      - nothing at or above seq_cap is touched, and no byte of a window that is not copied.
+ *                    With d_seq_off NULL nothing is packed (d_seq, d_seq_qlt, d_seq_alt NULL and seq_cap 0 then).
+ * Example          : the 12 columns of the bsa_window_msa_* example with vote 1 (nseq = nmax = 3: the draft votes), the default rates 0.10 0.10 0.15 0.15
+ *                    0.20 0.20 0.40, cwin = {0, ~0, 0, nall 3, nseq 3, nmax 3, mlen 12}, cols_cap 72, out_cap 12, max_rows 3 --
+ *                      called symbol of the columns   0  1  2  3  2  4  0  1  2  3  0  1     (column 5: one inserted base against two gaps, called a gap)
+ *                      their quality                 90 90 90 90  2  4 10 90 90 90 90 90
+ *                      their alternative quality      0  0  0  0  5  5  5  0  0  0  0  0
+ *                    these are the bytes 3, 4 and 5 of every column; status 0, clen = 11, and the first 11 bytes of the output ranges are
+ *                      d_cns  0 1 2 3 2 0 1 2 3 0 1      d_qlt  90 90 90 90 2 10 90 90 90 90 90      d_alt  0 0 0 0 5 5 0 0 0 0 0
+ *                    (the twelfth byte of each range is not touched); d_seq_off = {0, 11} and d_seq, d_seq_qlt, d_seq_alt hold the same 11 bytes from 0 on.
+ *                    With vote 0 (nseq = nmax = 2) nothing is called a gap: clen = 12 and d_cns = row 0.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (a run that has to grow it may synchronise once; BSA_E_NOMEM when it cannot): about 80 bytes a window for the records and the
+ *                    scans' temporaries, and 42 bytes for every column of min(out_cap, cols_cap / 4) + nwin -- 40 for the five masses, 2 for the packed
+ *                    origins.  So the caps size the scratch: give out_cap as the sum of mlen (or bsa_window_msa_bound / 4 at most), not more.  At 100 000
+ *                    pairs of 10 kbp, windows of 500 and depth 40 it is about 1.8 GB.  The output is a function of the inputs alone; a second run on columns
+ *                    that already carry consensus bytes gives the same bytes; a run leaves nothing behind that a later run reads.
+ * _batch           : all pointers are HOST memory and `par` takes the model's place.  It creates a model, uploads the columns, the records and the output
+ *                    arrays as they are (so that a range no window owns comes down as it went up), runs, downloads clen, score, status and seq_off FIRST and
+ *                    synchronises: seq_cap too small is BSA_E_CIGAR_CAP there, seq_off[nwin] = the bytes needed, cols and the six arrays untouched.  Then the
+ *                    columns, the three output arrays and seq_off[nwin] bytes of the compact arrays come down.  It serves callers without device buffers and
+ *                    the tests; it is not a second implementation.
+ * errors (both)    : a NULL ctx or model (_batch: par); with nwin > 0 a NULL d_cwin, d_clen, d_cns, d_qlt or d_alt; a cap without its arena (cols_cap
+ *                    without d_cols, seq_cap without d_seq); d_seq, d_seq_qlt, d_seq_alt or seq_cap given without d_seq_off; nwin above 0xFFFFFFF0; a model
+ *                    of another context: BSA_E_ARG.  nwin == 0 writes d_seq_off[0] = 0 if d_seq_off is given, and nothing else.
+ * Example          : behind the bsa_window_msa_run of that block's example, with the model made once --
+ *                      bsa_cns_model_create(ctx, &par, &model);
+ *                      bsa_window_cns_run(ctx, model, d_cols, cols_cap, d_cwin, nwin, 40 + vote, d_cns, d_qlt, d_alt, out_cap, d_clen, NULL, d_status,
+ *                                         d_seq, d_seq_qlt, NULL, out_cap, d_seq_off); bsa_ctx_sync(ctx);
+ *                    then draft j's polished bases are d_seq[d_seq_off[first window of j] .. d_seq_off[first window of j + 1]). */
+#define BSA_CNS_ST_OK         0u
+#define BSA_CNS_ST_BAD_RECORD 1u
+#define BSA_CNS_ST_TOO_DEEP   2u
+#define BSA_CNS_ST_NO_ROOM    3u
+typedef struct bsa_cns_model bsa_cns_model_t;
+int  bsa_cns_model_create(bsa_ctx_t *ctx, const bsa_cns_params_t *par, bsa_cns_model_t **out);
+void bsa_cns_model_destroy(bsa_cns_model_t *m);          /* NULL is fine */
+int  bsa_window_cns_run(bsa_ctx_t *ctx, const bsa_cns_model_t *model,
+                        uint8_t *d_cols, size_t cols_cap, const bsa_cns_window_t *d_cwin, size_t nwin, uint32_t max_rows,
+                        uint8_t *d_cns, uint8_t *d_qlt, uint8_t *d_alt, size_t out_cap,     /* per window at out_off, room mlen each */
+                        uint32_t *d_clen, double *d_score, uint32_t *d_status,               /* nwin each; d_score and d_status may be NULL */
+                        uint8_t *d_seq, uint8_t *d_seq_qlt, uint8_t *d_seq_alt, size_t seq_cap, uint64_t *d_seq_off /* nwin + 1, or NULL: no compaction */);
+int  bsa_window_cns_batch(bsa_ctx_t *ctx, const bsa_cns_params_t *par,
+                          uint8_t *cols, size_t cols_cap, const bsa_cns_window_t *cwin, size_t nwin, uint32_t max_rows,
+                          uint8_t *cns, uint8_t *qlt, uint8_t *alt, size_t out_cap,
+                          uint32_t *clen, double *score, uint32_t *status,
+                          uint8_t *seq, uint8_t *seq_qlt, uint8_t *seq_alt, size_t seq_cap, uint64_t *seq_off /* nwin + 1, or NULL */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
