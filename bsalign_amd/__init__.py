@@ -101,6 +101,9 @@ CNS_WINDOW_DTYPE = np.dtype([("cols_off", np.uint64), ("idxs_off", np.uint64), (
                              ("nall", np.uint32), ("nseq", np.uint32), ("nmax", np.uint32), ("mlen", np.uint32)])
 # d_status of bsa_window_cns_*: the first clause of the live predicate that a window fails (BSA_CNS_ST_*)
 CNS_ST_OK, CNS_ST_BAD_RECORD, CNS_ST_TOO_DEEP, CNS_ST_NO_ROOM = 0, 1, 2, 3
+# bsa_stitch_t (bsa_window_stitch_*): a window's status, its emitted bases, its units of each kind, the draft bases kept, its words
+STITCH_DTYPE = np.dtype([(n, np.uint32) for n in ("status", "slen", "eq", "x", "ins", "del", "kept", "ncig")])
+STITCH_ST_CALLED, STITCH_ST_DRAFT, STITCH_ST_BAD_RECORD = 0, 1, 2
 DIAGDP_PROB_DTYPE = np.dtype([("seq0", np.uint64), ("seq1", np.uint64), ("mats0", np.uint64, (4,)), ("mats1", np.uint64, (4,)),
                               ("out0", np.uint64), ("out1", np.uint64), ("mlen", np.uint32), ("mbeg", np.uint32), ("mend", np.uint32), ("W", np.uint32)])
 
@@ -228,6 +231,10 @@ def lib():
                                              u8p, u8p, u8p, C.c_size_t, u64p]
             L.bsa_window_cns_batch.argtypes = L.bsa_window_cns_run.argtypes
             L.bsa_window_cns_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_cns_run.argtypes[1:]
+        if hasattr(L, "bsa_window_stitch_run"):
+            L.bsa_window_stitch_run.argtypes = [vp, u8p, C.c_size_t, vp, C.c_size_t, u32p, C.c_uint32, u8p, u8p, u8p, C.c_size_t, u64p, u32p, C.c_size_t, u64p, vp]
+            L.bsa_window_stitch_batch.argtypes = L.bsa_window_stitch_run.argtypes
+            L.bsa_window_stitch_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_stitch_run.argtypes[1:]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -1033,6 +1040,79 @@ class Context:
                         blob[c0:c0 + parts[g].size].reshape(int(w["mlen"]), int(w["nall"]) + 3).copy()))
         empty = np.zeros(0, np.uint8)
         return res, (seq if cap else empty, sq if cap else empty.copy(), sa if cap else empty.copy(), soff)
+
+    def window_stitch_run(self, d_cols, cols_cap, d_cwin, nwin, d_cns_status, min_cov, d_seq, d_seq_qlt, d_seq_alt, seq_cap, d_seq_off, d_cig, cig_cap, d_cig_off, d_rec):
+        """bsa_window_stitch_run on torch tensors (plumbing only), asynchronous on the context's stream: d_cols and d_cwin as window_msa_run wrote and
+        window_cns_run filled them, d_cns_status that run's d_status (or None: every window counts as called).  Window g's stitched bases are
+        d_seq[d_seq_off[g] : d_seq_off[g + 1]] where d_seq_off[g + 1] <= seq_cap (likewise d_seq_qlt and d_seq_alt, either may be None), its = / X / I / D
+        words d_cig[d_cig_off[g] : d_cig_off[g + 1]] where d_cig_off[g + 1] <= cig_cap (32-bit words); d_rec: nwin records of 32 bytes (STITCH_DTYPE).
+        d_seq_off[nwin] and d_cig_off[nwin] are what a complete run needs; None arenas with caps 0 make a count-only run."""
+        size = lambda t: t.numel() * t.element_size()
+        if d_cols is not None and size(d_cols) < cols_cap:
+            raise ValueError("window_stitch_run: d_cols holds fewer than cols_cap bytes")
+        if d_cwin is not None and size(d_cwin) < 40 * nwin:
+            raise ValueError("window_stitch_run: d_cwin holds fewer than nwin records")
+        if d_cns_status is not None and size(d_cns_status) < 4 * nwin:
+            raise ValueError("window_stitch_run: d_cns_status holds fewer than nwin entries")
+        if any(t is not None and size(t) < seq_cap for t in (d_seq, d_seq_qlt, d_seq_alt)):
+            raise ValueError("window_stitch_run: a sequence array holds fewer than seq_cap bytes")
+        if d_cig is not None and size(d_cig) < 4 * cig_cap:
+            raise ValueError("window_stitch_run: d_cig holds fewer than cig_cap words")
+        if any(t is not None and size(t) < 8 * (nwin + 1) for t in (d_seq_off, d_cig_off)):
+            raise ValueError("window_stitch_run: d_seq_off or d_cig_off holds fewer than nwin + 1 offsets")
+        if d_rec is not None and size(d_rec) < 32 * nwin:
+            raise ValueError("window_stitch_run: d_rec holds fewer than nwin records")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_stitch_run(self.h, ptr(d_cols), cols_cap, ptr(d_cwin), nwin, ptr(d_cns_status), int(min_cov), ptr(d_seq), ptr(d_seq_qlt), ptr(d_seq_alt),
+                                              seq_cap, ptr(d_seq_off), ptr(d_cig), cig_cap, ptr(d_cig_off), ptr(d_rec)))
+
+    def window_stitch(self, cns_out, min_cov=1, status=None):
+        """bsa_window_stitch_batch on what Context.window_cns returned -- its list over the windows of (cns, qlt, alt, score, status, cols), cols the
+        window's (mlen, nall + 3) columns with their consensus bytes -- or on a list of (cols, cwin) pairs with `status`, one CNS_ST_* a window (None:
+        every window counts as called): every window's stitched sequence, the consensus where at least min_cov reads cover a column and the draft
+        elsewhere, and its = / X / I / D words against the draft.  Returns (a list over the windows of (seq, qlt, alt, words, rec) with rec the
+        window's STITCH_DTYPE record, (seq, seq_qlt, seq_alt, seq_off, cig, cig_off): the windows' bases, qualities and words one behind the other)."""
+        nwin = len(cns_out)
+        cwin = np.zeros(max(nwin, 1), dtype=CNS_WINDOW_DTYPE)
+        cst = None if (status is None and nwin and len(cns_out[0]) == 2) else np.zeros(max(nwin, 1), np.uint32)
+        parts, cacc = [], 0
+        for g, item in enumerate(cns_out):
+            if len(item) == 2:
+                cols = _np(item[0], np.uint8)
+                if cols.ndim != 2:
+                    cols = cols.reshape(int(item[1]["mlen"]), int(item[1]["nall"]) + 3)
+                if cst is not None:
+                    cst[g] = int(status[g])
+            else:
+                cols = _np(item[5], np.uint8)
+                cst[g] = int(item[4]) if status is None else int(status[g])
+            if cols.ndim != 2 or cols.shape[1] < 4:
+                raise ValueError("window_stitch: a window's columns are an (mlen, nall + 3) array")
+            cwin[g] = (cacc, 0xFFFFFFFFFFFFFFFF, 0, cols.shape[1] - 3, 0, 0, cols.shape[0])
+            parts.append(cols.reshape(-1))
+            cacc += cols.size
+        blob = _np(np.concatenate([np.zeros(0, np.uint8)] + parts), np.uint8).copy()
+        soff, coff = np.zeros(nwin + 1, dtype=np.uint64), np.zeros(nwin + 1, dtype=np.uint64)
+        rec = np.zeros(max(nwin, 1), dtype=STITCH_DTYPE)
+        seq, sq, sa, cig, scap, ccap = None, None, None, None, 0, 0
+        for _ in range(2):                                     # a count-only call says what is needed
+            rc = lib().bsa_window_stitch_batch(self.h, _p(blob) if cacc else None, cacc, _p(cwin), nwin, _p(cst) if cst is not None else None, int(min_cov),
+                                               _p(seq) if scap else None, _p(sq) if scap else None, _p(sa) if scap else None, scap, _p(soff),
+                                               _p(cig) if ccap else None, ccap, _p(coff), _p(rec))
+            if rc != -5 or (int(soff[nwin]) <= scap and int(coff[nwin]) <= ccap):
+                break
+            scap, ccap = int(soff[nwin]), int(coff[nwin])
+            seq, sq, sa = (np.zeros(max(scap, 1), dtype=np.uint8) for _ in range(3))
+            cig = np.zeros(max(ccap, 1), dtype=np.uint32)
+        self._chk(rc)
+        empty = np.zeros(0, np.uint8)
+        seq, sq, sa = (a[:scap] if scap else empty.copy() for a in (seq, sq, sa))
+        cig = cig[:ccap] if ccap else np.zeros(0, np.uint32)
+        res = []
+        for g in range(nwin):
+            a, b, c, d = int(soff[g]), int(soff[g + 1]), int(coff[g]), int(coff[g + 1])
+            res.append((seq[a:b].copy(), sq[a:b].copy(), sa[a:b].copy(), cig[c:d].copy(), rec[g].copy()))
+        return res, (seq, sq, sa, soff, cig, coff)
 
 
 class CnsModel:

@@ -890,6 +890,92 @@ int  bsa_window_cns_batch(bsa_ctx_t *ctx, const bsa_cns_params_t *par,
                           uint32_t *clen, double *score, uint32_t *status,
                           uint8_t *seq, uint8_t *seq_qlt, uint8_t *seq_alt, size_t seq_cap, uint64_t *seq_off /* nwin + 1, or NULL */);
 
+/* bsa_window_stitch_* : the stitched sequence of every window -- the consensus where enough reads cover a column, the draft where they do not -- and its
+ *                    alignment to the draft as = / X / I / D words: what a polisher hands back, and what it changed.  bsa_window_cns_*'s own compaction
+ *                    copies only the columns called as a base, so with vote 0 every column no read covers (a coverage hole, a contig end) and every
+ *                    window that pass refuses loses its draft bases; this pass keeps them, without letting the draft vote anywhere else.
+ *                    A pass over public outputs (bsa_window_stitch.hip): it touches no plan and changes no existing call.
+ * inputs           : d_cols and d_cwin are what bsa_window_msa_run wrote and bsa_window_cns_run then filled with consensus bytes (any arrays of this layout
+ *                    serve); cols_cap is the room of d_cols.  The columns are READ-ONLY here.  d_cns_status is the d_status of bsa_window_cns_run, nwin
+ *                    entries, or NULL: every window counts as called.  That pass's per-window d_cns / d_qlt / d_alt ranges are not used at all: a caller
+ *                    of this pass gives d_seq_off NULL there and skips its compaction.
+ * readable record  : window g's record is READABLE if and only if all of these hold -- idxs_off == ~0;  nall >= 1;  mlen < 2^28 (so that a word's length
+ *                    always fits);  with stride = nall + 3 and mlen * stride formed in 64 bits, cols_off + mlen * stride does not wrap and is <= cols_cap.
+ *                    nseq and nmax are not looked at.  A record that is not readable has status BSA_STITCH_ST_BAD_RECORD, slen 0, no words and all counts
+ *                    0.  This test is the only door to the columns: nothing a caller puts into d_cwin makes the pass read outside [0, cols_cap) of d_cols.
+ * called window    : a readable window is CALLED (BSA_STITCH_ST_CALLED) if d_cns_status is NULL or d_cns_status[g] == 0, otherwise its status is
+ *                    BSA_STITCH_ST_DRAFT.
+ * a column's bytes : for column i with bytes b[0 .. nall + 3): d = b[nall - 1], the draft row -- the LAST row, as bsa_window_msa_run writes it; a
+ *                    precondition, not something the pass checks --; c = b[nall], q = b[nall + 1], a = b[nall + 2], the called symbol and its two
+ *                    qualities; cov = the number of rows r < nall - 1 with b[r] <= 4 (a row is absent at a column where its code is 5 or more).
+ * covered column   : column i is COVERED if and only if the window is called and cov >= min_cov.
+ * what it emits    : a covered column  -- to the sequence: base c with qualities q, a if c <= 3;  as a word unit: none if d > 3 and c > 3, I if d > 3,
+ *                                         D if c > 3, = if c == d, X otherwise;
+ *                    any other column  -- to the sequence: base d with qualities 0, 0 if d <= 3, and `kept` counts it;  as a unit: = if d <= 3, else none.
+ * a window's output: slen = the emitted bases; eq, x, ins, del = the units of each kind (kept is part of eq); the words are the maximal runs of equal kind
+ *                    over the emitted units in column order, len << 4 | op with the ops BSA_CIGAR_I, _D, _EQ, _X; ncig = their number.  Runs are never
+ *                    merged across windows.  With window_gbase numbering a draft's words are the contiguous range d_cig[d_cig_off[first window] ..
+ *                    d_cig_off[first window of the next draft]), its bases lie likewise in d_seq between the two d_seq_off entries.
+ * invariants       : eq + x + ins == slen;  eq + x + del == the number of columns with d <= 3;  the word lengths per op sum to the counts.
+ * and the consensus: with min_cov 0 every column of a called window is covered: d_seq, both quality arrays and d_seq_off of a batch of called windows are
+ *                    then exactly what bsa_window_cns_run's compaction writes.  With vote 0 and min_cov 1 a base is taken from the consensus exactly where
+ *                    at least one read spans the column.  A DRAFT window is the case "no column covered": its draft row, quality 0, one = word.
+ * Example 1        : nall 2, nseq = nmax = 1 (vote 0), mlen 10, the default rates; piece row 5 5 5 3 2 1 5 5 5 5, draft row 0 1 2 3 0 1 2 3 0 1; the host
+ *                    caller leaves the called bytes 4 4 4 3 2 1 4 4 4 4 and the quality bytes 0 0 0 90 90 90 0 0 0 0 (clen 3: seven draft bases are gone).
+ *                      min_cov 0              : seq 3 2 1                 qlt 90 90 90                 words 3D 1= 1X 1= 4D   eq 2  x 1  ins 0  del 7  kept 0
+ *                      min_cov 1              : seq 0 1 2 3 2 1 2 3 0 1   qlt 0 0 0 90 90 90 0 0 0 0   words 4= 1X 5=         eq 9  x 1  ins 0  del 0  kept 7
+ *                      min_cov 2 or not called: seq 0 1 2 3 0 1 2 3 0 1   qlt all 0                    words 10=              eq 10 x 0  ins 0  del 0  kept 10
+ *                    min_cov 0 is what the consensus pass packs.
+ * Example 2        : the 12 columns of the bsa_window_cns_* example with vote 1 (nall 3; coverage 1 1 2 2 2 2 2 2 2 2 1 1) --
+ *                      min_cov 0 or 1 : seq 0 1 2 3 2 0 1 2 3 0 1   qlt 90 90 90 90 2 10 90 90 90 90 90   words 4= 1I 6=   ins 1  kept 0
+ *                      min_cov 2      : the same bases              qlt 0 0 90 90 2 10 90 90 90 0 0       words 4= 1I 6=   ins 1  kept 4
+ *                      min_cov 3      : seq 0 1 2 3 0 1 2 3 0 1     qlt all 0                             words 10=        ins 0  kept 10
+ *                    Column 5 is an insertion column called a gap: it emits nothing.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (a run that has to grow it may synchronise once; BSA_E_NOMEM when it cannot): 44 bytes a window and the scans' temporaries,
+ *                    and 4 bytes -- the column's word -- for each of min(cols_cap / 4, max(seq_cap, cig_cap)) columns.  The windows whose columns fit that
+ *                    many words (counted through the batch) have their columns read ONCE; the others are read a second time when the arenas are filled.
+ *                    Disjoint windows sum to at most cols_cap / 4 columns, so caps of the sum of mlen read every column once.  The output is a function
+ *                    of the inputs alone; a run leaves nothing behind that a later run reads.
+ * arenas           : the house contract with the window as the unit and two arenas, d_seq (with d_seq_qlt, d_seq_alt; either may be NULL) and d_cig, that
+ *                    are independent of each other.  For ANY seq_cap and cig_cap, 0 with a non-NULL arena and a NULL arena with cap 0 (count-only) included:
+ *                      - all nwin + 1 entries of d_seq_off and of d_cig_off and all nwin records of d_rec are written and are those of a run with large
+ *                        arenas; d_seq_off[nwin] and d_cig_off[nwin] say what a complete run needs;
+ *                      - window g's bases (and the qualities that are given) are written, whole, if and only if d_seq_off[g + 1] <= seq_cap;
+ *                      - window g's words are written, whole, if and only if d_cig_off[g + 1] <= cig_cap;
+ *                      - no byte of a window that is not written is touched, nothing at or above a cap is touched, no arena is used as scratch.
+ *                    The sum of mlen suffices for both caps: every base and every word takes at least one column.
+ * _batch           : all pointers are HOST memory.  It uploads the columns, the records, the statuses and the arenas as they are, runs, downloads the offsets
+ *                    and records FIRST and synchronises: a cap too small is BSA_E_CIGAR_CAP there, with both totals in seq_off[nwin] and cig_off[nwin] and
+ *                    the arenas untouched.  Then seq_off[nwin] bytes of the sequence arrays and cig_off[nwin] words come down.
+ * errors (both)    : a NULL ctx, d_seq_off or d_cig_off; with nwin > 0 a NULL d_cwin or d_rec; a cap without its arena (cols_cap without d_cols, seq_cap
+ *                    without d_seq, cig_cap without d_cig); a quality array without d_seq; nwin above 0xFFFFFFF0: BSA_E_ARG.  nwin == 0 writes
+ *                    d_seq_off[0] = d_cig_off[0] = 0 and nothing else.
+ * Example          : behind the bsa_window_msa_run of that block's example, the consensus without its compaction, then the stitch --
+ *                      bsa_window_cns_run(ctx, model, d_cols, cols_cap, d_cwin, nwin, 40, d_cns, d_qlt, d_alt, out_cap, d_clen, NULL, d_status,
+ *                                         NULL, NULL, NULL, 0, NULL);
+ *                      bsa_window_stitch_run(ctx, d_cols, cols_cap, d_cwin, nwin, d_status, 1, d_seq, d_seq_qlt, NULL, out_cap, d_seq_off,
+ *                                            d_cig, out_cap, d_cig_off, d_rec); bsa_ctx_sync(ctx);
+ *                    then draft j's polished bases are d_seq[d_seq_off[first window of j] .. d_seq_off[first window of j + 1]) and its differences to
+ *                    the draft d_cig over the same two windows of d_cig_off; the sums of d_rec say whether another round is worth it. */
+#define BSA_STITCH_ST_CALLED     0u   /* consensus used in every covered column */
+#define BSA_STITCH_ST_DRAFT      1u   /* the consensus pass did not run this window: the draft row is kept whole */
+#define BSA_STITCH_ST_BAD_RECORD 2u   /* the record's columns are not readable: the window contributes nothing */
+typedef struct { uint32_t status, slen, eq, x, ins, del, kept, ncig; } bsa_stitch_t;   /* 32 bytes, one a window */
+int  bsa_window_stitch_run(bsa_ctx_t *ctx,
+                           const uint8_t *d_cols, size_t cols_cap, const bsa_cns_window_t *d_cwin, size_t nwin,
+                           const uint32_t *d_cns_status /* nwin, what bsa_window_cns_run wrote; NULL: every window counts as called */,
+                           uint32_t min_cov,
+                           uint8_t *d_seq, uint8_t *d_seq_qlt, uint8_t *d_seq_alt, size_t seq_cap, uint64_t *d_seq_off /* nwin + 1 */,
+                           uint32_t *d_cig, size_t cig_cap, uint64_t *d_cig_off /* nwin + 1 */,
+                           bsa_stitch_t *d_rec /* nwin */);
+int  bsa_window_stitch_batch(bsa_ctx_t *ctx,
+                             const uint8_t *cols, size_t cols_cap, const bsa_cns_window_t *cwin, size_t nwin,
+                             const uint32_t *cns_status /* nwin, or NULL */, uint32_t min_cov,
+                             uint8_t *seq, uint8_t *seq_qlt, uint8_t *seq_alt, size_t seq_cap, uint64_t *seq_off /* nwin + 1 */,
+                             uint32_t *cig, size_t cig_cap, uint64_t *cig_off /* nwin + 1 */,
+                             bsa_stitch_t *rec /* nwin */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
