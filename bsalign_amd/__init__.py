@@ -88,6 +88,13 @@ class KmerParams(C.Structure):
     _fields_ = [("ksz", C.c_uint32), ("threads", C.c_uint32)]
 
 
+class SELECT_PARAMS(C.Structure):
+    """bsa_select_params_t (bsa_window_select_*): at most max_depth pieces a window (0: no cap), a piece spans min_span target columns or more, its
+    pair has mat * ident_den >= ident_num * aln (ident_den 0: no test), seed decides among pieces of equal span"""
+    _fields_ = [("max_depth", C.c_uint32), ("min_span", C.c_uint32), ("ident_num", C.c_uint32), ("ident_den", C.c_uint32), ("seed", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
 RESULT_DTYPE = np.dtype([(n, np.int32) for n in ("score", "qb", "qe", "tb", "te", "mat", "mis", "ins", "del", "aln")])
 # bsa_piece_t (bsa_window_pieces_*): a read's piece in one window of the draft
 PIECE_DTYPE = np.dtype([("pair", np.uint32), ("q_first", np.uint32), ("len", np.uint32), ("t_first", np.uint32), ("t_last", np.uint32), ("reserved", np.uint32),
@@ -212,6 +219,10 @@ def lib():
                                                 vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
             L.bsa_window_pieces_batch.argtypes = [vp, u8p, C.c_size_t, u64p, u32p, vp, u64p, C.c_size_t, C.c_uint32, u64p, C.c_size_t, C.c_uint32,
                                                   vp, C.c_size_t, u64p, u8p, C.c_size_t, u64p]
+        if hasattr(L, "bsa_window_select_run"):
+            L.bsa_window_select_run.argtypes = [vp, vp, u64p, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(SELECT_PARAMS), vp, C.c_size_t, u64p, u32p, u32p]
+            L.bsa_window_select_batch.argtypes = L.bsa_window_select_run.argtypes
+            L.bsa_window_select_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_select_run.argtypes[1:]
         if hasattr(L, "bsa_piece_cigars_run"):
             L.bsa_piece_cigars_bound.argtypes = [u64p, C.c_size_t, C.c_size_t]
             L.bsa_piece_cigars_bound.restype = C.c_uint64
@@ -854,6 +865,62 @@ class Context:
         self._chk(lib().bsa_window_pieces_run(self.h, ptr(d_seqs), ptr(d_qoff), ptr(d_qlen), ptr(d_win), ptr(d_win_off), n, int(window), ptr(d_gbase),
                                               nwin, int(flags), ptr(d_piece), piece_cap, ptr(d_piece_off), ptr(d_bases), bases_cap, ptr(d_base_off)))
 
+    def window_select_run(self, d_piece, d_piece_off, nwin, piece_cap, d_out, n, par, d_sel, sel_cap, d_sel_off, d_sel_src=None, d_ncand=None):
+        """bsa_window_select_run on torch tensors (plumbing only), asynchronous on the context's stream: d_piece, d_piece_off as window_pieces_run
+        left them, with room for piece_cap records; d_out the aligner's n records, or None (par.ident_den is then 0); par a SELECT_PARAMS, read at
+        the call.  d_sel: room for sel_cap records of 32 bytes, or None with sel_cap 0 for a count-only run; d_sel_off: nwin + 1 64-bit words;
+        d_sel_src: sel_cap 32-bit words or None; d_ncand: nwin 32-bit words or None.  Window g's selected records are
+        d_sel[d_sel_off[g] : d_sel_off[g + 1]] where d_sel_off[g + 1] <= sel_cap; d_sel_off[nwin] is what a complete run needs."""
+        size = lambda t: t.numel() * t.element_size()
+        if d_piece is not None and size(d_piece) < 32 * piece_cap:
+            raise ValueError("window_select_run: d_piece holds fewer than piece_cap records")
+        if d_piece_off is not None and size(d_piece_off) < 8 * (nwin + 1):
+            raise ValueError("window_select_run: d_piece_off holds fewer than nwin + 1 offsets")
+        if d_out is not None and size(d_out) < 40 * n:
+            raise ValueError("window_select_run: d_out holds fewer than n records")
+        if d_sel is not None and size(d_sel) < 32 * sel_cap:
+            raise ValueError("window_select_run: d_sel holds fewer than sel_cap records")
+        if d_sel_off is not None and size(d_sel_off) < 8 * (nwin + 1):
+            raise ValueError("window_select_run: d_sel_off holds fewer than nwin + 1 offsets")
+        if d_sel_src is not None and size(d_sel_src) < 4 * sel_cap:
+            raise ValueError("window_select_run: d_sel_src holds fewer than sel_cap entries")
+        if d_ncand is not None and size(d_ncand) < 4 * nwin:
+            raise ValueError("window_select_run: d_ncand holds fewer than nwin entries")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_select_run(self.h, ptr(d_piece), ptr(d_piece_off), nwin, piece_cap, ptr(d_out), n, C.byref(par), ptr(d_sel), sel_cap,
+                                              ptr(d_sel_off), ptr(d_sel_src), ptr(d_ncand)))
+
+    def window_select(self, windows_out, max_depth=0, min_span=0, min_ident=None, results=None, seed=0):
+        """bsa_window_select_batch on what Context.window_pieces returned (the list over the windows of (pieces, codes)): the pieces that take part.
+        A piece needs min_span target columns or more; with min_ident = (num, den) and results, the aligner's record array, its pair needs
+        mat * den >= num * aln; of the candidates left at most max_depth a window are kept (0: all), the widest, ties by mix32(pair ^ seed) and then
+        by the index.  Returns (selected, src): selected a list over the windows of (pieces, codes) in the shape Context.piece_cigars and
+        Context.window_msa take, src a list of index arrays, src[g][i] the index in windows_out[g] of selected[g]'s piece i."""
+        nwin = len(windows_out)
+        piece = _np(np.concatenate([np.zeros(0, PIECE_DTYPE)] + [_np(ps, PIECE_DTYPE) for ps, _ in windows_out]), PIECE_DTYPE)
+        npiece = len(piece)
+        poff = np.zeros(nwin + 1, dtype=np.uint64)
+        poff[1:] = np.cumsum([len(ps) for ps, _ in windows_out], dtype=np.uint64)
+        par = SELECT_PARAMS(int(max_depth), int(min_span), 0, 0, int(seed))
+        out = None
+        if min_ident is not None:
+            if results is None:
+                raise ValueError("window_select: min_ident needs results")
+            par.ident_num, par.ident_den = int(min_ident[0]), int(min_ident[1])
+            out = _np(results, RESULT_DTYPE)
+        sel = np.zeros(max(npiece, 1), dtype=PIECE_DTYPE)
+        src = np.zeros(max(npiece, 1), dtype=np.uint32)
+        soff = np.zeros(nwin + 1, dtype=np.uint64)
+        self._chk(lib().bsa_window_select_batch(self.h, _p(piece) if npiece else None, _p(poff), nwin, npiece, _p(out) if out is not None else None,
+                                                len(out) if out is not None else 0, C.byref(par), _p(sel), npiece, _p(soff), _p(src), None))
+        selected, idx = [], []
+        for g, (ps, cs) in enumerate(windows_out):
+            a, b = int(soff[g]), int(soff[g + 1])
+            j = src[a:b].astype(np.int64) - int(poff[g])
+            selected.append((sel[a:b].copy(), [cs[int(x)] for x in j]))
+            idx.append(j)
+        return selected, idx
+
     def piece_cigars(self, results, cigars, windows_out):
         """bsa_piece_cigars_batch on what align_batch / edit_batch returned (the record array and the list of CIGAR arrays) and what
         Context.window_pieces made of them (the list over the windows of (pieces, codes)): every piece's own CIGAR words, the stretch of its pair's
@@ -1136,6 +1203,16 @@ class CnsModel:
             self.close()
         except Exception:
             pass
+
+
+def mix32(x):
+    """the 32-bit finaliser bsa_window_select_* hashes a pair with (include/bsalign_hip.h)"""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = x * 0x85EBCA6B & 0xFFFFFFFF
+    x ^= x >> 13
+    x = x * 0xC2B2AE35 & 0xFFFFFFFF
+    return x ^ x >> 16
 
 
 def window_gbase(target_id, target_len, window):

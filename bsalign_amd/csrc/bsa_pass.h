@@ -1,5 +1,5 @@
 // bsa_pass.h -- what the passes over an aligner's outputs share (bsa_cigar_eqx.hip, bsa_band_margin.hip, bsa_cigar_windows.hip, bsa_window_pieces.hip,
-// bsa_piece_cigars.hip): the context's internal entry points and the exclusive scan, declared once (bsa_api.hip and bsa_scan.hip include this header
+// bsa_window_select.hip, bsa_piece_cigars.hip, bsa_window_msa.hip, bsa_window_cns.hip, bsa_window_stitch.hip): the context's internal entry points and the exclusive scan, declared once (bsa_api.hip and bsa_scan.hip include this header
 // too, so the compiler checks declaration against definition), wave prefix sums, the rules of a CIGAR word, and the host arithmetic of their launchers.
 #pragma once
 #include "bsa_common.h"

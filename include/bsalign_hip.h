@@ -642,6 +642,88 @@ int      bsa_window_pieces_batch(bsa_ctx_t *ctx, const uint8_t *seqs, size_t seq
                                  bsa_piece_t *piece, size_t piece_cap, uint64_t *piece_off,
                                  uint8_t *bases, size_t bases_cap, uint64_t *base_off);
 
+/* bsa_window_select_* : which of a window's pieces take part -- the depth knob and the read filter of a windowed polisher.  bsa_window_pieces_* makes every piece
+ *                    that crosses a window a row of its MSA; the two passes that cost the most (bsa_window_msa_*, bsa_window_cns_*) grow linearly with that
+ *                    depth, one deep window (a collapsed repeat) holds a whole batch up, and a badly aligned read votes like any other.  This pass drops the
+ *                    pieces that are too short and those of pairs whose identity is too low, and keeps at most max_depth of the rest, in front of any
+ *                    expensive work.  A pass over public outputs (bsa_window_select.hip): it touches no plan and changes no existing call.
+ * inputs           : d_piece, d_piece_off (nwin + 1) are what bsa_window_pieces_run left, piece_cap the room of d_piece; d_out (n records, or NULL) what the
+ *                    aligner left for the pairs the pieces speak of.  d_sel must not overlap d_piece.
+ * windows          : window g's pieces are piece[piece_off[g] .. piece_off[g + 1]).  A window with piece_off[g + 1] > piece_cap or piece_off[g + 1] <
+ *                    piece_off[g] has no pieces (the rule of bsa_window_msa_* for depth 0).  This test is the only door to the piece records: nothing the
+ *                    caller puts into the offsets makes the pass read outside piece_cap records.
+ * candidates       : piece j of window g is a CANDIDATE if and only if
+ *                      t_first <= t_last  and  len >= 1;
+ *                      with sp = t_last - t_first (which cannot wrap):  min_span <= 1  or  sp >= min_span - 1;
+ *                      and, if ident_den != 0 (the identity test; d_out == NULL is then BSA_E_ARG):  pair < n,  and with mat and aln read as int32 from
+ *                      d_out[pair]:  aln > 0,  mat >= 0  and  (uint64)mat * ident_den >= (uint64)ident_num * (uint64)aln  (neither product can wrap).
+ *                    Without the identity test `pair` is used in the hash below only, never as an index, and d_out is not read.
+ * order            : candidate i is BETTER than candidate j if its sp is larger; or sp is equal and its h is smaller, h = mix32(pair ^ seed) with
+ *                      mix32(x):  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16;   (32-bit arithmetic)
+ *                    or both are equal and i < j.  The hash is one of the pair, not of the piece: a read that wins a tie wins it in every window where it
+ *                    ties, so neighbouring windows tend to keep the same reads.  (A rule by a piece's own indel balance would prefer the reads that agree
+ *                    with the draft's length -- the one bias a polisher must not have.)
+ * selected         : with C candidates, all of them if max_depth == 0 or C <= max_depth, otherwise the max_depth best.  d_ncand[g] = C.
+ * output           : window g's selected records, copied verbatim -- all 32 bytes, base_off and reserved included -- in ascending j, are
+ *                    sel[sel_off[g] .. sel_off[g + 1]); sel_src[i] is the index j in d_piece that record i came from; sel_off is the exclusive sum, in 64
+ *                    bits, of the selected counts.  The output is a function of the inputs alone.
+ * downstream       : d_sel and d_sel_off take the place of d_piece and d_piece_off in bsa_piece_cigars_run (d_npiece = d_sel_off + nwin, piece_cap = sel_cap)
+ *                    and in bsa_window_msa_run; d_bases and bases_cap stay those bsa_window_pieces_run wrote -- the records' base_off are absolute and are
+ *                    left alone (the bases of the dropped pieces stay where they are, unused).  With max_depth 0, min_span 0 and no identity test the
+ *                    selected records of well-formed windows are the input records, and d_sel_off is d_piece_off rebased.
+ * Example          : one window, seed 0, min_span 6, no identity test; the pieces as (pair, t_first..t_last):
+ *                      j0 (0, 0..9)   j1 (1, 2..9)   j2 (2, 0..9)   j3 (3, 0..4)   j4 (4, 0..9)   j5 (5, 1..9)
+ *                    j3 spans 5 columns and is no candidate: C = 5.  mix32 of the pairs 0, 2, 4 is 0x00000000, 0x30F4C306, 0x249CB285, so among the three
+ *                    pieces with sp 9 the order is j0, j4, j2.  Selected, by max_depth:
+ *                      0: {0, 1, 2, 4, 5}   1: {0}   2: {0, 4}   3: {0, 2, 4}   4: {0, 2, 4, 5}  (j5 with sp 8 goes before j1 with sp 7)
+ *                    With seed 1, max_depth 2 gives {0, 2}.  Identity: with ident_num / ident_den = 4 / 5 a pair with (mat, aln) = (80, 100) or (8, 10)
+ *                    passes, (79, 100) fails, (0, 0) fails.
+ * arena            : the contract of bsa_window_pieces_run with one arena and the window as the unit.  For ANY sel_cap, 0 with a non-NULL d_sel and a NULL
+ *                    d_sel with cap 0 (a count-only run) included:
+ *                      - all nwin + 1 entries of d_sel_off are those of a run with a large arena and every run writes every one of them, and all nwin
+ *                        entries of d_ncand if it is given;
+ *                      - d_sel_off[nwin] is the number of records a complete run needs (piece_cap always suffices);
+ *                      - window g's records are written, whole, if and only if d_sel_off[g + 1] <= sel_cap, with its d_sel_src entries if that array is given;
+ *                      - a window that is not written has no byte of its range touched; nothing at or above sel_cap, nor at or above the total, is touched;
+ *                      - the caller's arena is never used as scratch.
+ *                    A run leaves nothing behind that a later run reads.
+ * _run             : DEVICE pointers, `par` HOST memory that is read at the call; asynchronous on the context stream; no host/device copy, no synchronisation
+ *                    -- except that it may grow the context's scratch (16 bytes a window and the scan's temporaries; a run that has to grow it may
+ *                    synchronise once; BSA_E_NOMEM when it cannot).
+ * _batch           : all pointers are HOST memory: uploads the piece_cap records, the offsets as they are (a piece_off that decreases is handled window by
+ *                    window as stated above: it is no error) and, for the identity test, the n records; counts, downloads sel_off and ncand FIRST and
+ *                    synchronises: sel_cap too small is BSA_E_CIGAR_CAP there, sel_off[nwin] = the records needed, sel and sel_src untouched.  Then the
+ *                    selected records come down.
+ * errors (both)    : a NULL ctx, par or d_sel_off; a NULL d_piece_off with nwin > 0; piece_cap without d_piece; sel_cap without d_sel; d_sel_src without
+ *                    d_sel; ident_den != 0 without d_out; non-zero reserved; nwin, n, piece_cap or sel_cap above 0xFFFFFFF0: BSA_E_ARG.  nwin == 0 writes
+ *                    d_sel_off[0] = 0 and nothing else.
+ * Example          : a polisher's step on resident reads, at most 40 pieces a window of pairs that match in 7 of 10 columns or more --
+ *                      bsa_window_pieces_run(ctx, d_seqs, d_qoff, d_qlen, d_win, d_win_off, n, 500, d_gbase, nwin, flags, d_piece, cap, d_piece_off, d_bases, bcap, ...);
+ *                      bsa_select_params_t sp = { 40, 0, 7, 10, 0, { 0, 0, 0 } };
+ *                      bsa_window_select_run(ctx, d_piece, d_piece_off, nwin, cap, d_out, n, &sp, d_sel, cap, d_sel_off, NULL, NULL);
+ *                      bsa_piece_cigars_run(ctx, d_out, d_cigar, d_cigar_off, n, d_sel, d_sel_off + nwin, cap, d_pcig, cigar_cap + cap, d_pcig_off, NULL);
+ *                      bsa_window_msa_run(ctx, d_sel, d_sel_off, nwin, cap, d_bases, bcap, d_pcig, ...);
+ *                    and on as without the pass. */
+typedef struct {
+	uint32_t max_depth;             /* at most this many pieces a window; 0: no cap */
+	uint32_t min_span;              /* a piece needs t_last - t_first + 1 >= min_span target columns; 0 and 1: no test */
+	uint32_t ident_num, ident_den;  /* with d_out: the pair needs mat * ident_den >= ident_num * aln; ident_den 0: no test */
+	uint32_t seed;                  /* decides among pieces of equal span */
+	uint32_t reserved[3];           /* 0 */
+} bsa_select_params_t;              /* 32 bytes */
+int      bsa_window_select_run(bsa_ctx_t *ctx,
+                               const bsa_piece_t *d_piece, const uint64_t *d_piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                               const bsa_result_t *d_out /* n, or NULL: no identity test */, size_t n,
+                               const bsa_select_params_t *par /* HOST */,
+                               bsa_piece_t *d_sel, size_t sel_cap, uint64_t *d_sel_off /* nwin + 1 */,
+                               uint32_t *d_sel_src /* sel_cap, may be NULL */, uint32_t *d_ncand /* nwin, may be NULL */);
+int      bsa_window_select_batch(bsa_ctx_t *ctx,
+                                 const bsa_piece_t *piece, const uint64_t *piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                                 const bsa_result_t *out /* n, or NULL */, size_t n,
+                                 const bsa_select_params_t *par,
+                                 bsa_piece_t *sel, size_t sel_cap, uint64_t *sel_off /* nwin + 1 */,
+                                 uint32_t *sel_src /* sel_cap, may be NULL */, uint32_t *ncand /* nwin, may be NULL */);
+
 /* bsa_piece_cigars_* : every piece's own CIGAR words -- how the piece aligns to its window of the draft, which is what the POA's band placement takes as a
  *                    read's guide (bsa_pog_guide_t::sam, bsalign_poa.h).  bsa_window_pieces_* leaves, for every window, the reads' pieces and their codes;
  *                    the piece's alignment against the draft already exists: it is the stretch of its pair's CIGAR from the piece's first to its last
