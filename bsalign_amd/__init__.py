@@ -111,6 +111,19 @@ CNS_ST_OK, CNS_ST_BAD_RECORD, CNS_ST_TOO_DEEP, CNS_ST_NO_ROOM = 0, 1, 2, 3
 # bsa_stitch_t (bsa_window_stitch_*): a window's status, its emitted bases, its units of each kind, the draft bases kept, its words
 STITCH_DTYPE = np.dtype([(n, np.uint32) for n in ("status", "slen", "eq", "x", "ins", "del", "kept", "ncig")])
 STITCH_ST_CALLED, STITCH_ST_DRAFT, STITCH_ST_BAD_RECORD = 0, 1, 2
+# bsa_snv_t (bsa_msa_call_snvs, bsa_window_snv_*): a call's column, its position in the consensus and in the last row (the draft), its quality, the
+# column's coverage and the two alleles' counts and bases; bsa_snv_window_t: a window's status, calls, sites and estimated error rate;
+# bsa_snv_params_t with the reference's defaults
+SNV_DTYPE = np.dtype([("mpos", np.uint32), ("cpos", np.uint32), ("lpos", np.uint32), ("qual", np.uint32), ("covn", np.uint16), ("refn", np.uint16),
+                      ("altn", np.uint16), ("refb", np.uint8), ("altb", np.uint8)])
+SNV_WINDOW_DTYPE = np.dtype([("status", np.uint32), ("nsnv", np.uint32), ("nsites", np.uint32), ("pexp", np.float32)])
+SNV_PARAMS = np.dtype([("min_varcnt", np.int32), ("min_covfrq", np.float32), ("min_snvqlt", np.uint32), ("skip_first_row", np.uint32)])
+SNV_ST_OK, SNV_ST_BAD_RECORD, SNV_ST_TOO_DEEP, SNV_ST_TOO_LONG, SNV_ST_NOT_CALLED = 0, 1, 2, 3, 4
+
+
+def snv_params(min_varcnt=3, min_covfrq=0.5, min_snvqlt=5, skip_first_row=0):
+    """a bsa_snv_params_t as a SNV_PARAMS array of one record"""
+    return np.array([(min_varcnt, min_covfrq, min_snvqlt, skip_first_row)], dtype=SNV_PARAMS)
 DIAGDP_PROB_DTYPE = np.dtype([("seq0", np.uint64), ("seq1", np.uint64), ("mats0", np.uint64, (4,)), ("mats1", np.uint64, (4,)),
                               ("out0", np.uint64), ("out1", np.uint64), ("mlen", np.uint32), ("mbeg", np.uint32), ("mend", np.uint32), ("W", np.uint32)])
 
@@ -246,6 +259,12 @@ def lib():
             L.bsa_window_stitch_run.argtypes = [vp, u8p, C.c_size_t, vp, C.c_size_t, u32p, C.c_uint32, u8p, u8p, u8p, C.c_size_t, u64p, u32p, C.c_size_t, u64p, vp]
             L.bsa_window_stitch_batch.argtypes = L.bsa_window_stitch_run.argtypes
             L.bsa_window_stitch_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_stitch_run.argtypes[1:]
+        L.bsa_snv_model_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+        L.bsa_snv_model_destroy.argtypes = [vp]
+        L.bsa_snv_model_destroy.restype = None
+        L.bsa_window_snv_run.argtypes = [vp, vp, u8p, C.c_size_t, vp, C.c_size_t, u32p, vp, vp, C.c_size_t, u64p, vp]
+        L.bsa_window_snv_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_snv_run.argtypes[1:]
+        L.bsa_window_snv_batch.argtypes = [vp, C.c_uint32, u8p, C.c_size_t, vp, C.c_size_t, u32p, vp, vp, C.c_size_t, u64p, vp]
         L.bsa_rows_block_bytes.argtypes = [C.c_uint32, C.c_int8, C.c_int8, C.c_int8, C.c_int8]
         L.bsa_rows_block_bytes.restype = C.c_size_t
         L.bsa_rows_run.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(RowsParams)]
@@ -1180,6 +1199,104 @@ class Context:
             a, b, c, d = int(soff[g]), int(soff[g + 1]), int(coff[g]), int(coff[g + 1])
             res.append((seq[a:b].copy(), sq[a:b].copy(), sa[a:b].copy(), cig[c:d].copy(), rec[g].copy()))
         return res, (seq, sq, sa, soff, cig, coff)
+
+    def snv_model(self, max_rows):
+        """bsa_snv_model_create: the SNV caller's tables for windows of up to max_rows voting rows (at most 1000) resident on the device, for
+        window_snv_run; closed with the context (or by its own close())."""
+        m = SnvModel(self, max_rows)
+        self._models.append(m)
+        return m
+
+    def window_snv_run(self, model, d_cols, cols_cap, d_cwin, nwin, d_cns_status, par, d_snv, snv_cap, d_snv_off, d_rec):
+        """bsa_window_snv_run on torch tensors (plumbing only), asynchronous on the context's stream: d_cols and d_cwin as window_msa_run wrote and
+        window_cns_run filled them, d_cns_status that run's d_status (or None: every window counts), par a SNV_PARAMS record (snv_params()).  Window
+        g's calls are the 24-byte records (SNV_DTYPE) d_snv[d_snv_off[g] : d_snv_off[g + 1]] where d_snv_off[g + 1] <= snv_cap (records);
+        d_snv_off[nwin] is what a complete run needs; d_rec: nwin records of 16 bytes (SNV_WINDOW_DTYPE).  A None arena with cap 0 only counts."""
+        size = lambda t: t.numel() * t.element_size()
+        if d_cols is not None and size(d_cols) < cols_cap:
+            raise ValueError("window_snv_run: d_cols holds fewer than cols_cap bytes")
+        if d_cwin is not None and size(d_cwin) < 40 * nwin:
+            raise ValueError("window_snv_run: d_cwin holds fewer than nwin records")
+        if d_cns_status is not None and size(d_cns_status) < 4 * nwin:
+            raise ValueError("window_snv_run: d_cns_status holds fewer than nwin entries")
+        if d_snv is not None and size(d_snv) < 24 * snv_cap:
+            raise ValueError("window_snv_run: d_snv holds fewer than snv_cap records")
+        if d_snv_off is not None and size(d_snv_off) < 8 * (nwin + 1):
+            raise ValueError("window_snv_run: d_snv_off holds fewer than nwin + 1 offsets")
+        if d_rec is not None and size(d_rec) < 16 * nwin:
+            raise ValueError("window_snv_run: d_rec holds fewer than nwin records")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        par = None if par is None else np.ascontiguousarray(par, dtype=SNV_PARAMS).reshape(-1)[:1]
+        self._chk(lib().bsa_window_snv_run(self.h, model.h if model is not None else None, ptr(d_cols), cols_cap, ptr(d_cwin), nwin, ptr(d_cns_status),
+                                           _p(par) if par is not None else None, ptr(d_snv), snv_cap, ptr(d_snv_off), ptr(d_rec)))
+
+    def window_snv(self, cns_out, par=None, max_rows=None, status=None, nseq=None):
+        """bsa_window_snv_batch on what Context.window_cns returned -- its list over the windows of (cns, qlt, alt, score, status, cols) -- or on a list
+        of (cols, cwin) pairs with `status`, one CNS_ST_* a window (None: every window counts).  The voting rows of window g are nseq[g] (an int serves
+        all windows), by default the record's nseq of a (cols, cwin) pair and every row but the last -- the draft -- of a window_cns item.  par: a
+        SNV_PARAMS record (default: snv_params()); max_rows: the depth of the model (default: the largest nseq).  Returns (a list over the windows of
+        (snv, rec): the window's SNV_DTYPE records and its SNV_WINDOW_DTYPE record, (snv, snv_off) of the call)."""
+        nwin = len(cns_out)
+        par = snv_params() if par is None else np.ascontiguousarray(par, dtype=SNV_PARAMS).reshape(-1)[:1]
+        cwin = np.zeros(max(nwin, 1), dtype=CNS_WINDOW_DTYPE)
+        cst = None if (status is None and nwin and len(cns_out[0]) == 2) else np.zeros(max(nwin, 1), np.uint32)
+        parts, cacc = [], 0
+        for g, item in enumerate(cns_out):
+            if len(item) == 2:
+                cols = _np(item[0], np.uint8)
+                if cols.ndim != 2:
+                    cols = cols.reshape(int(item[1]["mlen"]), int(item[1]["nall"]) + 3)
+                rows = int(item[1]["nseq"])
+                if cst is not None:
+                    cst[g] = int(status[g])
+            else:
+                cols = _np(item[5], np.uint8)
+                rows = cols.shape[1] - 4 if cols.ndim == 2 else 0
+                cst[g] = int(item[4]) if status is None else int(status[g])
+            if cols.ndim != 2 or cols.shape[1] < 4:
+                raise ValueError("window_snv: a window's columns are an (mlen, nall + 3) array")
+            if nseq is not None:
+                rows = int(nseq) if np.isscalar(nseq) else int(nseq[g])
+            cwin[g] = (cacc, 0xFFFFFFFFFFFFFFFF, 0, cols.shape[1] - 3, rows, rows, cols.shape[0])
+            parts.append(cols.reshape(-1))
+            cacc += cols.size
+        blob = _np(np.concatenate([np.zeros(0, np.uint8)] + parts), np.uint8).copy()
+        if max_rows is None:
+            max_rows = int(cwin["nseq"][:nwin].max()) if nwin else 0
+        off = np.zeros(nwin + 1, dtype=np.uint64)
+        rec = np.zeros(max(nwin, 1), dtype=SNV_WINDOW_DTYPE)
+        snv, cap = None, 0
+        for _ in range(2):                                     # a count-only call says what is needed
+            rc = lib().bsa_window_snv_batch(self.h, int(max_rows), _p(blob) if cacc else None, cacc, _p(cwin), nwin, _p(cst) if cst is not None else None, _p(par),
+                                            _p(snv) if cap else None, cap, _p(off), _p(rec))
+            if rc != -5 or int(off[nwin]) <= cap:
+                break
+            cap = int(off[nwin])
+            snv = np.zeros(cap, dtype=SNV_DTYPE)
+        self._chk(rc)
+        snv = snv[:cap] if cap else np.zeros(0, SNV_DTYPE)
+        return [(snv[int(off[g]):int(off[g + 1])].copy(), rec[g].copy()) for g in range(nwin)], (snv, off)
+
+
+class SnvModel:
+    """the SNV caller's tables resident on the device -- bsa_snv_model_create / bsa_snv_model_destroy (Context.snv_model)"""
+
+    def __init__(self, ctx, max_rows):
+        h = C.c_void_p()
+        ctx._chk(lib().bsa_snv_model_create(ctx.h, int(max_rows), C.byref(h)))
+        self.h = h
+        self.max_rows = int(max_rows)
+
+    def close(self):
+        if self.h:
+            lib().bsa_snv_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CnsModel:

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import LIB_PATH, BsaError, CNS_WINDOW_DTYPE      # noqa: F401 (bsa_cns_window_t, defined with the other records)
+from . import SNV_DTYPE, SNV_PARAMS, snv_params
 
 _lib = None
 E_NOMEM = -3
@@ -21,6 +22,10 @@ def lib():
         L.bsa_msa_consensus.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32), vp, vp]
         L.bsa_msa_text.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_char_p,
                                    C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.bsa_msa_call_snvs.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_uint32)]
+        L.bsa_msa_snv_text.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_size_t, C.c_char_p, vp, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -133,3 +138,37 @@ def call_consensus_batch(ctx, windows, par7):
         o = int(win[k]["out_off"]); m = int(clen[k]); c0 = int(win[k]["cols_off"])
         out.append((cns[o:o + m].copy(), qlt[o:o + m].copy(), alt[o:o + m].copy(), float(score[k]), blob[c0:c0 + np.asarray(cols).size].copy()))
     return out
+
+
+def call_snvs(cols, nall, nseq, par=None, idxs=None, mlen=None):
+    """host form (bsa_msa_call_snvs = call_snvs_bspoa): cols the (mlen, nall + 3) columns with their consensus bytes (read-only), rows 0 .. nseq - 1
+    vote, par a SNV_PARAMS record (default: snv_params(): 3, 0.5, 5, 0) -> (snv: SNV_DTYPE records in column order, pexp: the estimated error rate,
+    nsites: the columns that entered the estimate)"""
+    cols = np.ascontiguousarray(cols, dtype=np.uint8)
+    idxs = None if idxs is None else np.ascontiguousarray(idxs, dtype=np.uint32)
+    if mlen is None:
+        mlen = len(idxs) if idxs is not None else cols.size // (nall + 3)
+    par = snv_params() if par is None else np.ascontiguousarray(par, dtype=SNV_PARAMS).reshape(-1)[:1]
+    n, pexp, nsites = C.c_size_t(0), C.c_float(0), C.c_uint32(0)
+    snv, cap = None, 0
+    for _ in range(2):                                         # a count-only call says what is needed
+        rc = lib().bsa_msa_call_snvs(_p(cols), _p(idxs), nall, nseq, mlen, _p(par), _p(snv) if cap else None, cap, C.byref(n), C.byref(pexp), C.byref(nsites))
+        if rc != E_NOMEM:
+            break
+        cap = n.value
+        snv = np.zeros(cap, dtype=SNV_DTYPE)
+    if rc != 0:
+        raise BsaError(rc)
+    return (snv[:n.value] if cap else np.zeros(0, SNV_DTYPE)), float(np.float32(pexp.value)), nsites.value
+
+
+def snv_text(cols, nall, nseq, cns, qlt, snv, label, idxs=None, mlen=None):
+    """print_snvs_bspoa: the `<label> SNP` lines of the records, cns / qlt the compact consensus and its quality"""
+    cols = np.ascontiguousarray(cols, dtype=np.uint8)
+    idxs = None if idxs is None else np.ascontiguousarray(idxs, dtype=np.uint32)
+    if mlen is None:
+        mlen = len(idxs) if idxs is not None else cols.size // (nall + 3)
+    cns, qlt = (np.ascontiguousarray(a, dtype=np.uint8) for a in (cns, qlt))
+    snv = np.ascontiguousarray(snv, dtype=SNV_DTYPE)
+    return _two_pass(lambda o, cap, need: lib().bsa_msa_snv_text(_p(cols), _p(idxs), nall, nseq, mlen, _p(cns) if cns.size else None, _p(qlt) if qlt.size else None,
+                                                                 cns.size, _p(snv) if snv.size else None, snv.size, label.encode(), o, cap, C.byref(need)))

@@ -1058,6 +1058,68 @@ int  bsa_window_stitch_batch(bsa_ctx_t *ctx,
                              uint32_t *cig, size_t cig_cap, uint64_t *cig_off /* nwin + 1 */,
                              bsa_stitch_t *rec /* nwin */);
 
+/* bsa_window_snv_* : the SNVs of every window -- the columns where a second allele is too frequent to be sequencing error: bsa_msa_call_snvs
+ *                    (bsalign_msa.h, the reference's call_snvs_bspoa) on the resident columns, a few records a window where the MSA is gigabytes.
+ *                    The consensus keeps one allele a column; the evidence for the other is in the columns, and this pass reads it where it lies.
+ *                    A pass over public outputs (bsa_window_snv.hip): it touches no plan and changes no existing call.
+ * the model        : bsa_snv_model_create(ctx, max_rows, &model) uploads, once, everything that needs exp or log, computed by the host form's own code
+ *                    so that host and device share one libm: the log-factorial table, log(p) and log(1 - p) in double of the 100 grid rates and of
+ *                    0.01f, and for every (altn, covn), covn <= max_rows, whose own rate the host's float j admits to the grid (altn / covn below about
+ *                    0.05) its row of float weights with the first bin and the number of bins, stored sparsely: 20 rows at max_rows 40, 24 500 rows and
+ *                    under 10 MB at 1000.  max_rows above 1000 is BSA_E_UNSUPPORTED.  The model also sizes the kernels' LDS: 8.3 KB a wave at 40, 58 KB
+ *                    at 1000 -- make it as deep as the windows are, not deeper.  A model serves any number of runs on its context.
+ * inputs           : d_cols, d_cwin, cols_cap, d_cns_status as bsa_window_stitch_run takes them; the columns are READ-ONLY.  `par` is host memory, read
+ *                    at the call (defaults 3, 0.5, 5, 0; the chain's windows have no placeholder row: skip_first_row 0).
+ * a window's status: the readable-record test of bsa_window_stitch_run is the only door to the columns -- idxs_off == ~0, nall >= 1, mlen < 2^28, and
+ *                    cols_off + mlen * (nall + 3), formed in 64 bits, neither wraps nor exceeds cols_cap -- and here nseq <= nall belongs to it: a
+ *                    record that fails is BSA_SNV_ST_BAD_RECORD.  Then, in this order: nseq above the model's max_rows is BSA_SNV_ST_TOO_DEEP;  mlen >
+ *                    65535 is BSA_SNV_ST_TOO_LONG;  a non-zero d_cns_status[g] is BSA_SNV_ST_NOT_CALLED (the consensus bytes are not valid; a NULL array:
+ *                    every window counts).  A window with any status but BSA_SNV_ST_OK (0) has no records, nsites 0 and pexp 0.
+ * outputs          : d_rec[g] = { status, nsnv, nsites, pexp }: the records, the columns that entered the estimate, the estimated rate;  window g's
+ *                    records, bsa_snv_t as bsa_msa_call_snvs(cols + cols_off, NULL, nall, nseq, mlen, par, ...) writes them, in column order, at
+ *                    d_snv[d_snv_off[g] .. d_snv_off[g + 1]).  lpos counts the bases of row nall - 1, the draft: window * w + lpos is the site in draft
+ *                    coordinates, cpos the position in the window's consensus, mpos the column.  Every byte is the host form's.
+ * arena            : the house contract with the window as the unit.  For ANY snv_cap, 0 with a non-NULL arena and a NULL arena with cap 0 (count-only)
+ *                    included: all nwin + 1 entries of d_snv_off and all nwin records of d_rec are written and are those of a complete run;
+ *                    d_snv_off[nwin] is the need; window g's records are written, whole, if and only if d_snv_off[g + 1] <= snv_cap; nothing else is
+ *                    touched, the arena is not used as scratch.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the
+ *                    context's scratch (32 bytes a window and the scan's temporaries).  The columns are read twice by the wave that owns the window
+ *                    (the counts and the estimate, then the calls at the estimated rate) and a third time only for windows that have calls and whose
+ *                    records fit.  The output is a function of the inputs alone (the histogram is summed in integers); a run leaves nothing behind that
+ *                    a later run reads, whatever its parameters.
+ * _batch           : all pointers are HOST memory and max_rows takes the model's place.  It uploads the columns, the records, the statuses and the
+ *                    arena as it is, runs, downloads the offsets and window records FIRST and synchronises: a cap too small is BSA_E_CIGAR_CAP there,
+ *                    with the need in snv_off[nwin] and the arena untouched.  Then snv_off[nwin] records come down.
+ * errors (both)    : a NULL ctx, model, par or d_snv_off; with nwin > 0 a NULL d_cwin or d_rec; a cap without its arena (cols_cap without d_cols,
+ *                    snv_cap without d_snv); a model of another context; skip_first_row above 1 or min_covfrq outside [0, 65]; nwin or snv_cap above
+ *                    0xFFFFFFF0: BSA_E_ARG.  nwin == 0 writes d_snv_off[0] = 0 and nothing else.
+ * Example          : the five columns of bsa_msa_call_snvs's example (bsalign_msa.h) as one window, cwin = {0, ~0, 0, nall 4, nseq 4, nmax 4, mlen 5},
+ *                    cols_cap 35, par = {1, 0.5, 1, 0}, max_rows 4 -- d_rec[0] = {0, 2, 3, 0.01f}, d_snv_off = {0, 2},
+ *                      d_snv[0] = {mpos 1, cpos 1, lpos 1, qual 3, covn 4, refn 2, altn 2, refb 1, altb 3}
+ *                      d_snv[1] = {mpos 3, cpos 2, lpos 3, qual 1, covn 4, refn 3, altn 1, refb 2, altb 0}
+ *                    and behind the chain of the bsa_window_stitch_* example --
+ *                      bsa_snv_model_create(ctx, 40, &snv_model);
+ *                      bsa_window_snv_run(ctx, snv_model, d_cols, cols_cap, d_cwin, nwin, d_status, &par, d_snv, snv_cap, d_snv_off, d_rec); */
+#define BSA_SNV_ST_OK         0u
+#define BSA_SNV_ST_BAD_RECORD 1u
+#define BSA_SNV_ST_TOO_DEEP   2u
+#define BSA_SNV_ST_TOO_LONG   3u
+#define BSA_SNV_ST_NOT_CALLED 4u
+typedef struct { uint32_t status, nsnv, nsites; float pexp; } bsa_snv_window_t;          /* 16 bytes, one a window */
+typedef struct bsa_snv_model bsa_snv_model_t;
+int  bsa_snv_model_create(bsa_ctx_t *ctx, uint32_t max_rows, bsa_snv_model_t **out);
+void bsa_snv_model_destroy(bsa_snv_model_t *m);          /* NULL is fine */
+int  bsa_window_snv_run(bsa_ctx_t *ctx, const bsa_snv_model_t *model,
+                        const uint8_t *d_cols, size_t cols_cap, const bsa_cns_window_t *d_cwin, size_t nwin,
+                        const uint32_t *d_cns_status /* nwin, what bsa_window_cns_run wrote; NULL: every window counts */,
+                        const bsa_snv_params_t *par,
+                        bsa_snv_t *d_snv, size_t snv_cap, uint64_t *d_snv_off /* nwin + 1 */, bsa_snv_window_t *d_rec /* nwin */);
+int  bsa_window_snv_batch(bsa_ctx_t *ctx, uint32_t max_rows,
+                          const uint8_t *cols, size_t cols_cap, const bsa_cns_window_t *cwin, size_t nwin,
+                          const uint32_t *cns_status /* nwin, or NULL */, const bsa_snv_params_t *par,
+                          bsa_snv_t *snv, size_t snv_cap, uint64_t *snv_off /* nwin + 1 */, bsa_snv_window_t *rec /* nwin */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one

@@ -77,6 +77,49 @@ int bsa_msa_call_consensus_batch(struct bsa_ctx *ctx, uint8_t *cols, size_t cols
                                  const bsa_cns_window_t *win, size_t nwin, const bsa_cns_params_t *par,
                                  uint8_t *cns, uint8_t *qlt, uint8_t *alt, size_t out_bytes, uint32_t *clen, double *score);
 
+/* SNV calling of a window's MSA: call_snvs_bspoa (bspoa.h:4931-5049) on the same plain arrays, and print_snvs_bspoa (:5053-5089).  The third output of
+ * the reference's `poa` command beside the MSA and the consensus: the columns where a second allele is too frequent to be sequencing error.
+ *   cols / idxs   as above, mrow = nall + 3, READ-ONLY; byte nall of a column is the called consensus symbol (bsa_msa_call_consensus wrote it)
+ *   nseq          rows 0 .. nseq - 1 vote (nseq <= nall); with par->skip_first_row row 0 does not (the reference drops the empty placeholder row its
+ *                 command line makes), and realnseq = nseq - skip_first_row
+ * Per column  : cnt[c] = voting rows with code c, c <= 4; covn = their sum (codes 5 and above are not there).  The top two among A C G T only:
+ *               (m1, m2) = (0, 1) if cnt[0] >= cnt[1] else (1, 0); then for i = 2, 3: if cnt[i] > cnt[m1] { m2 = m1; m1 = i } else if cnt[i] > cnt[m2]
+ *               { m2 = i }.  refn = cnt[m1], altn = cnt[m2].  mincov = (uint16) max(2, (float) realnseq * min_covfrq).
+ * Error rate  : every column with refn + altn >= mincov is a SITE and adds one to the histogram entry (altn, covn).  On the grid p_i = i * 0.0005f,
+ *               i < 100, every non-zero entry, in ascending (altn, covn), with pexp = (float)(1.0 * altn / covn) and j = (int)(pexp / 0.0005f), 0 < j <
+ *               100, adds count * prob to the sums of the bins j - k and j + k, prob = (float) exp(B(covn, altn, pexp -/+ 0.0005f * k)), each direction
+ *               ending behind the first prob <= 0.01f; float multiply, float add, not fused.  B(n, m, p) = log(p) m + log(1 - p) (n - m) + LF[n] -
+ *               LF[m] - LF[n - m] in double, LF[k] = log(k!) by running summation.  The window's rate is the first grid value with the largest sum if
+ *               that sum exceeds 1, else 0.01f.  (altn / covn must be below 0.05 to count: windows of 20 rows or fewer always get 0.01f.)
+ * Calls       : a column is a call if altn >= min_varcnt, refn + altn >= mincov and qual >= min_snvqlt, qual = -((float) B(covn, altn, rate) / log(10))
+ *               truncated, at most 1000.  Records come in column order.
+ * The record  : mpos the column; cpos the number of columns in front whose consensus byte is below 4 (the reference's cpos: the position in the
+ *               consensus); lpos the same count for row nall - 1 -- in the window chain that row is the draft, so window * w + lpos is the site in draft
+ *               coordinates (the reference has no such field); refb = m1, refn, altb = m2, altn, covn, qual.
+ * Returns BSA_E_UNSUPPORTED for nseq > 1000 (beyond the log-factorial table the reference's formula changes meaning) and for mlen > 65535 (its 16-bit
+ * histogram would wrap); BSA_E_ARG for skip_first_row above 1 or min_covfrq outside [0, 65]; BSA_E_NOMEM with *nsnv = the records there are when
+ * snv_cap is smaller (the first snv_cap are written).  *pexp, *nsites (optional): the estimated rate and the number of sites.
+ * Example     : nall 4, nseq 4, mlen 5, defaults but min_varcnt 1, min_covfrq 0.5 (mincov 2), min_snvqlt 1; columns as rows | consensus --
+ *                 column 0   0 0 0 0 | 0    cnt 4 0 0 0  covn 4  m1 A m2 C  refn 4 altn 0   a site; altn 0 < 1: no call
+ *                 column 1   1 1 3 3 | 1    cnt 0 2 0 2  covn 4  m1 C m2 T  refn 2 altn 2   (T ties C and does not displace it)   a site; a candidate
+ *                 column 2   4 4 5 2 | 4    cnt 0 0 1 0  covn 3  m1 G m2 A  refn 1 altn 0   (the two gaps count for covn only)    refn + altn 1 < 2
+ *                 column 3   2 2 2 0 | 2    cnt 1 0 3 0  covn 4  m1 G m2 A  refn 3 altn 1   a site; a candidate
+ *                 column 4   3 6 6 6 | 3    cnt 0 0 0 1  covn 1  m1 T m2 A  refn 1 altn 0   refn + altn 1 < 2
+ *               three sites; 1 / 4 and 2 / 4 are not below 0.05, so no entry reaches the grid and the rate is 0.01f.
+ *                 column 1: B(4, 2, 0.01) = 2 log 0.01 + 2 log 0.99 + log 6 = -7.4387, qual = (int) 3.2306 = 3: a call, mpos 1 cpos 1 lpos 1 C 2 T 2
+ *                 column 3: B(4, 1, 0.01) = log 0.01 + 3 log 0.99 + log 4 = -3.2490, qual = (int) 1.4110 = 1: a call, mpos 3 cpos 2 lpos 3 G 3 A 1
+ *               (cpos 2 at column 3: column 2's consensus is a gap; lpos 3: its last row is a base.) */
+typedef struct { uint32_t mpos, cpos, lpos, qual; uint16_t covn, refn, altn; uint8_t refb, altb; } bsa_snv_t;       /* 24 bytes */
+typedef struct { int32_t min_varcnt; float min_covfrq; uint32_t min_snvqlt; uint32_t skip_first_row; } bsa_snv_params_t;   /* defaults 3, 0.5, 5, 0 */
+int bsa_msa_call_snvs(const uint8_t *cols, const uint32_t *idxs, uint32_t nall, uint32_t nseq, uint32_t mlen, const bsa_snv_params_t *par,
+                      bsa_snv_t *snv, size_t snv_cap, size_t *nsnv, float *pexp, uint32_t *nsites);
+/* print_snvs_bspoa: one `<label> SNP` line a record -- cpos, mpos, the five consensus bases in front and their qualities (+ '!'), reference base and
+ * count, alternative base and count, the five bases behind and their qualities, covn, qual, the column's rows 0 .. nseq - 1 as "ACGT-.*".  cns / qlt:
+ * the compact consensus and its quality (bsa_msa_consensus), clen bases.  Writers' convention: *need, BSA_E_NOMEM when cap is smaller. */
+int bsa_msa_snv_text(const uint8_t *cols, const uint32_t *idxs, uint32_t nall, uint32_t nseq, uint32_t mlen,
+                     const uint8_t *cns, const uint8_t *qlt, uint32_t clen, const bsa_snv_t *snv, size_t nsnv,
+                     const char *label, char *out, size_t cap, size_t *need);
+
 #ifdef __cplusplus
 }
 #endif
