@@ -95,6 +95,17 @@ class SELECT_PARAMS(C.Structure):
                 ("reserved", C.c_uint32 * 3)]
 
 
+class REALIGN_PARAMS(C.Structure):
+    """bsa_realign_params_t (bsa_window_realign_*): round 2's window size (a window's stitched sequence is at most that long), the longest piece, the
+    smallest band margin a piece may have, and the costs of a mismatch and of a gap unit"""
+    _fields_ = [("window2", C.c_uint32), ("max_len", C.c_uint32), ("min_margin", C.c_uint32), ("x", C.c_uint32), ("g", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def realign_params(window2, max_len=1024, min_margin=8, x=1, g=1):
+    """a bsa_realign_params_t"""
+    return REALIGN_PARAMS(int(window2), int(max_len), int(min_margin), int(x), int(g))
+
+
 RESULT_DTYPE = np.dtype([(n, np.int32) for n in ("score", "qb", "qe", "tb", "te", "mat", "mis", "ins", "del", "aln")])
 # bsa_piece_t (bsa_window_pieces_*): a read's piece in one window of the draft
 PIECE_DTYPE = np.dtype([("pair", np.uint32), ("q_first", np.uint32), ("len", np.uint32), ("t_first", np.uint32), ("t_last", np.uint32), ("reserved", np.uint32),
@@ -119,6 +130,9 @@ SNV_DTYPE = np.dtype([("mpos", np.uint32), ("cpos", np.uint32), ("lpos", np.uint
 SNV_WINDOW_DTYPE = np.dtype([("status", np.uint32), ("nsnv", np.uint32), ("nsites", np.uint32), ("pexp", np.float32)])
 SNV_PARAMS = np.dtype([("min_varcnt", np.int32), ("min_covfrq", np.float32), ("min_snvqlt", np.uint32), ("skip_first_row", np.uint32)])
 SNV_ST_OK, SNV_ST_BAD_RECORD, SNV_ST_TOO_DEEP, SNV_ST_TOO_LONG, SNV_ST_NOT_CALLED = 0, 1, 2, 3, 4
+# d_pstatus of bsa_window_realign_*: 0, or the first clause a piece fails (BSA_REALIGN_ST_*); REALIGN_ST_EDGE is a flag beside 0
+REALIGN_ST_OK, REALIGN_ST_NO_WINDOW, REALIGN_ST_BAD_PIECE, REALIGN_ST_TOO_LONG, REALIGN_ST_EMPTY_SPAN, REALIGN_ST_OFF_BAND, REALIGN_ST_NO_DIAG = 0, 1, 2, 3, 4, 5, 6
+REALIGN_ST_EDGE = 0x100
 
 
 def snv_params(min_varcnt=3, min_covfrq=0.5, min_snvqlt=5, skip_first_row=0):
@@ -259,6 +273,11 @@ def lib():
             L.bsa_window_stitch_run.argtypes = [vp, u8p, C.c_size_t, vp, C.c_size_t, u32p, C.c_uint32, u8p, u8p, u8p, C.c_size_t, u64p, u32p, C.c_size_t, u64p, vp]
             L.bsa_window_stitch_batch.argtypes = L.bsa_window_stitch_run.argtypes
             L.bsa_window_stitch_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_stitch_run.argtypes[1:]
+        if hasattr(L, "bsa_window_realign_run"):
+            L.bsa_window_realign_run.argtypes = [vp, vp, u64p, C.c_size_t, C.c_size_t, u8p, C.c_size_t, C.c_uint32, u8p, C.c_size_t, u64p, u32p, C.c_size_t, u64p,
+                                                 C.POINTER(REALIGN_PARAMS), vp, u32p, C.c_size_t, u64p, u32p, u32p, u64p, u32p]
+            L.bsa_window_realign_batch.argtypes = L.bsa_window_realign_run.argtypes
+            L.bsa_window_realign_step_internal.argtypes = [vp, C.c_int] + L.bsa_window_realign_run.argtypes[1:]
         L.bsa_snv_model_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
         L.bsa_snv_model_destroy.argtypes = [vp]
         L.bsa_snv_model_destroy.restype = None
@@ -1199,6 +1218,89 @@ class Context:
             a, b, c, d = int(soff[g]), int(soff[g + 1]), int(coff[g]), int(coff[g + 1])
             res.append((seq[a:b].copy(), sq[a:b].copy(), sa[a:b].copy(), cig[c:d].copy(), rec[g].copy()))
         return res, (seq, sq, sa, soff, cig, coff)
+
+    def window_realign_run(self, d_piece, d_piece_off, nwin, piece_cap, d_bases, bases_cap, window, d_seq, seq_cap, d_seq_off, d_cig, cig_cap, d_cig_off, par,
+                           d_piece2, d_pcig2, pcig2_cap, d_pcig2_off, d_pstatus, d_cost, d_doff2, d_dlen2):
+        """bsa_window_realign_run on torch tensors (plumbing only), asynchronous on the context's stream: d_piece, d_piece_off, d_bases as
+        window_pieces_run (or window_select_run) left them, `window` that round's window size, d_seq, d_seq_off, d_cig, d_cig_off as window_stitch_run
+        left them for the same windows, par a REALIGN_PARAMS (realign_params).  d_piece2: piece_cap records of 32 bytes; d_pcig2: room for pcig2_cap
+        32-bit words, or None with pcig2_cap 0 for a count-only run; d_pcig2_off: piece_cap + 1 64-bit words; d_pstatus and d_cost (or None): piece_cap
+        32-bit words; d_doff2 (64-bit) and d_dlen2 (32-bit): one entry a window.  Round 2 is window_msa_run(d_piece2, d_piece_off, nwin, piece_cap,
+        d_bases, bases_cap, d_pcig2, pcig2_cap, d_pcig2_off, d_seq, d_doff2, d_dlen2, par.window2, 0, vote, ...)."""
+        size = lambda t: t.numel() * t.element_size()
+        if any(t is not None and size(t) < 32 * piece_cap for t in (d_piece, d_piece2)):
+            raise ValueError("window_realign_run: d_piece or d_piece2 holds fewer than piece_cap records")
+        if any(t is not None and size(t) < 8 * (nwin + 1) for t in (d_piece_off, d_seq_off, d_cig_off)):
+            raise ValueError("window_realign_run: d_piece_off, d_seq_off or d_cig_off holds fewer than nwin + 1 offsets")
+        if d_bases is not None and size(d_bases) < bases_cap:
+            raise ValueError("window_realign_run: d_bases holds fewer than bases_cap bytes")
+        if d_seq is not None and size(d_seq) < seq_cap:
+            raise ValueError("window_realign_run: d_seq holds fewer than seq_cap bytes")
+        if d_cig is not None and size(d_cig) < 4 * cig_cap:
+            raise ValueError("window_realign_run: d_cig holds fewer than cig_cap words")
+        if d_pcig2 is not None and size(d_pcig2) < 4 * pcig2_cap:
+            raise ValueError("window_realign_run: d_pcig2 holds fewer than pcig2_cap words")
+        if d_pcig2_off is not None and size(d_pcig2_off) < 8 * (piece_cap + 1):
+            raise ValueError("window_realign_run: d_pcig2_off holds fewer than piece_cap + 1 offsets")
+        if any(t is not None and size(t) < 4 * piece_cap for t in (d_pstatus, d_cost)):
+            raise ValueError("window_realign_run: d_pstatus or d_cost holds fewer than piece_cap entries")
+        if (d_doff2 is not None and size(d_doff2) < 8 * nwin) or (d_dlen2 is not None and size(d_dlen2) < 4 * nwin):
+            raise ValueError("window_realign_run: d_doff2 or d_dlen2 holds fewer than nwin entries")
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self._chk(lib().bsa_window_realign_run(self.h, ptr(d_piece), ptr(d_piece_off), nwin, piece_cap, ptr(d_bases), bases_cap, int(window), ptr(d_seq), seq_cap,
+                                               ptr(d_seq_off), ptr(d_cig), cig_cap, ptr(d_cig_off), C.byref(par), ptr(d_piece2), ptr(d_pcig2), pcig2_cap,
+                                               ptr(d_pcig2_off), ptr(d_pstatus), ptr(d_cost), ptr(d_doff2), ptr(d_dlen2)))
+
+    def window_realign(self, windows_out, stitch_out, window, par):
+        """bsa_window_realign_batch on what Context.window_pieces or Context.window_select returned (the list over the windows of (pieces, codes)) and
+        what Context.window_stitch returned for the same windows: every piece aligned again, against its window's stitched sequence.  `window` is the
+        window size of that round, par a REALIGN_PARAMS (realign_params).  Returns the three things Context.window_msa takes, in the shape it takes
+        them -- (pieces, guides, drafts): the list over the windows of (piece records, codes) with t_first and t_last positions in the window's
+        stitched sequence and the codes cut to the re-aligned piece, the list over the windows of lists of (words, status) with status a
+        REALIGN_ST_* value (REALIGN_ST_EDGE set beside 0), and one code array a window, its stitched sequence.  A piece that is
+        not re-aligned has len 0, no codes and no words: a dead row of round 2."""
+        nwin = len(windows_out)
+        _, (seq, _, _, soff, cig, coff) = stitch_out
+        if len(soff) != nwin + 1 or len(coff) != nwin + 1:
+            raise ValueError("window_realign: the stitch of the same windows")
+        piece = _np(np.concatenate([np.zeros(0, PIECE_DTYPE)] + [_np(ps, PIECE_DTYPE) for ps, _ in windows_out]), PIECE_DTYPE).copy()
+        P = len(piece)
+        poff = np.zeros(nwin + 1, dtype=np.uint64)
+        poff[1:] = np.cumsum([len(ps) for ps, _ in windows_out], dtype=np.uint64)
+        codes = [_np(c, np.uint8) for _, cs in windows_out for c in cs]
+        if len(codes) != P:
+            raise ValueError("window_realign: one code array per piece")
+        boff = np.zeros(P + 1, dtype=np.uint64)
+        boff[1:] = np.cumsum([len(c) for c in codes], dtype=np.uint64)
+        piece["base_off"] = boff[:-1]                           # the codes as they are laid out here
+        bases = _np(np.concatenate([np.zeros(0, np.uint8)] + codes), np.uint8)
+        seq, cig = _np(seq, np.uint8), _np(cig, np.uint32)
+        soff, coff = _np(soff, np.uint64), _np(coff, np.uint64)
+        piece2 = np.zeros(max(P, 1), dtype=PIECE_DTYPE)
+        off2 = np.zeros(P + 1, dtype=np.uint64)
+        pst, cost = np.zeros(max(P, 1), np.uint32), np.zeros(max(P, 1), np.uint32)
+        doff2, dlen2 = np.zeros(max(nwin, 1), np.uint64), np.zeros(max(nwin, 1), np.uint32)
+        words, cap = None, 0
+        for _ in range(2):                                     # a count-only call says what is needed
+            rc = lib().bsa_window_realign_batch(self.h, _p(piece) if P else None, _p(poff), nwin, P, _p(bases) if len(bases) else None, len(bases), int(window),
+                                                _p(seq) if len(seq) else None, len(seq), _p(soff), _p(cig) if len(cig) else None, len(cig), _p(coff), C.byref(par),
+                                                _p(piece2), _p(words) if cap else None, cap, _p(off2), _p(pst), _p(cost), _p(doff2), _p(dlen2))
+            if rc != -5 or int(off2[P]) <= cap:
+                break
+            cap = int(off2[P])
+            words = np.zeros(cap, dtype=np.uint32)
+        self._chk(rc)
+        pieces, guides, drafts = [], [], []
+        for g in range(nwin):
+            a, b = int(poff[g]), int(poff[g + 1])
+            cs = []
+            for j in range(a, b):
+                lead = int(piece2[j]["base_off"]) - int(piece[j]["base_off"])
+                cs.append(codes[j][lead:lead + int(piece2[j]["len"])].copy())
+            pieces.append((piece2[a:b].copy(), cs))
+            guides.append([(words[int(off2[j]):int(off2[j + 1])].copy() if cap else np.zeros(0, np.uint32), int(pst[j])) for j in range(a, b)])
+            drafts.append(seq[int(doff2[g]):int(doff2[g]) + int(dlen2[g])].copy())
+        return pieces, guides, drafts
 
     def snv_model(self, max_rows):
         """bsa_snv_model_create: the SNV caller's tables for windows of up to max_rows voting rows (at most 1000) resident on the device, for

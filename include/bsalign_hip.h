@@ -1120,6 +1120,104 @@ int  bsa_window_snv_batch(bsa_ctx_t *ctx, uint32_t max_rows,
                           const uint32_t *cns_status /* nwin, or NULL */, const bsa_snv_params_t *par,
                           bsa_snv_t *snv, size_t snv_cap, uint64_t *snv_off /* nwin + 1 */, bsa_snv_window_t *rec /* nwin */);
 
+/* bsa_window_realign_* : every piece of a window aligned again, against the sequence bsa_window_stitch_* called for that window -- what a SECOND round inside the
+ *                    window needs.  Round 1's MSA is draft-anchored: every read was aligned on its own against a draft that is wrong in places, each piece's gaps
+ *                    sit where that one alignment put them, and two reads that carry the same missing base at different places of a homopolymer split their
+ *                    vote over two insertion columns.  This pass aligns every piece against its window's called sequence with one rule for every ambiguous gap
+ *                    (the leftmost place) and leaves the result in the shape bsa_window_msa_run takes: piece records, guides whose first and last word are
+ *                    diagonal, and the called sequence as the per-window draft.
+ *                    A pass over public outputs (bsa_window_realign.hip): it touches no plan and changes no existing call.
+ * inputs           : d_piece, d_piece_off (nwin + 1), d_bases are what bsa_window_pieces_run left (bsa_window_select_run's d_sel, d_sel_off with the same d_bases
+ *                    serve equally), piece_cap and bases_cap the room of d_piece and d_bases; `window` is that round's window size; d_seq, d_seq_off, d_cig,
+ *                    d_cig_off (nwin + 1 each) are what bsa_window_stitch_run left for the same windows, seq_cap and cig_cap the room of d_seq and d_cig.
+ *                    `par` is host memory, read at the call.  Precondition: d_piece_off does not decrease (every pass in front writes it so); where it does,
+ *                    nothing is read or written outside the caps, but which window a doubly claimed piece is lifted through is unspecified.
+ * liftable window  : window g is LIFTABLE if and only if all of these hold -- d_seq_off[g] <= d_seq_off[g + 1] <= seq_cap;  slen = d_seq_off[g + 1] - d_seq_off[g]
+ *                    <= window2;  d_cig_off[g] <= d_cig_off[g + 1] <= cig_cap;  every word has op I, D, = or X and a length of at least 1;  the units that consume
+ *                    a sequence base (=, X, I) sum to slen;  the units that consume a draft column (=, X, D) sum to Ld <= window (both sums in 64 bits).  This
+ *                    test is the only door to a window's words and bases.  A window that is not liftable has d_doff2[g] = 0, d_dlen2[g] = 0 and every piece of
+ *                    it gets BSA_REALIGN_ST_NO_WINDOW; a liftable window has d_doff2[g] = d_seq_off[g], d_dlen2[g] = slen.
+ * the lift         : draft column j of window g is the unit that consumes the j-th draft column, counting from 0; s(j) is the number of sequence-consuming
+ *                    units in front of that unit, k(j) is 1 if the unit is = or X and 0 if it is D.  For a piece, a = t_first % window and b = a + (t_last -
+ *                    t_first); its target is T = seq[d_seq_off[g] + u .. d_seq_off[g] + v] (inclusive) with u = s(a), v = s(b) + k(b) - 1, m = v - u + 1 bases.
+ *                    Bases inserted in front of column a are not in the span, just as the piece's row is 5 in those columns.
+ * a piece's status : the pieces of window g are piece_off[g] <= j < piece_off[g + 1] if piece_off[g] <= piece_off[g + 1] <= piece_cap, none otherwise; an index
+ *                    below piece_cap that is in no window, or in a window that is not liftable, gets BSA_REALIGN_ST_NO_WINDOW.  A piece of a liftable window
+ *                    is RE-ALIGNABLE if and only if all of these hold, and gets the status of the FIRST clause that fails, in this order, otherwise --
+ *                      n = len >= 1 (_BAD_PIECE)  and  len <= max_len (_TOO_LONG);   base_off + len <= bases_cap, in 64 bits (_BAD_PIECE);   t_last >= t_first
+ *                      (_BAD_PIECE);   b < Ld (_BAD_PIECE);   m >= 1 (_EMPTY_SPAN);   |m - n| <= 63 (_OFF_BAND);   margin = (63 - |m - n|) / 2 >= min_margin (_OFF_BAND).
+ * the DP           : a global alignment of the n codes & 3 against the m bases & 3 of T that minimises the cost -- a mismatch x, a gap unit g, a match 0, both in
+ *                    1 .. 255, linear gaps -- over the cells 0 <= i <= n, 0 <= jt <= m with dlo <= jt - i <= dlo + 63, dlo = min(0, m - n) - margin; every other
+ *                    cell is unreachable.  That is 64 fixed diagonals: both corners are always inside and a path always exists.  The traceback goes from (n, m)
+ *                    to (0, 0) and at every cell takes the FIRST step that explains the cell's value: the diagonal, then the target step (D), then the query
+ *                    step (I).  Every ambiguous gap so lies at its leftmost place, for every read alike.  d_cost[j] is the value at (n, m) (0 for a piece that
+ *                    is not re-alignable).  BSA_REALIGN_ST_EDGE, a flag bit beside status 0, is set if any cell of the path, the corners included, lies on
+ *                    diagonal dlo or dlo + 63: the piece to run again with another band, as BSA_MODE_BAND_MARGIN reports for the aligner.
+ * what leaves      : leading and trailing D and I steps are cut off; a path without a diagonal step is BSA_REALIGN_ST_NO_DIAG.  The words are the maximal runs
+ *                    of the remaining steps, len << 4 | op with BSA_CIGAR_M, _I, _D (the MSA pass takes M; = / X would cost a second comparison for nothing).
+ *                    d_piece2[j] keeps pair, has reserved = 0, q_first and base_off raised by the leading I units, len reduced by the leading and trailing I
+ *                    units, t_first = u + the leading D units and t_last = v - the trailing D units: positions in the window's own round-1 sequence, window-
+ *                    relative, so that nothing overflows and t_first % window2 is the column.  A piece with any status but 0 (or 0 | _EDGE) is DEAD: its
+ *                    record is its input record with len = 0, and it has no words.  d_piece_off is reused unchanged in round 2: piece j stays row j -
+ *                    piece_off[g] of window g, a dead piece is a dead row there, and every re-aligned piece is live under bsa_window_msa_run's predicate
+ *                    with window = window2 and L = slen.
+ * round 2          : bsa_window_msa_run(ctx, d_piece2, d_piece_off, nwin, piece_cap, d_bases, bases_cap, d_pcig2, pcig2_cap, d_pcig2_off, d_seq, d_doff2,
+ *                    d_dlen2, par.window2, 0, vote, ...), then the consensus and the stitch as before, nothing coming down in between.  The words a round-2
+ *                    stitch writes are against the ROUND-1 SEQUENCE, not against the original draft; composing the two word arenas is not part of this pass.
+ * Example 1        : the window of bsa_window_stitch_*'s example 2 -- seq 0 1 2 3 2 0 1 2 3 0 1, words 4= 1I 6=, window 10 -- and a piece {pair 9, q_first 100,
+ *                    len 6, t 32..37, base_off 0} with the codes 2 3 2 0 2 3, par = {window2 16, max_len 64, min_margin 8, x 1, g 1}: a = 2, b = 7, u = s(2) = 2,
+ *                    v = s(7) + 1 - 1 = 8, T = 2 3 2 0 1 2 3, m = 7, margin 31; the cost is 1, the path 4M 1D 2M (the sequence's 1 is missing in the read),
+ *                    d_piece2 = {9, 100, 6, t 2..8, 0, base_off 0}, status 0, d_doff2 = 0, d_dlen2 = 11.
+ * Example 2        : a and b on D units: window 8, seq 0 1 2 3 0, words 2= 2D 3= 1D (Ld 8, slen 5), a piece {pair 3, q_first 10, len 5, t 2..7, base_off 0}
+ *                    with the codes 1 2 3 0 2, window2 8: a = 2, b = 7, u = s(2) = 2, v = s(7) + 0 - 1 = 4, T = 2 3 0, m = 3, margin 30; the cost is 2, the
+ *                    path 1I 3M 1I, both I steps are cut: words 3M, d_piece2 = {3, 11, 3, t 2..4, 0, base_off 1}.
+ * _run             : DEVICE pointers; asynchronous on the context stream; no host/device copy, no synchronisation -- except that it may grow the context's
+ *                    scratch (a run that has to grow it may synchronise once; BSA_E_NOMEM when it cannot): 20 bytes a piece of piece_cap, the scan's
+ *                    temporaries, and (2 max_len + 63) / 4 bytes a piece for the paths (2 bits a step) -- make max_len as long as the pieces are, not longer.
+ *                    max_len also sizes the DP kernel's LDS (a wave a piece: 16 bytes a row for the directions and the two sequences, about 11 KB at 600,
+ *                    37 KB at 2048).  The DP of a piece runs once a run.
+ * arena            : the contract of bsa_piece_cigars_run with the piece as the unit and piece_cap + 1 offsets.  For ANY pcig2_cap, 0 with a non-NULL d_pcig2 and
+ *                    a NULL d_pcig2 with cap 0 (a count-only run) included:
+ *                      - every entry of d_pcig2_off, d_pstatus, d_piece2, d_cost (if given), d_doff2 and d_dlen2 is written and is that of a run with a large
+ *                        arena; d_pcig2_off[piece_cap] is the number of words needed;
+ *                      - piece j's words are there, whole, if and only if d_pcig2_off[j + 1] <= pcig2_cap;
+ *                      - nothing else is touched, nothing at or above pcig2_cap; the arena is never used as scratch.
+ *                    The output is a function of the inputs alone; a run leaves nothing behind that a later run reads.  The sum over the pieces of 2 len + 63
+ *                    words always suffices; a count-only run gives the exact need.
+ * _batch           : all pointers are HOST memory.  It uploads the arrays as they are, runs, downloads the offsets, statuses and records FIRST and
+ *                    synchronises: pcig2_cap too small is BSA_E_CIGAR_CAP there, pcig2_off[piece_cap] = the words needed, pcig2 untouched.
+ * errors (both)    : window2 above 4096 (bsa_window_msa_run's limit) or max_len above 2048: BSA_E_UNSUPPORTED.  A NULL ctx or par; window, window2, max_len, x or
+ *                    g of 0; x or g above 255; min_margin above 31; non-zero reserved; a NULL d_pcig2_off; with nwin > 0 a NULL d_piece_off, d_seq_off,
+ *                    d_cig_off, d_doff2 or d_dlen2; with piece_cap > 0 a NULL d_piece, d_piece2 or d_pstatus; a cap without its arena; nwin, piece_cap or
+ *                    pcig2_cap above 0xFFFFFFF0: BSA_E_ARG.  nwin == 0 writes d_pcig2_off[0 .. piece_cap] as 0 and every status BSA_REALIGN_ST_NO_WINDOW. */
+#define BSA_REALIGN_ST_OK         0u
+#define BSA_REALIGN_ST_NO_WINDOW  1u   /* in no window, or in a window that is not liftable */
+#define BSA_REALIGN_ST_BAD_PIECE  2u   /* len 0, codes outside bases_cap, t_last < t_first, or b outside the window's draft columns */
+#define BSA_REALIGN_ST_TOO_LONG   3u   /* len above max_len */
+#define BSA_REALIGN_ST_EMPTY_SPAN 4u   /* the called sequence has no base on the piece's columns */
+#define BSA_REALIGN_ST_OFF_BAND   5u   /* |m - n| above 63, or a margin below min_margin */
+#define BSA_REALIGN_ST_NO_DIAG    6u   /* the best path has no diagonal step */
+#define BSA_REALIGN_ST_EDGE   0x100u   /* flag beside status 0: the path touches the first or the last diagonal of the band */
+typedef struct { uint32_t window2, max_len, min_margin, x, g, reserved[3]; } bsa_realign_params_t;   /* 32 bytes */
+int  bsa_window_realign_run(bsa_ctx_t *ctx,
+                            const bsa_piece_t *d_piece, const uint64_t *d_piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                            const uint8_t *d_bases, size_t bases_cap, uint32_t window,
+                            const uint8_t *d_seq, size_t seq_cap, const uint64_t *d_seq_off /* nwin + 1 */,
+                            const uint32_t *d_cig, size_t cig_cap, const uint64_t *d_cig_off /* nwin + 1 */,
+                            const bsa_realign_params_t *par,
+                            bsa_piece_t *d_piece2 /* piece_cap */, uint32_t *d_pcig2, size_t pcig2_cap, uint64_t *d_pcig2_off /* piece_cap + 1 */,
+                            uint32_t *d_pstatus /* piece_cap */, uint32_t *d_cost /* piece_cap, or NULL */,
+                            uint64_t *d_doff2 /* nwin */, uint32_t *d_dlen2 /* nwin */);
+int  bsa_window_realign_batch(bsa_ctx_t *ctx,
+                              const bsa_piece_t *piece, const uint64_t *piece_off /* nwin + 1 */, size_t nwin, size_t piece_cap,
+                              const uint8_t *bases, size_t bases_cap, uint32_t window,
+                              const uint8_t *seq, size_t seq_cap, const uint64_t *seq_off /* nwin + 1 */,
+                              const uint32_t *cig, size_t cig_cap, const uint64_t *cig_off /* nwin + 1 */,
+                              const bsa_realign_params_t *par,
+                              bsa_piece_t *piece2 /* piece_cap */, uint32_t *pcig2, size_t pcig2_cap, uint64_t *pcig2_off /* piece_cap + 1 */,
+                              uint32_t *pstatus /* piece_cap */, uint32_t *cost /* piece_cap, or NULL */,
+                              uint64_t *doff2 /* nwin */, uint32_t *dlen2 /* nwin */);
+
 /* ---- row-level kernels for the POA seq->graph DP (P4; reference bspoa.h:2232-2272) ----------------------------
  * The POA sweep calls, per graph edge u -> v, row_movx + row_cal on u's DP row (dpalign_row_update_bspoa) and, per
  * extra in-edge, row_merge (dpalign_row_merge_bspoa).  bsa_rows_run executes a batch of such INDEPENDENT tasks (one
